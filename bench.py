@@ -7,10 +7,17 @@ One "step" = forward over the whole batch, then inverse over the whole batch (2 
 Multi-GPU: one process per GPU (torch.distributed / RCCL), polynomials sharded, no data-path collective,
 weak scaling (4096 polynomials per GPU).  `python bench.py --gpus N` without a launcher starts the N ranks itself.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel, HIP-event
-timed on the launch stream), `verified` (the timed buffers are checked: round trip == identity over the whole run,
-forward == the CPU oracle on 64 polynomials) and, at N = 1, `cpu_baseline` (the oracle's C restatement timed on host
-cores).  Secondary blocks (`ntt_mul`, `fhew`, `ckks`, `tfhe`) carry their own roofline (SURVEY.md 8(d) bytes) and CPU figure.
+Prints ONE JSON line on rank 0 (contract in the task statement) with `ms_per_step` and `roofline` (dominant kernel, HIP-event
+timed on the launch stream).  A plain run does only that: set-up, pre-heat and warm-up, the timed steps, the line.
+
+`--full` adds everything else, outside the timed region: `verified` (the timed buffers are checked: round trip == identity over the
+whole run, forward == the CPU oracle on 64 polynomials), at N = 1 `cpu_baseline` (the oracle's C restatement timed on host cores) and
+the secondary blocks (`ntt_mul`, `fhew`, `ckks`, `tfhe`) with their own roofline (SURVEY.md 8(d) bytes) and CPU figure, at N > 1 `sharded`.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last step computed on a fixed sample of 64 polynomials (rank 0's shard):
+`ntt_fwd.npy` (its forward transform) and `ntt_inv.npy` (its inverse, i.e. the buffer the step leaves).  The u64 residues go out as
+float64 of shape (64, 2^14, 2): [..., 0] the low 32 bits, [..., 1] the high bits, both exact.  The inputs are seeded: the same arguments
+give the same inputs in every run.
 """
 import argparse
 import json
@@ -469,15 +476,21 @@ def main():
     ap.add_argument("--batch", type=int, default=BATCH, help="polynomials per GPU (default: BASELINE cfg2)")
     ap.add_argument("--preheat-ms", type=float, default=100.0,
                     help="untimed run of the same kernels before the warm-up steps: the GPU needs ~10 ms of load to settle its clocks")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: verify the timed buffers, time the secondary blocks and the CPU baselines (N = 1), "
+                         "the sharded secondary figures (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed (a fixed sample) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--gather", action="store_true", help="also time the final all_gather of results (not in value)")
-    ap.add_argument("--no-fhew", action="store_true", help="skip the secondary figures (ring product, cfg3 FHEW, cfg4 CKKS, cfg5 TFHE)")
-    ap.add_argument("--no-verify-secondary", action="store_true", help="skip the oracle comparison of the secondary blocks (profiling passes)")
+    ap.add_argument("--no-fhew", action="store_true", help="with --full: skip the secondary figures (ring product, cfg3 FHEW, cfg4 CKKS, cfg5 TFHE)")
+    ap.add_argument("--no-verify-secondary", action="store_true", help="with --full: skip the oracle comparison of the secondary blocks (profiling passes)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for N > 1 (nccl = RCCL over xGMI; gloo only to rehearse the control path)")
     ap.add_argument("--single-device", action="store_true",
                     help="rehearsal on a 1-GPU box: every rank uses cuda:0 (only meaningful with --dist-backend gloo)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -520,7 +533,14 @@ def main():
     gen = torch.Generator(device=dev)
     gen.manual_seed(2 + rank)
     a = torch.randint(0, Q, (batch, n), dtype=torch.int64, device=dev, generator=gen)
-    a_init = a.clone()  # the run is forward+inverse pairs: at the end the buffer must equal this, bit for bit
+    a_init = a.clone() if args.full else None  # the run is forward+inverse pairs: at the end the buffer must equal this, bit for bit
+    dump = args.dump_outputs is not None and rank == 0
+    if dump:  # a fixed sample of rank 0's polynomials; the forward output of the last step is gathered into fwd_out
+        import numpy as np
+        pick = np.sort(np.random.Generator(np.random.PCG64(11)).choice(batch, size=min(64, batch), replace=False))
+        pick = torch.from_numpy(pick).to(dev)
+        fwd_out = torch.empty((pick.numel(), n), dtype=torch.int64, device=dev)
+        inv_mark = torch.cuda.Event(enable_timing=True)
 
     def barrier():
         torch.cuda.synchronize()
@@ -545,10 +565,14 @@ def main():
     ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.steps)]
     barrier()
     t0 = time.perf_counter()
+    last = args.steps - 1
     for s in range(args.steps):
         ev[s][0].record()
         ctx.ntt_(a, n)
         ev[s][1].record()
+        if dump and s == last:  # the sample of the last forward output, before the inverse overwrites it (not in inv_ms)
+            torch.index_select(a, 0, pick, out=fwd_out)
+            inv_mark.record()
         ctx.intt_(a, n)
         ev[s][2].record()
     barrier()
@@ -558,21 +582,34 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     fwd_ms = sum(e[0].elapsed_time(e[1]) for e in ev) / args.steps
-    inv_ms = sum(e[1].elapsed_time(e[2]) for e in ev) / args.steps
+    inv_ms = sum((inv_mark if dump and s == last else e[1]).elapsed_time(e[2]) for s, e in enumerate(ev)) / args.steps
 
-    # ---- verification of what was timed (outside the timed region) ----
-    import numpy as np
-    from oracle import cref  # the checker, never the thing measured
-    round_trip_ok = bool(torch.equal(a, a_init))
-    chk = a_init[:64].clone()
-    ctx.ntt_(chk, n)
-    fwd_ok = bool(np.array_equal(chk.cpu().numpy().view(np.uint64).reshape(-1),
-                                 cref.ntt_fwd(Q, a_init[:64].cpu().numpy().view(np.uint64).reshape(-1), n, threads=8)))
-    verified = round_trip_ok and fwd_ok
-    if dist is not None:
-        v = torch.tensor([1.0 if verified else 0.0], dtype=torch.float64, device=dev if args.dist_backend == "nccl" else "cpu")
-        dist.all_reduce(v, op=dist.ReduceOp.MIN)
-        verified = bool(v.item() == 1.0)
+    if dump:  # what the last step computed, outside the timed region
+        import numpy as np
+
+        def words(t):  # u64 residues as exact float64 32-bit words: [..., 0] low, [..., 1] high
+            u = t.cpu().numpy().view(np.uint64)
+            return np.stack([(u & np.uint64(0xFFFFFFFF)).astype(np.float64), (u >> np.uint64(32)).astype(np.float64)], axis=-1)
+
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "ntt_fwd.npy"), words(fwd_out))
+        np.save(os.path.join(args.dump_outputs, "ntt_inv.npy"), words(a.index_select(0, pick)))
+
+    # ---- --full: verification of what was timed (outside the timed region) ----
+    verified = True
+    if args.full:
+        import numpy as np
+        from oracle import cref  # the checker, never the thing measured
+        round_trip_ok = bool(torch.equal(a, a_init))
+        chk = a_init[:64].clone()
+        ctx.ntt_(chk, n)
+        fwd_ok = bool(np.array_equal(chk.cpu().numpy().view(np.uint64).reshape(-1),
+                                     cref.ntt_fwd(Q, a_init[:64].cpu().numpy().view(np.uint64).reshape(-1), n, threads=8)))
+        verified = round_trip_ok and fwd_ok
+        if dist is not None:
+            v = torch.tensor([1.0 if verified else 0.0], dtype=torch.float64, device=dev if args.dist_backend == "nccl" else "cpu")
+            dist.all_reduce(v, op=dist.ReduceOp.MIN)
+            verified = bool(v.item() == 1.0)
 
     gather_ms = None
     if args.gather and dist is not None:
@@ -584,7 +621,7 @@ def main():
         gather_ms = (time.perf_counter() - t0) * 1e3
 
     sharded = None
-    if dist is not None and not args.no_fhew:
+    if dist is not None and args.full and not args.no_fhew:
         try:  # extras: a failure here (the same code runs on every rank, so it fails on every rank) must not cost the headline line
             sharded = sharded_secondary(torch, F, dist, dev, local_rank, rank, world, args.dist_backend)
         except Exception as e:  # noqa: BLE001
@@ -603,9 +640,6 @@ def main():
             "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup, "preheat_ms": preheat_ms,
             "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "u64", "data": "synthetic",
-            "verified": verified,
-            "verification": {"round_trip_after_%d_fwd_inv_pairs_is_identity" % (preheat_steps + args.warmup + args.steps): round_trip_ok,
-                             "forward_of_64_polynomials_equals_cpu_oracle": fwd_ok},
             "config": {"workload": "cfg2: batched forward+inverse negacyclic NTT, N=2^14, q=%d, batch=%d per GPU, "
                                    "HBM-resident" % (Q, args.batch), "n": n, "q": Q, "batch_per_gpu": args.batch,
                        "parallelism": "batch-sharded x%d, no data-path collective" % n_gpus},
@@ -624,6 +658,10 @@ def main():
                          "issue": issue_block("inv", inv_ms, batch, cus, pmc, isa), "fwd_issue": issue_block("fwd", fwd_ms, batch, cus, pmc, isa),
                          "secondary_bound": "VALU issue (64-bit modular butterflies on 32-bit multipliers): see DESIGN.md 4.3"},
         }
+        if args.full:
+            out["verified"] = verified
+            out["verification"] = {"round_trip_after_%d_fwd_inv_pairs_is_identity" % (preheat_steps + args.warmup + args.steps): round_trip_ok,
+                                   "forward_of_64_polynomials_equals_cpu_oracle": fwd_ok}
         prop = torch.cuda.get_device_properties(dev)
         out["device"] = {"name": prop.name, "compute_units": prop.multi_processor_count, "max_clock_mhz": getattr(prop, "clock_rate", 2400000) / 1e3,  # torch builds without the field: the 2.4 GHz specification
                          "hbm_gib": round(prop.total_memory / 2 ** 30, 1), "hbm_peak_gbs_used": HBM_PEAK_GBS}
@@ -631,7 +669,7 @@ def main():
             out["final_gather_ms"] = gather_ms
         if sharded is not None:
             out["sharded"] = sharded
-        if n_gpus == 1 and not args.no_fhew:
+        if n_gpus == 1 and args.full and not args.no_fhew:
             vs = not args.no_verify_secondary
             out["ntt_mul"] = ntt_mul_bench(torch, F, dev, local_rank, min(args.batch, 2048), verify=vs)
             out["fhew"] = fhew_bench(torch, F, dev, local_rank, verify=vs)
@@ -640,7 +678,7 @@ def main():
             if vs:  # what the secondary blocks time is checked too: one oracle comparison per block, outside its timed region
                 out["verified_secondary"] = {k: out[k].get("verified") for k in ("ntt_mul", "fhew", "ckks", "tfhe")}
                 secondary_ok = all(v is True for v in out["verified_secondary"].values())
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if n_gpus == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
             if not args.no_fhew:
                 sec = cpu_secondary_baselines()

@@ -8,5 +8,5 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 for occ in 2 3 4; do
   echo "== occ $occ"
-  FHE_RING_LIB=$R/tools/libfhe_occ$occ.so python3 $R/bench.py --no-cpu-baseline --steps 3 --warmup 1 | python3 -c "import sys,json; d=json.loads([l for l in sys.stdin if l.startswith('{')][0]); print(d['fhew']); print(d['tfhe'])"
+  FHE_RING_LIB=$R/tools/libfhe_occ$occ.so python3 $R/bench.py --full --no-cpu-baseline --steps 3 --warmup 1 | python3 -c "import sys,json; d=json.loads([l for l in sys.stdin if l.startswith('{')][0]); print(d['fhew']); print(d['tfhe'])"
 done

@@ -1,12 +1,14 @@
 #!/bin/bash
 # instruction-cache counters of the transform kernels (default bench command, short)
 R=${GRAFT_REPO_ROOT:-$(pwd)}
+O=${PROFILE_OUT:-$R/profile_out}  # profiler output and logs (kept out of git)
+mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rm -rf $R/gpurun_out/pmc_icache
-rocprofv3 --kernel-trace --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_IFETCH SQ_WAVES SQ_BUSY_CYCLES --output-format csv -d $R/gpurun_out/pmc_icache -- python3 $R/bench.py --no-cpu-baseline --steps 5 --warmup 2 --preheat-ms 0 > $R/gpurun_out/pmc_icache.log 2>&1
+rm -rf $O/pmc_icache
+rocprofv3 --kernel-trace --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_IFETCH SQ_WAVES SQ_BUSY_CYCLES --output-format csv -d $O/pmc_icache -- python3 $R/bench.py --full --no-cpu-baseline --steps 5 --warmup 2 --preheat-ms 0 > $O/pmc_icache.log 2>&1
 python3 - <<PY
 import csv,glob,collections
-f=sorted(glob.glob("$R/gpurun_out/pmc_icache/**/*counter_collection.csv",recursive=True))[-1]
+f=sorted(glob.glob("$O/pmc_icache/**/*counter_collection.csv",recursive=True))[-1]
 acc=collections.defaultdict(lambda: collections.defaultdict(float)); best={}
 for r in csv.DictReader(open(f)):
     n=r["Kernel_Name"]

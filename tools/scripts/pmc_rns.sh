@@ -1,12 +1,14 @@
 #!/bin/bash
 # SQ counters of the cfg4 kernels (bench.py secondary block), one counter pass; prints per-kernel sums for the batch-64 launches
 R=${GRAFT_REPO_ROOT:-$(pwd)}
+O=${PROFILE_OUT:-$R/profile_out}  # profiler output and logs (kept out of git)
+mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rm -rf $R/gpurun_out/pmc_rns
-rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES --output-format csv -d $R/gpurun_out/pmc_rns -- python3 $R/bench.py --no-cpu-baseline --steps 2 --warmup 1 --preheat-ms 0 > $R/gpurun_out/pmc_rns.log 2>&1
+rm -rf $O/pmc_rns
+rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES --output-format csv -d $O/pmc_rns -- python3 $R/bench.py --full --no-cpu-baseline --steps 2 --warmup 1 --preheat-ms 0 > $O/pmc_rns.log 2>&1
 python3 - <<PY
 import csv,glob,collections
-f=sorted(glob.glob("$R/gpurun_out/pmc_rns/**/*counter_collection.csv",recursive=True))[-1]
+f=sorted(glob.glob("$O/pmc_rns/**/*counter_collection.csv",recursive=True))[-1]
 acc=collections.defaultdict(lambda: collections.defaultdict(float)); best={}
 for r in csv.DictReader(open(f)):
     n=r["Kernel_Name"]
