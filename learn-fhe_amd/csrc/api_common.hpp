@@ -134,7 +134,54 @@ inline int current_cu_count() {
     if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 256; }
     return cu_count(dev);
 }
+
+// blocks of 256 threads for `total` items of a grid-stride kernel: at least one, at most `cap`
+inline unsigned grid_for(size_t total, unsigned cap = 16384) {
+    size_t b = (total + 255) / 256;
+    return (unsigned)(b > cap ? cap : (b ? b : 1));
+}
+
+// K's dynamic-LDS limit on the current device, raised to at least `lds`.  Registered per (kernel, device) at the largest size
+// asked for so far: once that covers the call, one acquire load and no lock; the slow path only ever raises the limit.
+template <auto K>
+int raise_lds(size_t lds) {
+    static std::atomic<size_t> registered[MAX_DEVICES];
+    static std::mutex mu;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess && (dev < 0 || dev >= MAX_DEVICES)) e = hipErrorInvalidDevice;
+    if (e == hipSuccess && registered[dev].load(std::memory_order_acquire) < lds) {
+        std::lock_guard<std::mutex> lock(mu);
+        if (registered[dev].load(std::memory_order_relaxed) < lds) {
+            e = hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e == hipSuccess) registered[dev].store(lds, std::memory_order_release);
+        }
+    }
+    if (e != hipSuccess) { g_last_hip = (int)e; return FHE_ERR_HIP; }
+    return FHE_OK;
+}
+
+// Every kernel launch of the library: raises K's LDS limit above 64 KiB (raise_lds), launches, and returns FHE_OK or
+// FHE_ERR_HIP with g_last_hip set.
+template <auto K, class... A>
+int launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
+    if (lds > 64 * 1024) {
+        const int rc = raise_lds<K>(lds);
+        if (rc != FHE_OK) return rc;
+    }
+    hipLaunchKernelGGL(K, grid, block, lds, st, args...);
+    HIP_TRY(hipGetLastError());
+    return FHE_OK;
+}
 }  // namespace fhe
+using fhe::grid_for;
+
+// returns from the enclosing function with the FHE_* status of `expr` unless it is FHE_OK
+#define FHE_TRY(expr)                   \
+    do {                                \
+        const int rc_ = (expr);         \
+        if (rc_ != FHE_OK) return rc_;  \
+    } while (0)
 
 namespace {
 struct StreamWs {

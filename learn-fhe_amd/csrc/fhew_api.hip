@@ -54,10 +54,8 @@ int make_decomp(uint64_t q, int log_b, int d, fhe::DecompParams *P) {
     return FHE_OK;
 }
 
-inline unsigned grid_for(size_t total) {
-    size_t b = (total + 255) / 256;
-    return (unsigned)(b > 8192 ? 8192 : (b ? b : 1));
-}
+// the grid-stride launches of this unit stop at 8192 blocks (api_common.hpp grid_for: 16384)
+inline unsigned fhew_grid(size_t total) { return grid_for(total, 8192); }
 
 fhe::RingConsts ring_consts(const fhe_ctx *c, int) {
     fhe::RingConsts K;
@@ -91,12 +89,6 @@ inline int fhew_pm(const fhe_ctx *c, int log_n) { return ((c->pm_b == 54 || c->p
         default: return FHE_ERR_UNSUPPORTED;                               \
     }
 
-template <typename K>
-int set_lds(K kern, size_t bytes) {
-    if (bytes > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return FHE_OK;
-}
-
 int key_prepare(const fhe_ctx *ctx, int log_b, int d, int rows_per_ct, const uint64_t *rows_a, const uint64_t *rows_b, size_t n,
                 size_t count, fhe_mem mem, fhe_key **out) {
     if (!out) return FHE_ERR_INVALID;
@@ -125,18 +117,16 @@ int key_prepare(const fhe_ctx *ctx, int log_b, int d, int rows_per_ct, const uin
     // rows -> evaluation domain once (what Rgsw::internal_product does per call, rgsw.rs:136-138)
     if (rc == FHE_OK) rc = fhe::ntt_fwd_device(ctx, ta, log_n, 2 * rows, st);
     if (rc == FHE_OK) {
-        FHEW_DISPATCH(log_n, hipLaunchKernelGGL(fhe::key_permute_kernel<fhe::WaveRing<LN>>, dim3(grid_for(words)), dim3(256), 0, st, ta, tb, dst, rows,
-                                                 fhew_pm(ctx, log_n)));
-        if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
+        FHEW_DISPATCH(log_n, rc = fhe::launch<fhe::key_permute_kernel<fhe::WaveRing<LN>>>(fhew_grid(words), 256, 0, st, ta, tb, dst, rows,
+                                                                                           fhew_pm(ctx, log_n)));
     }
     u64 *dst_small = nullptr;
     if (rc == FHE_OK && log_n >= 10) {
         if (hipMalloc((void **)&dst_small, 2 * words * sizeof(u64)) != hipSuccess) rc = FHE_ERR_HIP;
         if (rc == FHE_OK) {
             const int pm = fhew_pm(ctx, log_n);
-            if (log_n == 10) hipLaunchKernelGGL((fhe::key_permute_kernel<fhe::WaveRing<10, 2>>), dim3(grid_for(words)), dim3(256), 0, st, ta, tb, dst_small, rows, pm);
-            else hipLaunchKernelGGL((fhe::key_permute_kernel<fhe::WaveRing<11, 2>>), dim3(grid_for(words)), dim3(256), 0, st, ta, tb, dst_small, rows, pm);
-            if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
+            if (log_n == 10) rc = fhe::launch<fhe::key_permute_kernel<fhe::WaveRing<10, 2>>>(fhew_grid(words), 256, 0, st, ta, tb, dst_small, rows, pm);
+            else rc = fhe::launch<fhe::key_permute_kernel<fhe::WaveRing<11, 2>>>(fhew_grid(words), 256, 0, st, ta, tb, dst_small, rows, pm);
         }
     }
     if (hipStreamSynchronize(st) != hipSuccess && rc == FHE_OK) rc = FHE_ERR_HIP;
@@ -201,8 +191,7 @@ int fhe_decompose(uint64_t q, int log_b, int d, const uint64_t *in, size_t n, si
     hipStream_t st = (hipStream_t)stream;
     Mirror mi(in, n * polys, mem, true, st), mo(out, n * polys * d, mem, false, st);
     if (mi.rc != FHE_OK || mo.rc != FHE_OK) return FHE_ERR_HIP;
-    hipLaunchKernelGGL(fhe::decompose_kernel, dim3(grid_for(n * polys)), dim3(256), 0, st, mi.d, mo.d, n, polys, P);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::decompose_kernel>(fhew_grid(n * polys), 256, 0, st, mi.d, mo.d, n, polys, P));
     return mo.sync_out(st);
 }
 
@@ -219,8 +208,7 @@ int fhe_automorphism(uint64_t q, int64_t t, const uint64_t *in, uint64_t *out, s
     if (mi.rc != FHE_OK || mo.rc != FHE_OK) return FHE_ERR_HIP;
     // `let mut v = self.clone()` (avec.rs:36): positions no X^(i t) lands on keep the input value (even t)
     HIP_TRY(hipMemcpyAsync(mo.d, mi.d, n * batch * sizeof(u64), hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(fhe::automorphism_kernel, dim3(grid_for(n * batch)), dim3(256), 0, st, mi.d, mo.d, (unsigned)n, batch, tt, (u64)q);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::automorphism_kernel>(fhew_grid(n * batch), 256, 0, st, mi.d, mo.d, (unsigned)n, batch, tt, (u64)q));
     return mo.sync_out(st);
 }
 
@@ -235,8 +223,7 @@ int fhe_monomial_mul(uint64_t q, int64_t k, const uint64_t *in, uint64_t *out, s
     hipStream_t st = (hipStream_t)stream;
     Mirror mi(in, n * batch, mem, true, st), mo(out, n * batch, mem, false, st);
     if (mi.rc != FHE_OK || mo.rc != FHE_OK) return FHE_ERR_HIP;
-    hipLaunchKernelGGL(fhe::monomial_mul_kernel, dim3(grid_for(n * batch)), dim3(256), 0, st, mi.d, mo.d, (unsigned)n, batch, kk, (u64)q);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::monomial_mul_kernel>(fhew_grid(n * batch), 256, 0, st, mi.d, mo.d, (unsigned)n, batch, kk, (u64)q));
     return mo.sync_out(st);
 }
 
@@ -279,15 +266,10 @@ static int gadget_entry(const fhe_ctx *ctx, const fhe_key *key, size_t index, bo
     Mirror ma(ct_a, n * batch, mem, true, st), mb(ct_b, n * batch, mem, true, st);
     if (ma.rc != FHE_OK || mb.rc != FHE_OK) return FHE_ERR_HIP;
     const bool small = small_shape(key->log_n, batch);
-#define GP_LAUNCH_W(AR, WR)                                                                                                  \
-    {                                                                                                                        \
-        const size_t lds = WR::LDS_BYTES;                                                                                    \
-        rc = set_lds(fhe::gadget_product_kernel<AR, WR>, lds);                                                               \
-        if (rc != FHE_OK) return rc;                                                                                         \
-        hipLaunchKernelGGL((fhe::gadget_product_kernel<AR, WR>), dim3((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS)),      \
-                           dim3(WR::THREADS), lds, st, ma.d, mb.d, (unsigned)batch, key_view(key, small), (unsigned)index,   \
-                           both ? 1u : 0u, tt, ring_consts(ctx, 0));                                                         \
-    }
+#define GP_LAUNCH_W(AR, WR)                                                                                                    \
+    rc = fhe::launch<fhe::gadget_product_kernel<AR, WR>>((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS, WR::LDS_BYTES, st, \
+                                                         ma.d, mb.d, (unsigned)batch, key_view(key, small), (unsigned)index, both ? 1u : 0u, \
+                                                         tt, ring_consts(ctx, 0));
 #define GP_LAUNCH(AR, LN) GP_LAUNCH_W(AR, fhe::WaveRing<LN>)
 #define GP_LAUNCH_BIG(AR, LN)                                                                \
     {                                                                                        \
@@ -322,7 +304,7 @@ static int gadget_entry(const fhe_ctx *ctx, const fhe_key *key, size_t index, bo
 #undef GP_LAUNCH_BIG
 #undef GP_LAUNCH_W
 #undef GP_LAUNCH
-    HIP_TRY(hipGetLastError());
+    if (rc != FHE_OK) return rc;
     rc = ma.sync_out(st);
     return rc != FHE_OK ? rc : mb.sync_out(st);
 }
@@ -358,8 +340,7 @@ int fhe_lwe_mod_switch(uint64_t q, uint64_t q_prime, const uint64_t *in, uint64_
     hipStream_t st = (hipStream_t)stream;
     Mirror mi(in, count, mem, true, st), mo(out, count, mem, false, st);
     if (mi.rc | mo.rc) return FHE_ERR_HIP;
-    hipLaunchKernelGGL(fhe::lwe_mod_switch_kernel, dim3(grid_for(count)), dim3(256), 0, st, (const u64 *)mi.d, mo.d, count, (u64)q, (u64)q_prime, odd);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::lwe_mod_switch_kernel>(fhew_grid(count), 256, 0, st, (const u64 *)mi.d, mo.d, count, (u64)q, (u64)q_prime, odd));
     return mo.sync_out(st);
 }
 
@@ -383,14 +364,13 @@ int fhe_lwe_key_switch(uint64_t q, int log_b, int d, const uint64_t *ksk_a, cons
     const int tile = fhe::ks_tile(batch, rows);
     if (tile && batch < (size_t(1) << 31)) {  // tiled kernel (lwe_kernels.hpp); sums wrap and are masked once when q is a power of two
         const bool pow2 = (q & (q - 1)) == 0;
-        const int bad = pow2 ? fhe::launch_key_switch_tiled(fhe::KsZqPow2{P}, ma.d, mb.d, n_in, n_out, batch, mka.d, mkb.d, moa.d, mob.d, tile, st)
-                             : fhe::launch_key_switch_tiled(fhe::KsZq{P}, ma.d, mb.d, n_in, n_out, batch, mka.d, mkb.d, moa.d, mob.d, tile, st);
-        if (bad) return FHE_ERR_HIP;
+        rc = pow2 ? fhe::launch_key_switch_tiled(fhe::KsZqPow2{P}, ma.d, mb.d, n_in, n_out, batch, mka.d, mkb.d, moa.d, mob.d, tile, st)
+                  : fhe::launch_key_switch_tiled(fhe::KsZq{P}, ma.d, mb.d, n_in, n_out, batch, mka.d, mkb.d, moa.d, mob.d, tile, st);
     } else {
-        hipLaunchKernelGGL(fhe::lwe_key_switch_kernel, dim3(grid_for((n_out + 1) * batch)), dim3(256), 0, st, (const u64 *)ma.d,
-                           (const u64 *)mb.d, (unsigned)n_in, (unsigned)n_out, batch, (const u64 *)mka.d, (const u64 *)mkb.d, P, moa.d, mob.d);
+        rc = fhe::launch<fhe::lwe_key_switch_kernel>(fhew_grid((n_out + 1) * batch), 256, 0, st, (const u64 *)ma.d, (const u64 *)mb.d,
+                                                     (unsigned)n_in, (unsigned)n_out, batch, (const u64 *)mka.d, (const u64 *)mkb.d, P, moa.d, mob.d);
     }
-    HIP_TRY(hipGetLastError());
+    if (rc != FHE_OK) return rc;
     rc = moa.sync_out(st);
     return rc != FHE_OK ? rc : mob.sync_out(st);
 }
@@ -413,8 +393,7 @@ int fhe_lwe_lincomb(uint64_t q, int k, const int64_t *coef, const uint64_t *cons
     lc.k = k;
     const u64 *ptrs[4] = {m0.d, m1.d, m2.d, m3.d};
     for (int t = 0; t < k; ++t) { lc.in[t] = ptrs[t]; lc.coef[t] = coef[t]; }
-    hipLaunchKernelGGL(fhe::lwe_lincomb_kernel, dim3(grid_for(count)), dim3(256), 0, st, lc, (u64)q, (u64)addend, mo.d, count);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::lwe_lincomb_kernel>(fhew_grid(count), 256, 0, st, lc, (u64)q, (u64)addend, mo.d, count));
     return mo.sync_out(st);
 }
 
@@ -430,9 +409,8 @@ int fhe_rlwe_sample_extract(uint64_t q, const uint64_t *ct_a, const uint64_t *ct
     Mirror ma(ct_a, n * batch, mem, true, st), mb(ct_b, n * batch, mem, true, st), moa(out_a, n * batch, mem, false, st),
         mob(out_b, batch, mem, false, st);
     if (ma.rc | mb.rc | moa.rc | mob.rc) return FHE_ERR_HIP;
-    hipLaunchKernelGGL(fhe::rlwe_sample_extract_kernel, dim3(grid_for(n * batch)), dim3(256), 0, st, (const u64 *)ma.d, (const u64 *)mb.d,
-                       (unsigned)n, batch, (unsigned)index, (u64)q, (u64)addend, moa.d, mob.d);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::rlwe_sample_extract_kernel>(fhew_grid(n * batch), 256, 0, st, (const u64 *)ma.d, (const u64 *)mb.d, (unsigned)n,
+                                                         batch, (unsigned)index, (u64)q, (u64)addend, moa.d, mob.d));
     int rc = moa.sync_out(st);
     return rc != FHE_OK ? rc : mob.sync_out(st);
 }
@@ -527,9 +505,9 @@ int fhe_blind_rotate(const fhe_bootstrap_key *bk, const uint64_t *lwe_a, const u
     int rc = FHE_OK;
     auto fail = [&](int code) { return code; };
     if (!async && hipMemsetAsync(d_err, 0, sizeof(int), st) != hipSuccess) return fail(FHE_ERR_HIP);
-    hipLaunchKernelGGL(fhe::blind_rotate_schedule_kernel, dim3((unsigned)batch), dim3(64), 3 * n_lwe * sizeof(unsigned), st, ma.d,
-                       (unsigned)n_lwe, (unsigned)batch, (unsigned)n, (unsigned)bk->w, bk->d_dlog, d_ops, d_nops, max_ops, d_err);
-    if (hipGetLastError() != hipSuccess) return fail(FHE_ERR_HIP);
+    rc = fhe::launch<fhe::blind_rotate_schedule_kernel>((unsigned)batch, 64, 3 * n_lwe * sizeof(unsigned), st, ma.d, (unsigned)n_lwe,
+                                                         (unsigned)batch, (unsigned)n, (unsigned)bk->w, bk->d_dlog, d_ops, d_nops, max_ops, d_err);
+    if (rc != FHE_OK) return fail(rc);
     fhe::BlindRotateParams BR;
     const bool small = small_shape(log_n, batch);
     BR.brk = key_view(bk->brk, small);
@@ -542,13 +520,8 @@ int fhe_blind_rotate(const fhe_bootstrap_key *bk, const uint64_t *lwe_a, const u
     BR.f = mf.d;
     BR.f_stride = f_stride;
 #define BR_LAUNCH_W(AR, WR)                                                                                                  \
-    {                                                                                                                        \
-        const size_t lds = WR::LDS_BYTES;                                                                                    \
-        rc = set_lds(fhe::blind_rotate_kernel<AR, WR>, lds);                                                                 \
-        if (rc == FHE_OK)                                                                                                    \
-            hipLaunchKernelGGL((fhe::blind_rotate_kernel<AR, WR>), dim3((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS)),    \
-                               dim3(WR::THREADS), lds, st, BR, moa.d, mob.d, (unsigned)batch, ring_consts(ctx, 0));          \
-    }
+    rc = fhe::launch<fhe::blind_rotate_kernel<AR, WR>>((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS, WR::LDS_BYTES, st, \
+                                                       BR, moa.d, mob.d, (unsigned)batch, ring_consts(ctx, 0));
 #define BR_CASE(AR, LN) case LN: { typedef fhe::WaveRing<LN> WD; BR_LAUNCH_W(AR, WD) break; }
 #define BR_CASE_BIG(AR, LN)                                                                  \
     case LN: {                                                                               \
@@ -577,7 +550,7 @@ int fhe_blind_rotate(const fhe_bootstrap_key *bk, const uint64_t *lwe_a, const u
 #undef BR_CASE_BIG
 #undef BR_LAUNCH_W
 #undef BR_CASE
-    if (rc != FHE_OK || hipGetLastError() != hipSuccess) return fail(FHE_ERR_HIP);
+    if (rc != FHE_OK) return fail(rc);
     if (async) return FHE_OK;  // (the workspace is stream ordered: released after the kernels above)
     int h_err = 0;
     if (hipMemcpyAsync(&h_err, d_err, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) return fail(FHE_ERR_HIP);

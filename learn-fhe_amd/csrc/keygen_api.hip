@@ -16,11 +16,6 @@
 using fhe::u64;
 
 namespace {
-inline unsigned grid_for(size_t total) {
-    size_t b = (total + 255) / 256;
-    return (unsigned)(b > 16384 ? 16384 : (b ? b : 1));
-}
-
 // distribution.rs:25-45 (keygen_kernels.hpp: fhe::make_dg_table) with the entry points' status codes
 int dg_table_rc(double std_dev, int n_sigma, fhe::DgTable *T) {
     if (!(std_dev > 0) || n_sigma < 1) return FHE_ERR_INVALID;
@@ -32,12 +27,10 @@ inline unsigned long long blocks_uniform(size_t count) { return (count + 3) / 4;
 inline unsigned long long blocks_words(size_t count) { return (count + 7) / 8; }
 
 int sample_uniform_dev(u64 q, const fhe::ChaChaKey &K, unsigned long long first, u64 *out, size_t count, hipStream_t st) {
-    hipLaunchKernelGGL(fhe::sample_uniform_kernel, dim3(grid_for(blocks_uniform(count))), dim3(256), 0, st, out, count, fhe::make_barrett(q), K, first);
-    return hipGetLastError() == hipSuccess ? FHE_OK : FHE_ERR_HIP;
+    return fhe::launch<fhe::sample_uniform_kernel>(grid_for(blocks_uniform(count)), 256, 0, st, out, count, fhe::make_barrett(q), K, first);
 }
 int sample_dg_dev(u64 q, const fhe::DgTable &T, const fhe::ChaChaKey &K, unsigned long long first, u64 *out, size_t count, hipStream_t st) {
-    hipLaunchKernelGGL(fhe::sample_dg_kernel, dim3(grid_for(blocks_words(count))), dim3(256), 0, st, out, count, q, T, K, first);
-    return hipGetLastError() == hipSuccess ? FHE_OK : FHE_ERR_HIP;
+    return fhe::launch<fhe::sample_dg_kernel>(grid_for(blocks_words(count)), 256, 0, st, out, count, q, T, K, first);
 }
 
 // rlwe.rs:146-156 for `rows` ciphertexts under one secret key, device buffers: a uniform, e <- dg(3.2, 6), b = a sk + e + pt
@@ -69,10 +62,7 @@ int rlwe_sk_encrypt_dev(const fhe_ctx *ctx, const u64 *sk_eval, const u64 *pt, s
     } else if (rc == FHE_OK) {
         return FHE_ERR_UNSUPPORTED;
     }
-    if (rc == FHE_OK) {
-        hipLaunchKernelGGL(fhe::add3_kernel, dim3(grid_for(count)), dim3(256), 0, st, ct_b, (const u64 *)e, pt, count, pt ? pt_rows * n : 1, (u64)ctx->q);
-        if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
-    }
+    if (rc == FHE_OK) rc = fhe::launch<fhe::add3_kernel>(grid_for(count), 256, 0, st, ct_b, (const u64 *)e, pt, count, pt ? pt_rows * n : 1, (u64)ctx->q);
     return rc;
 }
 
@@ -160,8 +150,7 @@ int fhe_sample_torus(const fhe_rng *rng, uint64_t stream_id, uint64_t *out, size
     hipStream_t st = (hipStream_t)stream;
     Mirror mo(out, count, mem, false, st);
     if (mo.rc != FHE_OK) return mo.rc;
-    hipLaunchKernelGGL(fhe::sample_u64_kernel, dim3(grid_for(blocks_words(count))), dim3(256), 0, st, mo.d, count, fhe::call_key(rng, stream_id, fhe::RNG_SAMPLE_TORUS), 0ull);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::sample_u64_kernel>(grid_for(blocks_words(count)), 256, 0, st, mo.d, count, fhe::call_key(rng, stream_id, fhe::RNG_SAMPLE_TORUS), 0ull));
     return mo.sync_out(st);
 }
 
@@ -193,9 +182,7 @@ int fhe_power_up(uint64_t q, int log_b, int d, const uint64_t *in, size_t n, siz
     hipStream_t st = (hipStream_t)stream;
     Mirror mi(in, n * polys, mem, true, st), mo(out, n * polys * d, mem, false, st);
     if (mi.rc | mo.rc) return FHE_ERR_HIP;
-    hipLaunchKernelGGL(fhe::power_up_kernel, dim3(grid_for(n * polys * d)), dim3(256), 0, st, (const u64 *)mi.d, mo.d, n, polys, d, rb, log_b,
-                       fhe::make_barrett(q), 0);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::power_up_kernel>(grid_for(n * polys * d), 256, 0, st, (const u64 *)mi.d, mo.d, n, polys, d, rb, log_b, fhe::make_barrett(q), 0));
     return mo.sync_out(st);
 }
 
@@ -260,10 +247,8 @@ int fhe_rlwe_share_encrypt(const fhe_ctx *ctx, const uint64_t *a, size_t a_rows,
         mul.mul = sk_eval; mul.mul_div = (unsigned)rows; mul.mul_period = 1;
         rc = fhe::ntt_inv_multi(ctx->d_desc, 1, mb.d, log_n, rows, st, ctx->pm_b, mul);
     }
-    if (rc == FHE_OK) {
-        hipLaunchKernelGGL(fhe::add3_kernel, dim3(grid_for(count)), dim3(256), 0, st, mb.d, (const u64 *)e, pt ? (const u64 *)mpt.d : nullptr, count, count, (u64)ctx->q);
-        if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
-    }
+    if (rc == FHE_OK)
+        rc = fhe::launch<fhe::add3_kernel>(grid_for(count), 256, 0, st, mb.d, (const u64 *)e, pt ? (const u64 *)mpt.d : nullptr, count, count, (u64)ctx->q);
     return rc == FHE_OK ? mb.sync_out(st) : rc;
 }
 
@@ -294,9 +279,8 @@ int fhe_rlwe_pk_encrypt(const fhe_ctx *ctx, const uint64_t *pk_a, const uint64_t
     src.src = mpb.d;
     if (rc == FHE_OK) rc = fhe::ntt_fwd_multi(ctx->d_desc, 1, pk_eval + n, log_n, 1, st, ctx->pm_b, src);
     if (rc != FHE_OK) return rc;
-    hipLaunchKernelGGL(fhe::sample_zo_kernel, dim3(grid_for(blocks_words(count))), dim3(256), 0, st, ma.d, count, 0.5, K, 0ull);
-    hipLaunchKernelGGL(fhe::small_i64_to_zq_kernel, dim3(grid_for(count)), dim3(256), 0, st, ma.d, count, (u64)ctx->q);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::sample_zo_kernel>(grid_for(blocks_words(count)), 256, 0, st, ma.d, count, 0.5, K, 0ull));
+    FHE_TRY(fhe::launch<fhe::small_i64_to_zq_kernel>(grid_for(count), 256, 0, st, ma.d, count, (u64)ctx->q));
     fhe::DgTable T;
     rc = dg_table_rc(3.2, 6, &T);
     if (rc == FHE_OK) rc = sample_dg_dev(ctx->q, T, K, blocks_words(count), e, 2 * count, st);
@@ -307,9 +291,8 @@ int fhe_rlwe_pk_encrypt(const fhe_ctx *ctx, const uint64_t *pk_a, const uint64_t
         mul.mul = pk_eval + half * n; mul.mul_div = (unsigned)batch; mul.mul_period = 1;
         rc = fhe::ntt_inv_multi(ctx->d_desc, 1, half ? mb.d : ma.d, log_n, batch, st, ctx->pm_b, mul);
         if (rc != FHE_OK) break;
-        hipLaunchKernelGGL(fhe::add3_kernel, dim3(grid_for(count)), dim3(256), 0, st, half ? mb.d : ma.d, (const u64 *)(e + half * count),
-                           (half && pt) ? (const u64 *)mpt.d : nullptr, count, count, (u64)ctx->q);
-        if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
+        rc = fhe::launch<fhe::add3_kernel>(grid_for(count), 256, 0, st, half ? mb.d : ma.d, (const u64 *)(e + half * count),
+                                           (half && pt) ? (const u64 *)mpt.d : nullptr, count, count, (u64)ctx->q);
     }
     if (rc == FHE_OK) rc = ma.sync_out(st);
     if (rc == FHE_OK) rc = mb.sync_out(st);
@@ -347,8 +330,7 @@ int fhe_rlwe_decrypt(const fhe_ctx *ctx, const uint64_t *sk, const uint64_t *ct_
         rc = fhe::ntt_inv_multi(ctx->d_desc, 1, as, log_n, batch, st, ctx->pm_b, mul);
     }
     if (rc != FHE_OK) return rc;
-    hipLaunchKernelGGL(fhe::rsub_kernel, dim3(grid_for(count)), dim3(256), 0, st, as, (const u64 *)mb.d, count, (u64)ctx->q);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::rsub_kernel>(grid_for(count), 256, 0, st, as, (const u64 *)mb.d, count, (u64)ctx->q));
     HIP_TRY(hipMemcpyAsync(mo.d, as, count * sizeof(u64), hipMemcpyDeviceToDevice, st));
     return mo.sync_out(st);
 }
@@ -377,14 +359,13 @@ int fhe_rgsw_encrypt(const fhe_ctx *ctx, int log_b, int d, const uint64_t *sk, c
     // 2d encryptions of zero per plaintext (rgsw.rs:91-99) ...
     if (rc == FHE_OK) rc = rlwe_sk_encrypt_dev(ctx, sk_eval, nullptr, 0, ma.d, mb.d, n, rows, fhe::call_key(rng, stream_id, fhe::RNG_RGSW_ENC), &cursor, st);
     if (rc == FHE_OK) {
-        hipLaunchKernelGGL(fhe::power_up_kernel, dim3(grid_for(n * count * d)), dim3(256), 0, st, (const u64 *)mpt.d, pw, n, count, d, rb, log_b,
-                           fhe::make_barrett(ctx->q), 0);
+        rc = fhe::launch<fhe::power_up_kernel>(grid_for(n * count * d), 256, 0, st, (const u64 *)mpt.d, pw, n, count, d, rb, log_b, fhe::make_barrett(ctx->q), 0);
         // ... rows 0..d: a += pt base_j; rows d..2d: b += pt base_j (rgsw.rs:100-103)
         for (size_t c = 0; c < count && rc == FHE_OK; ++c) {
-            hipLaunchKernelGGL(fhe::add_assign_kernel, dim3(grid_for(d * n)), dim3(256), 0, st, ma.d + c * 2 * d * n, (const u64 *)(pw + c * d * n), (size_t)d * n, (u64)ctx->q);
-            hipLaunchKernelGGL(fhe::add_assign_kernel, dim3(grid_for(d * n)), dim3(256), 0, st, mb.d + (c * 2 * d + d) * n, (const u64 *)(pw + c * d * n), (size_t)d * n, (u64)ctx->q);
+            rc = fhe::launch<fhe::add_assign_kernel>(grid_for(d * n), 256, 0, st, ma.d + c * 2 * d * n, (const u64 *)(pw + c * d * n), (size_t)d * n, (u64)ctx->q);
+            if (rc == FHE_OK)
+                rc = fhe::launch<fhe::add_assign_kernel>(grid_for(d * n), 256, 0, st, mb.d + (c * 2 * d + d) * n, (const u64 *)(pw + c * d * n), (size_t)d * n, (u64)ctx->q);
         }
-        if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
     }
     if (rc == FHE_OK) rc = ma.sync_out(st);
     if (rc == FHE_OK) rc = mb.sync_out(st);
@@ -415,13 +396,12 @@ int fhe_rgsw_pk_encrypt(const fhe_ctx *ctx, int log_b, int d, const uint64_t *pk
     rc = fhe_rlwe_pk_encrypt(ctx, (const uint64_t *)mpa.d, (const uint64_t *)mpb.d, nullptr, n, rows, rng, stream_id, (uint64_t *)ma.d, (uint64_t *)mb.d, FHE_MEM_DEVICE,
                              stream);
     if (rc == FHE_OK) {
-        hipLaunchKernelGGL(fhe::power_up_kernel, dim3(grid_for(n * count * d)), dim3(256), 0, st, (const u64 *)mpt.d, pw, n, count, d, rb, log_b,
-                           fhe::make_barrett(ctx->q), 0);
-        for (size_t c = 0; c < count; ++c) {
-            hipLaunchKernelGGL(fhe::add_assign_kernel, dim3(grid_for(d * n)), dim3(256), 0, st, ma.d + c * 2 * d * n, (const u64 *)(pw + c * d * n), (size_t)d * n, (u64)ctx->q);
-            hipLaunchKernelGGL(fhe::add_assign_kernel, dim3(grid_for(d * n)), dim3(256), 0, st, mb.d + (c * 2 * d + d) * n, (const u64 *)(pw + c * d * n), (size_t)d * n, (u64)ctx->q);
+        rc = fhe::launch<fhe::power_up_kernel>(grid_for(n * count * d), 256, 0, st, (const u64 *)mpt.d, pw, n, count, d, rb, log_b, fhe::make_barrett(ctx->q), 0);
+        for (size_t c = 0; c < count && rc == FHE_OK; ++c) {
+            rc = fhe::launch<fhe::add_assign_kernel>(grid_for(d * n), 256, 0, st, ma.d + c * 2 * d * n, (const u64 *)(pw + c * d * n), (size_t)d * n, (u64)ctx->q);
+            if (rc == FHE_OK)
+                rc = fhe::launch<fhe::add_assign_kernel>(grid_for(d * n), 256, 0, st, mb.d + (c * 2 * d + d) * n, (const u64 *)(pw + c * d * n), (size_t)d * n, (u64)ctx->q);
         }
-        if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
     }
     if (rc == FHE_OK) rc = ma.sync_out(st);
     if (rc == FHE_OK) rc = mb.sync_out(st);
@@ -447,11 +427,9 @@ int fhe_rlwe_ksk_gen(const fhe_ctx *ctx, int log_b, int d, const uint64_t *sk0, 
     src.src = m0.d; src.src_mod = 1;
     rc = fhe::ntt_fwd_multi(ctx->d_desc, 1, sk_eval, ilog2(n), 1, st, ctx->pm_b, src);
     if (rc == FHE_OK && t != 0) rc = fhe_automorphism(ctx->q, t, (const uint64_t *)m0.d, (uint64_t *)s1, n, 1, FHE_MEM_DEVICE, stream);  // rlwe.rs:129
-    if (rc == FHE_OK) {
-        hipLaunchKernelGGL(fhe::power_up_kernel, dim3(grid_for(n * d)), dim3(256), 0, st, (const u64 *)(t != 0 ? s1 : m1.d), pw, n, (size_t)1, d, rb, log_b,
-                           fhe::make_barrett(ctx->q), 1);  // power_up(-sk1)
-        if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
-    }
+    if (rc == FHE_OK)  // power_up(-sk1)
+        rc = fhe::launch<fhe::power_up_kernel>(grid_for(n * d), 256, 0, st, (const u64 *)(t != 0 ? s1 : m1.d), pw, n, (size_t)1, d, rb, log_b,
+                                               fhe::make_barrett(ctx->q), 1);
     unsigned long long cursor = 0;
     if (rc == FHE_OK) rc = rlwe_sk_encrypt_dev(ctx, sk_eval, pw, d, ma.d, mb.d, n, d, fhe::call_key(rng, stream_id, fhe::RNG_RLWE_KSK), &cursor, st);
     if (rc == FHE_OK) rc = ma.sync_out(st);
@@ -471,11 +449,9 @@ static int lwe_encrypt_common(uint64_t q, const u64 *sk, const u64 *pt, const u6
     if (we.rc != FHE_OK) return we.rc;
     if (!a_given) rc = sample_uniform_dev(q, K, 0, out_a, rows * n, st);
     if (rc == FHE_OK) rc = sample_dg_dev(q, T, K, blocks_uniform(rows * n), we.as<u64>(), rows, st);
-    if (rc == FHE_OK) {
-        hipLaunchKernelGGL(fhe::lwe_encrypt_kernel, dim3(grid_for(rows)), dim3(256), 0, st, a_given ? a_given : (const u64 *)out_a, sk, (const u64 *)we.as<u64>(), pt,
-                           out_b, n, rows, fhe::make_barrett(q), sk1, n1 ? n1 : 1, rb, log_b);
-        if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
-    }
+    if (rc == FHE_OK)
+        rc = fhe::launch<fhe::lwe_encrypt_kernel>(grid_for(rows), 256, 0, st, a_given ? a_given : (const u64 *)out_a, sk, (const u64 *)we.as<u64>(), pt, out_b,
+                                                  n, rows, fhe::make_barrett(q), sk1, n1 ? n1 : 1, rb, log_b);
     return rc;
 }
 
@@ -559,8 +535,7 @@ int fhe_rq_sum(uint64_t q, const uint64_t *in, size_t len, size_t count, uint64_
     hipStream_t st = (hipStream_t)stream;
     Mirror mi(in, len * count, mem, true, st), mo(out, len, mem, false, st);
     if (mi.rc | mo.rc) return FHE_ERR_HIP;
-    hipLaunchKernelGGL(fhe::rq_sum_kernel, dim3(grid_for(len)), dim3(256), 0, st, (const u64 *)mi.d, mo.d, len, count, (u64)q);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::rq_sum_kernel>(grid_for(len), 256, 0, st, (const u64 *)mi.d, mo.d, len, count, (u64)q));
     return mo.sync_out(st);
 }
 

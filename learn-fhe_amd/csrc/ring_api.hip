@@ -27,36 +27,15 @@ int check_transform(const fhe_ctx *ctx, const void *a, size_t n, size_t batch) {
     return FHE_OK;
 }
 
-// hipFuncSetAttribute once per (kernel, device), not per launch
-// `done`: one bit per device, owned by the launch-template instantiation of this kernel -- the attribute is set once per (kernel,
-// device) and every later launch costs one relaxed load (no lock, no lookup)
-hipError_t set_max_lds(const void *kernel, int bytes, std::atomic<uint64_t> &done) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const uint64_t bit = uint64_t(1) << (dev & 63);
-    if (done.load(std::memory_order_acquire) & bit) return hipSuccess;
-    static std::mutex mu;
-    std::lock_guard<std::mutex> lock(mu);
-    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) done.fetch_or(bit, std::memory_order_release);
-    return e;
-}
-
 template <class A, int LOG_N, int LOG_E, int PPW, bool PFX = false>
 int launch_gen(bool inverse, const fhe::ModDesc *descs, unsigned n_desc, u64 *a, size_t subs, int pb, hipStream_t st, fhe::NttIo io) {
     using C = fhe::NttCfg<LOG_N, LOG_E, PPW>;
     // measured on MI355X (tools/ntt_lab.hip): staging through LDS wins for the forward stores, direct 16-byte loads win
     // for the inverse
-    auto k = inverse ? fhe::ntt_inv_kernel<A, LOG_N, LOG_E, PPW, PFX, true> : fhe::ntt_fwd_kernel<A, LOG_N, LOG_E, PPW, PFX, false>;
-    if (C::LDS_BYTES > 64 * 1024) {
-        static std::atomic<uint64_t> done[2];
-        HIP_TRY(set_max_lds((const void *)k, (int)C::LDS_BYTES, done[inverse ? 1 : 0]));
-    }
-    unsigned grid = (unsigned)((subs + PPW - 1) / PPW);
-    hipLaunchKernelGGL(k, dim3(grid), dim3(C::THREADS), C::LDS_BYTES, st, a, descs, n_desc, (unsigned)subs, pb, io);
-    HIP_TRY(hipGetLastError());
-    return FHE_OK;
+    const unsigned grid = (unsigned)((subs + PPW - 1) / PPW);
+    if (inverse)
+        return fhe::launch<fhe::ntt_inv_kernel<A, LOG_N, LOG_E, PPW, PFX, true>>(grid, C::THREADS, C::LDS_BYTES, st, a, descs, n_desc, (unsigned)subs, pb, io);
+    return fhe::launch<fhe::ntt_fwd_kernel<A, LOG_N, LOG_E, PPW, PFX, false>>(grid, C::THREADS, C::LDS_BYTES, st, a, descs, n_desc, (unsigned)subs, pb, io);
 }
 
 // (LOG_N -> LOG_E, PPW): 16 coefficients per thread from N = 128 up; small rings pack many polynomials
@@ -97,32 +76,25 @@ inline bool wave_local_small_disabled() { return fhe::opt(fhe::OPT_NO_W12) != 0;
 inline size_t several_generations() { return size_t(8) * (size_t)fhe::current_cu_count(); }
 template <class AF, class AI, int R0 = 3>
 int launch14(bool inv, const fhe::ModDesc *d, unsigned nd, u64 *a, size_t subs, int pb, hipStream_t st, fhe::NttIo io) {
-    auto k = pb ? (inv ? (io.mul ? fhe::ntt14w_inv_kernel<AI, true, true, R0> : fhe::ntt14w_inv_kernel<AI, true, false, R0>) : fhe::ntt14w_fwd_kernel<AF, true, R0>)
-                : (inv ? (io.mul ? fhe::ntt14w_inv_kernel<AI, false, true, R0> : fhe::ntt14w_inv_kernel<AI, false, false, R0>) : fhe::ntt14w_fwd_kernel<AF, false, R0>);
-    static std::atomic<uint64_t> done[8];
-    HIP_TRY(set_max_lds((const void *)k, (int)fhe::w14::lds_bytes<R0>(), done[(pb ? 4 : 0) | (inv ? 2 : 0) | (io.mul ? 1 : 0)]));
     // several moduli: modulus-major dispatch order (ntt14w.hpp, sub_of_block)
     const size_t polys = subs >> pb;
     // (only launches of several generations of workgroups: when the whole launch is resident at once the order is irrelevant, and
     // measured 3 % slower at cfg4 batch 8)
     const bool by_mod = nd > 1 && nd <= 65535 && polys % nd == 0 && subs >= several_generations() && !limb_major_disabled();
     const dim3 grid = by_mod ? dim3((unsigned)(subs / nd), nd) : dim3((unsigned)subs);
-    hipLaunchKernelGGL(k, grid, dim3(fhe::w14::threads<R0>()), fhe::w14::lds_bytes<R0>(), st, a, d, nd, (unsigned)subs, pb, io);
-    HIP_TRY(hipGetLastError());
-    return FHE_OK;
+#define W14(K) fhe::launch<K>(grid, fhe::w14::threads<R0>(), fhe::w14::lds_bytes<R0>(), st, a, d, nd, (unsigned)subs, pb, io)
+    if (!inv) return pb ? W14((fhe::ntt14w_fwd_kernel<AF, true, R0>)) : W14((fhe::ntt14w_fwd_kernel<AF, false, R0>));
+    if (pb) return io.mul ? W14((fhe::ntt14w_inv_kernel<AI, true, true, R0>)) : W14((fhe::ntt14w_inv_kernel<AI, true, false, R0>));
+    return io.mul ? W14((fhe::ntt14w_inv_kernel<AI, false, true, R0>)) : W14((fhe::ntt14w_inv_kernel<AI, false, false, R0>));
+#undef W14
 }
 
 // the fused ring product (ntt14w_mul_kernel): a <- inverse(forward(a) (.) io.mul), 2^13 .. 2^15
 template <class A, int R0>
 int launch_mul14(const fhe::ModDesc *d, unsigned nd, u64 *a, size_t subs, hipStream_t st, fhe::NttIo io) {
-    auto k = fhe::ntt14w_mul_kernel<A, R0>;
-    static std::atomic<uint64_t> done;
-    HIP_TRY(set_max_lds((const void *)k, (int)fhe::w14::lds_bytes<R0>(), done));
     const bool by_mod = nd > 1 && nd <= 65535 && subs % nd == 0 && subs >= several_generations() && !limb_major_disabled();
     const dim3 grid = by_mod ? dim3((unsigned)(subs / nd), nd) : dim3((unsigned)subs);
-    hipLaunchKernelGGL(k, grid, dim3(fhe::w14::threads<R0>()), fhe::w14::lds_bytes<R0>(), st, a, d, nd, (unsigned)subs, 0, io);
-    HIP_TRY(hipGetLastError());
-    return FHE_OK;
+    return fhe::launch<fhe::ntt14w_mul_kernel<A, R0>>(grid, fhe::w14::threads<R0>(), fhe::w14::lds_bytes<R0>(), st, a, d, nd, (unsigned)subs, 0, io);
 }
 template <class A>
 int dispatch_mul14(int log_n, const fhe::ModDesc *d, unsigned nd, u64 *a, size_t subs, hipStream_t st, fhe::NttIo io) {
@@ -173,11 +145,6 @@ int sub_inv(const fhe::ModDesc *d, unsigned nd, u64 *a, int log_n, size_t subs, 
     return sub_transform(true, d, nd, a, log_n, subs, pb, pm, st, io);
 }
 
-inline unsigned pass_grid(size_t total) {
-    size_t b = (total + 255) / 256;
-    return (unsigned)(b > 16384 ? 16384 : (b ? b : 1));
-}
-
 }  // namespace
 
 namespace fhe {
@@ -190,13 +157,14 @@ int ntt_fwd_multi(const ModDesc *descs, unsigned n_desc, u64 *a, int log_n, size
     if (io.src_group) return FHE_ERR_UNSUPPORTED;  // several sources: single-pass rings only (callers fall back to one launch each)
     const int pb = log_n - 14;
     const size_t cols = batch << 14;
+    int rc = FHE_OK;
     switch (pb) {  // the opening pass reads the source, everything after it runs in place
-        case 1: hipLaunchKernelGGL(ntt_big_fwd_pass<1>, dim3(pass_grid(cols)), dim3(256), 0, st, a, descs, n_desc, (unsigned)batch, log_n, io.src, io.src_mod); break;
-        case 2: hipLaunchKernelGGL(ntt_big_fwd_pass<2>, dim3(pass_grid(cols)), dim3(256), 0, st, a, descs, n_desc, (unsigned)batch, log_n, io.src, io.src_mod); break;
-        case 3: hipLaunchKernelGGL(ntt_big_fwd_pass<3>, dim3(pass_grid(cols)), dim3(256), 0, st, a, descs, n_desc, (unsigned)batch, log_n, io.src, io.src_mod); break;
+        case 1: rc = launch<ntt_big_fwd_pass<1>>(grid_for(cols), 256, 0, st, a, descs, n_desc, (unsigned)batch, log_n, io.src, io.src_mod); break;
+        case 2: rc = launch<ntt_big_fwd_pass<2>>(grid_for(cols), 256, 0, st, a, descs, n_desc, (unsigned)batch, log_n, io.src, io.src_mod); break;
+        case 3: rc = launch<ntt_big_fwd_pass<3>>(grid_for(cols), 256, 0, st, a, descs, n_desc, (unsigned)batch, log_n, io.src, io.src_mod); break;
         default: return FHE_ERR_UNSUPPORTED;
     }
-    HIP_TRY(hipGetLastError());
+    if (rc != FHE_OK) return rc;
     return sub_fwd(descs, n_desc, a, 14, batch << pb, pb, pm, st, NttIo());
 }
 
@@ -210,13 +178,12 @@ int ntt_inv_multi(const ModDesc *descs, unsigned n_desc, u64 *a, int log_n, size
     if (rc != FHE_OK) return rc;
     const size_t cols = batch << 14;
     switch (pb) {
-        case 1: hipLaunchKernelGGL(ntt_big_inv_pass<1>, dim3(pass_grid(cols)), dim3(256), 0, st, a, descs, n_desc, (unsigned)batch, log_n); break;
-        case 2: hipLaunchKernelGGL(ntt_big_inv_pass<2>, dim3(pass_grid(cols)), dim3(256), 0, st, a, descs, n_desc, (unsigned)batch, log_n); break;
-        case 3: hipLaunchKernelGGL(ntt_big_inv_pass<3>, dim3(pass_grid(cols)), dim3(256), 0, st, a, descs, n_desc, (unsigned)batch, log_n); break;
+        case 1: rc = launch<ntt_big_inv_pass<1>>(grid_for(cols), 256, 0, st, a, descs, n_desc, (unsigned)batch, log_n); break;
+        case 2: rc = launch<ntt_big_inv_pass<2>>(grid_for(cols), 256, 0, st, a, descs, n_desc, (unsigned)batch, log_n); break;
+        case 3: rc = launch<ntt_big_inv_pass<3>>(grid_for(cols), 256, 0, st, a, descs, n_desc, (unsigned)batch, log_n); break;
         default: return FHE_ERR_UNSUPPORTED;
     }
-    HIP_TRY(hipGetLastError());
-    return FHE_OK;
+    return rc;
 }
 
 // N = 2^15 with the outermost layer left to the caller (rns_kernels.hpp, the edge kernels of the key switch): what remains of
@@ -478,11 +445,7 @@ int fhe_ntt_inv(const fhe_ctx *ctx, uint64_t *a, size_t n, size_t batch, fhe_mem
 }
 
 static int launch_pointwise(const fhe_ctx *ctx, u64 *a, const u64 *b, size_t len, hipStream_t st) {
-    size_t blocks = (len + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(fhe::pointwise_mul_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, b, len, ctx->barrett);
-    HIP_TRY(hipGetLastError());
-    return FHE_OK;
+    return fhe::launch<fhe::pointwise_mul_kernel>(grid_for(len, 4096), 256, 0, st, a, b, len, ctx->barrett);
 }
 
 int fhe_pointwise_mul(const fhe_ctx *ctx, uint64_t *a, const uint64_t *b, size_t len, fhe_mem mem, void *stream) {
@@ -508,9 +471,8 @@ int rq_elementwise(uint64_t q, const void *a, const void *b, uint64_t *out, size
     hipStream_t st = (hipStream_t)stream;
     Mirror ma(a, len, mem, true, st), mb(op < 2 ? b : nullptr, op < 2 ? len : 0, mem, true, st), mo(out, len, mem, false, st);
     if (ma.rc | mb.rc | mo.rc) return FHE_ERR_HIP;
-    hipLaunchKernelGGL(fhe::rq_elementwise_kernel, dim3(pass_grid(len)), dim3(256), 0, st, (const u64 *)ma.d, (const u64 *)mb.d, mo.d, len, op,
-                       (u64)scalar, fhe::make_barrett(q));
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::rq_elementwise_kernel>(grid_for(len), 256, 0, st, (const u64 *)ma.d, (const u64 *)mb.d, mo.d, len, op, (u64)scalar,
+                                                     fhe::make_barrett(q)));
     return mo.sync_out(st);
 }
 }  // namespace

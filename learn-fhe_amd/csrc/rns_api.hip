@@ -167,11 +167,6 @@ RowOffsets build_rows(BlobBuilder &bb, const std::vector<uint64_t> &Bm, int la, 
 }
 fhe::PmRows rows_view(const RowOffsets &o, const uint64_t *base) { return fhe::PmRows{o.stride, (const unsigned *)(base + o.tab)}; }
 
-inline unsigned grid_for(size_t total) {
-    size_t b = (total + 255) / 256;
-    return (unsigned)(b > 16384 ? 16384 : (b ? b : 1));
-}
-
 }  // namespace
 
 extern "C" {
@@ -383,24 +378,26 @@ fhe::PmRows rows_from(const fhe::PmRows &R, int lo) { return fhe::PmRows{R.strid
 
 // the new limbs of extend_bases: qs -> ps (in [batch][L][n] -> out [batch][K][n]) or, `to_qs`, ps -> qs; `copy` (optional) receives the
 // source limbs [c_lo, c_hi); only the target rows [r_lo, r_hi) are produced (default: all)
-void launch_extend(const fhe_rns_ctx *r, const u64 *in, size_t in_bs, u64 *out, size_t out_bs, size_t n, size_t batch, hipStream_t st,
+int launch_extend(const fhe_rns_ctx *r, const u64 *in, size_t in_bs, u64 *out, size_t out_bs, size_t n, size_t batch, hipStream_t st,
                    u64 *copy = nullptr, size_t copy_bs = 0, bool to_qs = false, int c_lo = 0, int c_hi = -1, int r_lo = 0, int r_hi = -1) {
     const dim3 grid(grid_for(n * batch));
     const int la = to_qs ? r->K : r->L, lb = to_qs ? r->L : r->K;
+    int rc = FHE_OK;
     if (c_hi < 0) c_hi = la;
     if (r_hi < 0) r_hi = lb;
     if (r->pm) {
         const fhe::PmSrc &S = to_qs ? r->s_p2q_plain : r->s_q2p;
         const fhe::PmRows R = rows_from(to_qs ? r->r_p2q_plain : r->r_q2p, r_lo);
-#define CALL(M, F) hipLaunchKernelGGL((fhe::rns_extend_pm_kernel<M, F>), grid, dim3(256), 0, st, in, in_bs, out, out_bs, n, batch, S, R, r_hi - r_lo, r->uni, copy, copy_bs, c_lo, c_hi)
+#define CALL(M, F) rc = fhe::launch<fhe::rns_extend_pm_kernel<M, F>>(grid, 256, 0, st, in, in_bs, out, out_bs, n, batch, S, R, r_hi - r_lo, r->uni, copy, copy_bs, c_lo, c_hi)
         RNS_BOUND(la, CALL);
 #undef CALL
     } else {  // (the Shoup route has no limb subsets: callers check r->pm first)
         const fhe::BaseConv &C = to_qs ? r->p2q : r->q2p;
-#define CALL(M, F) hipLaunchKernelGGL((fhe::rns_extend_kernel<M, F>), grid, dim3(256), 0, st, in, in_bs, out, out_bs, n, batch, C, copy, copy_bs)
+#define CALL(M, F) rc = fhe::launch<fhe::rns_extend_kernel<M, F>>(grid, 256, 0, st, in, in_bs, out, out_bs, n, batch, C, copy, copy_bs)
         RNS_BOUND(la, CALL);
 #undef CALL
     }
+    return rc;
 }
 // where a whole [batch][L+K][n] block keeps the limbs of a rescale (rns_kernels.hpp RescaleIn)
 fhe::RescaleIn rescale_in_block(const u64 *in, size_t in_bs, int L, int K, size_t n) {
@@ -411,43 +408,49 @@ fhe::RescaleIn rescale_in_block(const u64 *in, size_t in_bs, int L, int K, size_
 }
 // rescale_k(K) (last = false: L q-limbs + K p-limbs -> out [batch][L][n]) or rescale() (last = true: in [batch][L][n] -> [batch][L-1][n]);
 // rows [q_lo, q_hi) of the q-limbs only (pseudo-Mersenne route; default: all), I.in_q then holds those limbs
-void launch_rescale(const fhe_rns_ctx *r, bool last, const fhe::RescaleIn &I, u64 *out, size_t out_bs, const u64 *addend, size_t add_bs, size_t n,
+int launch_rescale(const fhe_rns_ctx *r, bool last, const fhe::RescaleIn &I, u64 *out, size_t out_bs, const u64 *addend, size_t add_bs, size_t n,
                     size_t batch, hipStream_t st, int q_lo = 0, int q_hi = -1) {
     const dim3 grid(grid_for(n * batch));
     const int k = last ? 1 : r->K, L = last ? r->L - 1 : r->L;
     if (q_hi < 0) q_hi = L;
+    int rc = FHE_OK;
     if (r->pm) {
         const fhe::PmSrc &S = last ? r->s_last : r->s_p2q;
         const fhe::PmRows R = rows_from(last ? r->r_last : r->r_resc, q_lo);
-#define CALL(M, F) hipLaunchKernelGGL((fhe::rns_rescale_pm_kernel<M, F>), grid, dim3(256), 0, st, I, out, out_bs, addend, add_bs, n, batch, q_hi - q_lo, S, R, r->uni)
+#define CALL(M, F) rc = fhe::launch<fhe::rns_rescale_pm_kernel<M, F>>(grid, 256, 0, st, I, out, out_bs, addend, add_bs, n, batch, q_hi - q_lo, S, R, r->uni)
         RNS_BOUND(k, CALL);
 #undef CALL
     } else {
         const fhe::RescaleConsts &R = last ? r->resc_last : r->resc;
-#define CALL(M, F) hipLaunchKernelGGL((fhe::rns_rescale_kernel<M, F>), grid, dim3(256), 0, st, I.in_q, I.q_bs, out, out_bs, addend, add_bs, n, batch, R)
+#define CALL(M, F) rc = fhe::launch<fhe::rns_rescale_kernel<M, F>>(grid, 256, 0, st, I.in_q, I.q_bs, out, out_bs, addend, add_bs, n, batch, R)
         RNS_BOUND(k, CALL);
 #undef CALL
     }
+    return rc;
 }
 // the same two steps with the outermost transform layer of a 2^15 ring in them (rns_kernels.hpp); pseudo-Mersenne bases only
-void launch_extend_edge(const fhe_rns_ctx *r, const u64 *in, size_t in_bs, u64 *out, size_t out_bs, size_t n, size_t batch, hipStream_t st,
+int launch_extend_edge(const fhe_rns_ctx *r, const u64 *in, size_t in_bs, u64 *out, size_t out_bs, size_t n, size_t batch, hipStream_t st,
                         int c_lo = 0, int c_hi = -1, int r_lo = 0, int r_hi = -1) {
     if (c_hi < 0) c_hi = r->L;
     if (r_hi < 0) r_hi = r->K;
     const fhe::PmRows R = rows_from(r->r_q2p, r_lo), RW = rows_from(r->r_q2p_w, r_lo);
-#define CALL(M, F) hipLaunchKernelGGL((fhe::rns_extend_edge_pm_kernel<M, F>), dim3(grid_for(n / 2 * batch)), dim3(256), 0, st, in, in_bs, out, out_bs, n, batch, \
-                                      r->s_q2p, R, RW, r_hi - r_lo, r->uni, c_lo, c_hi)
+    int rc = FHE_OK;
+#define CALL(M, F) rc = fhe::launch<fhe::rns_extend_edge_pm_kernel<M, F>>(grid_for(n / 2 * batch), 256, 0, st, in, in_bs, out, out_bs, n, batch, r->s_q2p, R, \
+                                                                         RW, r_hi - r_lo, r->uni, c_lo, c_hi)
     RNS_BOUND(r->L, CALL);
 #undef CALL
+    return rc;
 }
-void launch_rescale_edge(const fhe_rns_ctx *r, const fhe::RescaleIn &I, u64 *out, size_t out_bs, const u64 *addend, size_t add_bs, size_t n,
+int launch_rescale_edge(const fhe_rns_ctx *r, const fhe::RescaleIn &I, u64 *out, size_t out_bs, const u64 *addend, size_t add_bs, size_t n,
                          size_t batch, hipStream_t st, int q_lo = 0, int q_hi = -1) {
     if (q_hi < 0) q_hi = r->L;
     const fhe::PmRows R = rows_from(r->r_resc_edge, q_lo);
-#define CALL(M, F) hipLaunchKernelGGL((fhe::rns_rescale_edge_pm_kernel<M, F>), dim3(grid_for(n / 2 * batch)), dim3(256), 0, st, I, out, out_bs, addend, \
-                                      add_bs, n, batch, q_hi - q_lo, r->s_p2q_sum, r->s_p2q_diff, R, r->uni)
+    int rc = FHE_OK;
+#define CALL(M, F) rc = fhe::launch<fhe::rns_rescale_edge_pm_kernel<M, F>>(grid_for(n / 2 * batch), 256, 0, st, I, out, out_bs, addend, add_bs, n, batch, \
+                                                                          q_hi - q_lo, r->s_p2q_sum, r->s_p2q_diff, R, r->uni)
     RNS_BOUND(r->K, CALL);
 #undef CALL
+    return rc;
 }
 // lab switch NO_EDGE: the key switch keeps whole 2^15 transforms (A/B runs and the test that both routes agree bit for bit)
 bool edge_enabled() { return fhe::opt(fhe::OPT_NO_EDGE) == 0; }
@@ -462,8 +465,7 @@ int fhe_rns_extend_bases(const fhe_rns_ctx *r, const uint64_t *in, uint64_t *out
     if (!guard.ok) return FHE_ERR_HIP;
     Mirror mi(in, n * batch * r->L, mem, true, st), mo(out, n * batch * r->K, mem, false, st);
     if (mi.rc | mo.rc) return FHE_ERR_HIP;
-    launch_extend(r, mi.d, size_t(r->L) * n, mo.d, size_t(r->K) * n, n, batch, st);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(launch_extend(r, mi.d, size_t(r->L) * n, mo.d, size_t(r->K) * n, n, batch, st));
     return mo.sync_out(st);
 }
 
@@ -479,8 +481,7 @@ int fhe_rns_switch_bases(const fhe_rns_ctx *r, int to_qs, const uint64_t *in, ui
     const size_t la = to_qs ? r->K : r->L, lb = to_qs ? r->L : r->K;
     Mirror mi(in, n * batch * la, mem, true, st), mo(out, n * batch * lb, mem, false, st);
     if (mi.rc | mo.rc) return FHE_ERR_HIP;
-    launch_extend(r, mi.d, la * n, mo.d, lb * n, n, batch, st, nullptr, 0, to_qs != 0);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(launch_extend(r, mi.d, la * n, mo.d, lb * n, n, batch, st, nullptr, 0, to_qs != 0));
     return mo.sync_out(st);
 }
 
@@ -494,8 +495,7 @@ int fhe_rns_rescale_k(const fhe_rns_ctx *r, const uint64_t *in, uint64_t *out, s
     const size_t lk = size_t(r->L + r->K);
     Mirror mi(in, n * batch * lk, mem, true, st), mo(out, n * batch * r->L, mem, false, st);
     if (mi.rc | mo.rc) return FHE_ERR_HIP;
-    launch_rescale(r, false, rescale_in_block(mi.d, lk * n, r->L, r->K, n), mo.d, size_t(r->L) * n, nullptr, 0, n, batch, st);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(launch_rescale(r, false, rescale_in_block(mi.d, lk * n, r->L, r->K, n), mo.d, size_t(r->L) * n, nullptr, 0, n, batch, st));
     return mo.sync_out(st);
 }
 
@@ -539,9 +539,8 @@ int fhe_rns_pointwise_mul(const fhe_rns_ctx *r, int extended, uint64_t *a, const
     Mirror ma(a, count, mem, true, st), mb(b, count, mem, true, st);
     if (ma.rc | mb.rc) return FHE_ERR_HIP;
     if (n >> 31) return FHE_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(fhe::rns_pointwise_kernel, PointwiseGrid(n, batch * limbs).g, dim3(256), 0, st, ma.d, (const u64 *)mb.d, (unsigned)n,
-                       (unsigned)limbs, batch * limbs, (const fhe::Barrett *)r->d_barrett);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::rns_pointwise_kernel>(PointwiseGrid(n, batch * limbs).g, 256, 0, st, ma.d, (const u64 *)mb.d, (unsigned)n, (unsigned)limbs,
+                                                   batch * limbs, (const fhe::Barrett *)r->d_barrett));
     return ma.sync_out(st);
 }
 
@@ -557,9 +556,8 @@ int rns_addsub(const fhe_rns_ctx *r, int extended, uint64_t *a, const uint64_t *
     Mirror ma(a, count, mem, true, st), mb(b, op != 2 ? count : 0, mem, true, st);
     if (ma.rc | mb.rc) return FHE_ERR_HIP;
     if (n >> 31) return FHE_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(fhe::rns_addsub_kernel, PointwiseGrid(n, batch * limbs).g, dim3(256), 0, st, ma.d, (const u64 *)mb.d, (unsigned)n, (unsigned)limbs,
-                       batch * limbs, (const fhe::Barrett *)r->d_barrett, op);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::rns_addsub_kernel>(PointwiseGrid(n, batch * limbs).g, 256, 0, st, ma.d, (const u64 *)mb.d, (unsigned)n, (unsigned)limbs,
+                                                batch * limbs, (const fhe::Barrett *)r->d_barrett, op));
     return ma.sync_out(st);
 }
 }  // namespace
@@ -630,8 +628,7 @@ int key_switch_dev(const fhe_rns_ctx *r, const fhe_ckks_key *key, const u64 *a_i
     if (log_n == 15 && r->pm && r->L <= 8 && r->K <= 8 && edge_enabled()) {  // (wider bases: two limb vectors per thread would spill)
         // N = 2^15 (cfg4): layer 0 of the forward transforms runs inside the extend kernel, layer 0 of the inverse ones (and n^-1)
         // inside the rescales; the transform launches are 2^14 sub-transforms, two workgroups per CU (rns_kernels.hpp)
-        launch_extend_edge(r, a_in, L * n, ext, lk * n, n, batch, st);
-        if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
+        rc = launch_extend_edge(r, a_in, L * n, ext, lk * n, n, batch, st);
         if (rc == FHE_OK) rc = fhe::ntt_fwd_inner15(r->d_descs, (unsigned)lk, ext, batch * lk, st, r->all_pm);
         if (rc == FHE_OK) {
             fhe::NttIo io;
@@ -639,16 +636,12 @@ int key_switch_dev(const fhe_rns_ctx *r, const fhe_ckks_key *key, const u64 *a_i
             io.mul = key->d_kb; io.mul_div = (unsigned)(batch * lk); io.mul_period = (unsigned)lk;
             rc = fhe::ntt_inv_inner15(r->d_descs, (unsigned)lk, pb, 2 * batch * lk, st, r->all_pm, io);
         }
-        if (rc == FHE_OK) {
-            launch_rescale_edge(r, rescale_in_block(pb, lk * n, r->L, r->K, n), out_b, L * n, add_b, L * n, n, batch, st);
-            launch_rescale_edge(r, rescale_in_block(pb + blk, lk * n, r->L, r->K, n), out_a, L * n, add_a, L * n, n, batch, st);
-            if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
-        }
+        if (rc == FHE_OK) rc = launch_rescale_edge(r, rescale_in_block(pb, lk * n, r->L, r->K, n), out_b, L * n, add_b, L * n, n, batch, st);
+        if (rc == FHE_OK) rc = launch_rescale_edge(r, rescale_in_block(pb + blk, lk * n, r->L, r->K, n), out_a, L * n, add_a, L * n, n, batch, st);
         return rc;
     }
     // ext[:, :L] = ct_a; ext[:, L:] = extend_bases(ct_a, ps): one kernel, the q-limbs written back out of the registers it read them into
-    launch_extend(r, a_in, L * n, ext + L * n, lk * n, n, batch, st, ext, lk * n);
-    if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
+    rc = launch_extend(r, a_in, L * n, ext + L * n, lk * n, n, batch, st, ext, lk * n);
     if (rc == FHE_OK && n > 1) rc = fhe::ntt_fwd_multi(r->d_descs, (unsigned)lk, ext, log_n, batch * lk, st, r->all_pm);
     // ksk.b * a~ and ksk.a * a~ (ring/rns.rs:148-158) ride on the load of ONE inverse launch over the 2 * batch * lk output
     // limbs: output limb s reads a~ limb s % (batch lk) and key limb (s / (batch lk)) lk + s % lk (d_kb and d_ka are adjacent)
@@ -658,15 +651,11 @@ int key_switch_dev(const fhe_rns_ctx *r, const fhe_ckks_key *key, const u64 *a_i
         io.mul = key->d_kb; io.mul_div = (unsigned)(batch * lk); io.mul_period = (unsigned)lk;
         rc = fhe::ntt_inv_multi(r->d_descs, (unsigned)lk, pb, log_n, 2 * batch * lk, st, r->all_pm, io);
     } else if (rc == FHE_OK) {
-        hipLaunchKernelGGL(fhe::rns_pointwise2_kernel, PointwiseGrid(n, batch * lk).g, dim3(256), 0, st, (const u64 *)ext, (const u64 *)key->d_kb,
-                           (const u64 *)key->d_ka, pb, pb + blk, (unsigned)n, (unsigned)lk, batch * lk, (const fhe::Barrett *)r->d_barrett);
-        if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
+        rc = fhe::launch<fhe::rns_pointwise2_kernel>(PointwiseGrid(n, batch * lk).g, 256, 0, st, (const u64 *)ext, (const u64 *)key->d_kb, (const u64 *)key->d_ka,
+                                                     pb, pb + blk, (unsigned)n, (unsigned)lk, batch * lk, (const fhe::Barrett *)r->d_barrett);
     }
-    if (rc == FHE_OK) {
-        launch_rescale(r, false, rescale_in_block(pb, lk * n, r->L, r->K, n), out_b, L * n, add_b, L * n, n, batch, st);
-        launch_rescale(r, false, rescale_in_block(pb + blk, lk * n, r->L, r->K, n), out_a, L * n, add_a, L * n, n, batch, st);
-        if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
-    }
+    if (rc == FHE_OK) rc = launch_rescale(r, false, rescale_in_block(pb, lk * n, r->L, r->K, n), out_b, L * n, add_b, L * n, n, batch, st);
+    if (rc == FHE_OK) rc = launch_rescale(r, false, rescale_in_block(pb + blk, lk * n, r->L, r->K, n), out_a, L * n, add_a, L * n, n, batch, st);
     return rc;
 }
 }  // namespace
@@ -761,10 +750,9 @@ int fhe_ckks_shard_products(const fhe_ckks_shard *sh, const uint64_t *ct_a, uint
     StreamWs wsp((batch * nl * n + (split ? 0 : 2 * batch * nl * n)) * sizeof(u64), st);  // ext [batch][nl][n] (| prod [2][batch][nl][n])
     if (wsp.rc != FHE_OK) return wsp.rc;
     u64 *ext = wsp.as<u64>(), *tmp = ext + batch * nl * n;
-    int rc = FHE_OK;
-    if (sh->edge) launch_extend_edge(r, ma.d, L * n, ext, size_t(nl) * n, n, batch, st, sh->q_lo, sh->q_hi, sh->p_lo, sh->p_hi);
-    else launch_extend(r, ma.d, L * n, ext + size_t(nq) * n, size_t(nl) * n, n, batch, st, ext, size_t(nl) * n, false, sh->q_lo, sh->q_hi, sh->p_lo, sh->p_hi);
-    if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
+    int rc = sh->edge ? launch_extend_edge(r, ma.d, L * n, ext, size_t(nl) * n, n, batch, st, sh->q_lo, sh->q_hi, sh->p_lo, sh->p_hi)
+                      : launch_extend(r, ma.d, L * n, ext + size_t(nq) * n, size_t(nl) * n, n, batch, st, ext, size_t(nl) * n, false, sh->q_lo,
+                                      sh->q_hi, sh->p_lo, sh->p_hi);
     if (rc == FHE_OK && n > 1)
         rc = sh->edge ? fhe::ntt_fwd_inner15(sh->d_descs, (unsigned)nl, ext, batch * nl, st, r->all_pm)
                       : fhe::ntt_fwd_multi(sh->d_descs, (unsigned)nl, ext, log_n, batch * nl, st, r->all_pm);
@@ -777,14 +765,12 @@ int fhe_ckks_shard_products(const fhe_ckks_shard *sh, const uint64_t *ct_a, uint
         rc = sh->edge ? fhe::ntt_inv_inner15(sh->d_descs, (unsigned)nl, dst, 2 * batch * nl, st, r->all_pm, io)
                       : fhe::ntt_inv_multi(sh->d_descs, (unsigned)nl, dst, log_n, 2 * batch * nl, st, r->all_pm, io);
     } else if (rc == FHE_OK) {  // n = 1: the ring product is the scalar product
-        hipLaunchKernelGGL(fhe::rns_pointwise2_desc_kernel, PointwiseGrid(n, batch * nl).g, dim3(256), 0, st, (const u64 *)ext, (const u64 *)sh->d_key,
-                           (const u64 *)(sh->d_key + size_t(nl) * n), tmp, tmp + batch * nl * n, (unsigned)n, (unsigned)nl, batch * nl, (const fhe::ModDesc *)sh->d_descs);
-        if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
+        rc = fhe::launch<fhe::rns_pointwise2_desc_kernel>(PointwiseGrid(n, batch * nl).g, 256, 0, st, (const u64 *)ext, (const u64 *)sh->d_key,
+                                                          (const u64 *)(sh->d_key + size_t(nl) * n), tmp, tmp + batch * nl * n, (unsigned)n, (unsigned)nl,
+                                                          batch * nl, (const fhe::ModDesc *)sh->d_descs);
     }
-    if (rc == FHE_OK && !split) {
-        hipLaunchKernelGGL(fhe::rns_split_limbs_kernel, dim3(grid_for(2 * batch * nl * n)), dim3(256), 0, st, (const u64 *)tmp, mq.d, mp.d, n, 2 * batch, nl, nq);
-        if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
-    }
+    if (rc == FHE_OK && !split)
+        rc = fhe::launch<fhe::rns_split_limbs_kernel>(grid_for(2 * batch * nl * n), 256, 0, st, (const u64 *)tmp, mq.d, mp.d, n, 2 * batch, nl, nq);
     if (rc == FHE_OK) rc = mq.sync_out(st);
     if (rc == FHE_OK) rc = mp.sync_out(st);
     return rc;
@@ -812,10 +798,9 @@ int fhe_ckks_shard_finish(const fhe_ckks_shard *sh, const uint64_t *prod_q, cons
         for (int j = 0; j < K; ++j) I.off[j] = size_t(j / np) * 2 * pw + size_t(j % np) * n;
         u64 *o = part ? moa.d : mob.d;
         const u64 *add = part ? nullptr : (ct_b ? mb.d : nullptr);
-        if (sh->edge) launch_rescale_edge(r, I, o, size_t(nq) * n, add, size_t(nq) * n, n, batch, st, sh->q_lo, sh->q_hi);
-        else launch_rescale(r, false, I, o, size_t(nq) * n, add, size_t(nq) * n, n, batch, st, sh->q_lo, sh->q_hi);
+        FHE_TRY(sh->edge ? launch_rescale_edge(r, I, o, size_t(nq) * n, add, size_t(nq) * n, n, batch, st, sh->q_lo, sh->q_hi)
+                         : launch_rescale(r, false, I, o, size_t(nq) * n, add, size_t(nq) * n, n, batch, st, sh->q_lo, sh->q_hi));
     }
-    HIP_TRY(hipGetLastError());
     int rc = mob.sync_out(st);
     return rc != FHE_OK ? rc : moa.sync_out(st);
 }
@@ -832,8 +817,7 @@ int fhe_rns_rescale(const fhe_rns_ctx *r, const uint64_t *in, uint64_t *out, siz
     const size_t L = r->L;
     Mirror mi(in, n * batch * L, mem, true, st), mo(out, n * batch * (L - 1), mem, false, st);
     if (mi.rc | mo.rc) return FHE_ERR_HIP;
-    launch_rescale(r, true, rescale_in_block(mi.d, L * n, r->L - 1, 1, n), mo.d, (L - 1) * n, nullptr, 0, n, batch, st);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(launch_rescale(r, true, rescale_in_block(mi.d, L * n, r->L - 1, 1, n), mo.d, (L - 1) * n, nullptr, 0, n, batch, st));
     return mo.sync_out(st);
 }
 
@@ -851,9 +835,8 @@ int fhe_rns_automorphism(const fhe_rns_ctx *r, int64_t t, const uint64_t *in, ui
     const size_t L = r->L;
     Mirror mi(in, n * batch * L, mem, true, st), mo(out, n * batch * L, mem, false, st);
     if (mi.rc | mo.rc) return FHE_ERR_HIP;
-    hipLaunchKernelGGL(fhe::rns_automorphism_kernel, PointwiseGrid(n, batch * L).g, dim3(256), 0, st, (const u64 *)mi.d, mo.d, (unsigned)n, (unsigned)L,
-                       batch * L, tt, (const fhe::Barrett *)r->d_barrett);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::rns_automorphism_kernel>(PointwiseGrid(n, batch * L).g, 256, 0, st, (const u64 *)mi.d, mo.d, (unsigned)n, (unsigned)L,
+                                                      batch * L, tt, (const fhe::Barrett *)r->d_barrett));
     return mo.sync_out(st);
 }
 
@@ -876,11 +859,10 @@ int fhe_ckks_rotate(const fhe_rns_ctx *r, const fhe_ckks_key *key, int64_t t, ui
     StreamWs rot(2 * words * sizeof(u64), st);
     if (rot.rc != FHE_OK) return rot.rc;
     u64 *rb = rot.as<u64>(), *ra = rb + words;
-    hipLaunchKernelGGL(fhe::rns_automorphism_kernel, PointwiseGrid(n, batch * L).g, dim3(256), 0, st, (const u64 *)mb.d, rb, (unsigned)n, (unsigned)L,
-                       batch * L, tt, (const fhe::Barrett *)r->d_barrett);
-    hipLaunchKernelGGL(fhe::rns_automorphism_kernel, PointwiseGrid(n, batch * L).g, dim3(256), 0, st, (const u64 *)ma.d, ra, (unsigned)n, (unsigned)L,
-                       batch * L, tt, (const fhe::Barrett *)r->d_barrett);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::rns_automorphism_kernel>(PointwiseGrid(n, batch * L).g, 256, 0, st, (const u64 *)mb.d, rb, (unsigned)n, (unsigned)L,
+                                                      batch * L, tt, (const fhe::Barrett *)r->d_barrett));
+    FHE_TRY(fhe::launch<fhe::rns_automorphism_kernel>(PointwiseGrid(n, batch * L).g, 256, 0, st, (const u64 *)ma.d, ra, (unsigned)n, (unsigned)L,
+                                                      batch * L, tt, (const fhe::Barrett *)r->d_barrett));
     int rc = key_switch_dev(r, key, ra, rb, nullptr, mb.d, ma.d, batch, st);
     if (rc == FHE_OK) rc = mb.sync_out(st);
     if (rc == FHE_OK) rc = ma.sync_out(st);
@@ -924,19 +906,14 @@ int fhe_ckks_mul(const fhe_rns_ctx *r, const fhe_ckks_key *rlk, const uint64_t *
             rc = fhe::ntt_fwd_multi(r->d_descs, (unsigned)L, e + i * words, log_n, batch * L, st, r->all_pm, io);
         } else if (hipMemcpyAsync(e + i * words, src[i], words * sizeof(u64), hipMemcpyDeviceToDevice, st) != hipSuccess) rc = FHE_ERR_HIP;
     }
-    if (rc == FHE_OK) {
-        hipLaunchKernelGGL(fhe::rns_tensor_kernel, PointwiseGrid(n, batch * L).g, dim3(256), 0, st, (const u64 *)e, d, (unsigned)n, (unsigned)L, batch * L,
-                           (const fhe::Barrett *)r->d_barrett);
-        if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
-    }
+    if (rc == FHE_OK)
+        rc = fhe::launch<fhe::rns_tensor_kernel>(PointwiseGrid(n, batch * L).g, 256, 0, st, (const u64 *)e, d, (unsigned)n, (unsigned)L, batch * L,
+                                                 (const fhe::Barrett *)r->d_barrett);
     if (rc == FHE_OK && n > 1) rc = fhe::ntt_inv_multi(r->d_descs, (unsigned)L, d, log_n, 3 * batch * L, st, r->all_pm);
     // (d0, d1) + relinearize(d2) (ckks.rs:262, 265-272): the key switch adds d0 and d1 as it rescales; its outputs reuse e
     if (rc == FHE_OK) rc = key_switch_dev(r, rlk, d + 2 * words, d, d + words, e, e + words, batch, st);
-    if (rc == FHE_OK) {
-        launch_rescale(r, true, rescale_in_block(e, L * n, r->L - 1, 1, n), mob.d, (L - 1) * n, nullptr, 0, n, batch, st);
-        launch_rescale(r, true, rescale_in_block(e + words, L * n, r->L - 1, 1, n), moa.d, (L - 1) * n, nullptr, 0, n, batch, st);
-        if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
-    }
+    if (rc == FHE_OK) rc = launch_rescale(r, true, rescale_in_block(e, L * n, r->L - 1, 1, n), mob.d, (L - 1) * n, nullptr, 0, n, batch, st);
+    if (rc == FHE_OK) rc = launch_rescale(r, true, rescale_in_block(e + words, L * n, r->L - 1, 1, n), moa.d, (L - 1) * n, nullptr, 0, n, batch, st);
     if (rc == FHE_OK) rc = mob.sync_out(st);
     if (rc == FHE_OK) rc = moa.sync_out(st);
     return rc;
@@ -953,24 +930,20 @@ int ckks_sk_encrypt_dev(const fhe_rns_ctx *r, int limbs, const u64 *sk, const u6
     StreamWs ws((size_t(limbs) * n + batch * n) * sizeof(u64), st);
     if (ws.rc != FHE_OK) return ws.rc;
     u64 *s_eval = ws.as<u64>(), *e = s_eval + size_t(limbs) * n;
-    hipLaunchKernelGGL(fhe::rns_from_i64_kernel, dim3(grid_for(n * limbs)), dim3(256), 0, st, sk, s_eval, n, limbs, (const fhe::Barrett *)r->d_barrett,
-                       (const u64 *)nullptr);
-    int rc = hipGetLastError() == hipSuccess ? FHE_OK : FHE_ERR_HIP;
+    int rc = fhe::launch<fhe::rns_from_i64_kernel>(grid_for(n * limbs), 256, 0, st, sk, s_eval, n, limbs, (const fhe::Barrett *)r->d_barrett,
+                                                   (const u64 *)nullptr, (size_t)1);
     if (rc == FHE_OK) rc = fhe::ntt_fwd_multi(r->d_descs, (unsigned)limbs, s_eval, log_n, limbs, st, r->all_pm);
     for (size_t c = 0; c < batch && rc == FHE_OK; ++c)
         for (int l = 0; l < limbs && rc == FHE_OK; ++l) {  // one modulus per launch: set-up code
             const uint64_t m = l < r->L ? r->qs[l] : r->ps[l - r->L];
-            hipLaunchKernelGGL(fhe::sample_uniform_kernel, dim3(grid_for((n + 3) / 4)), dim3(256), 0, st, out_a + (c * limbs + l) * n, n, fhe::make_barrett(m), K,
-                               *cursor);
+            rc = fhe::launch<fhe::sample_uniform_kernel>(grid_for((n + 3) / 4), 256, 0, st, out_a + (c * limbs + l) * n, n, fhe::make_barrett(m), K, *cursor);
             *cursor += (n + 3) / 4;
-            if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
         }
     fhe::DgTable T;
     if (rc == FHE_OK && !fhe::make_dg_table(3.2, 6, &T)) rc = FHE_ERR_UNSUPPORTED;  // dg(3.2, 6): 39 entries
     if (rc == FHE_OK) {
-        hipLaunchKernelGGL(fhe::sample_dg_kernel, dim3(grid_for((batch * n + 7) / 8)), dim3(256), 0, st, e, batch * n, (u64)0, T, K, *cursor);
+        rc = fhe::launch<fhe::sample_dg_kernel>(grid_for((batch * n + 7) / 8), 256, 0, st, e, batch * n, (u64)0, T, K, *cursor);
         *cursor += (batch * n + 7) / 8;
-        if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
     }
     if (rc == FHE_OK) {  // a s: forward of a out of place into b, inverse with the evaluation-domain key on its load (limb s % limbs)
         fhe::NttIo src;
@@ -982,11 +955,9 @@ int ckks_sk_encrypt_dev(const fhe_rns_ctx *r, int limbs, const u64 *sk, const u6
         mul.mul = s_eval; mul.mul_div = (unsigned)(batch * limbs); mul.mul_period = (unsigned)limbs;
         rc = fhe::ntt_inv_multi(r->d_descs, (unsigned)limbs, out_b, log_n, batch * limbs, st, r->all_pm, mul);
     }
-    if (rc == FHE_OK) {
-        hipLaunchKernelGGL(fhe::ckks_finish_b_kernel, dim3(grid_for(batch * limbs * n)), dim3(256), 0, st, out_b, (const u64 *)e, pt, n, limbs, batch,
-                           pt ? pt_batch : 1, (const fhe::Barrett *)r->d_barrett, 1);
-        if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
-    }
+    if (rc == FHE_OK)
+        rc = fhe::launch<fhe::ckks_finish_b_kernel>(grid_for(batch * limbs * n), 256, 0, st, out_b, (const u64 *)e, pt, n, limbs, batch, pt ? pt_batch : 1,
+                                                    (const fhe::Barrett *)r->d_barrett, 1);
     return rc;
 }
 
@@ -1024,8 +995,7 @@ int fhe_sample_zo(double rho, const fhe_rng *rng, uint64_t stream_id, uint64_t *
     hipStream_t st = (hipStream_t)stream;
     Mirror mo(out, count, mem, false, st);
     if (mo.rc != FHE_OK) return mo.rc;
-    hipLaunchKernelGGL(fhe::sample_zo_kernel, dim3(grid_for((count + 7) / 8)), dim3(256), 0, st, mo.d, count, rho, fhe::call_key(rng, stream_id, fhe::RNG_SAMPLE_ZO), 0ull);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::sample_zo_kernel>(grid_for((count + 7) / 8), 256, 0, st, mo.d, count, rho, fhe::call_key(rng, stream_id, fhe::RNG_SAMPLE_ZO), 0ull));
     return mo.sync_out(st);
 }
 
@@ -1076,14 +1046,11 @@ int fhe_ckks_ksk_gen(const fhe_rns_ctx *r, const uint64_t *sk, const uint64_t *s
         // sk^2 over Z is computed mod q_0 and lifted back centred: exact only while n max|sk_i|^2 < q_0 / 2 (ternary keys from
         // fhe_sample_zo: |coefficient| <= n).  The bound is CHECKED on the device: any other key is an error, not a wrong key.
         if (hipMemsetAsync(d_max, 0, sizeof(u64), st) != hipSuccess) rc = FHE_ERR_HIP;
-        if (rc == FHE_OK) {
-            hipLaunchKernelGGL(fhe::max_abs_i64_kernel, dim3(grid_for(n)), dim3(256), 0, st, (const u64 *)msk.d, n, (unsigned long long *)d_max);
-            if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
-        }
+        if (rc == FHE_OK) rc = fhe::launch<fhe::max_abs_i64_kernel>(grid_for(n), 256, 0, st, (const u64 *)msk.d, n, (unsigned long long *)d_max);
         if (rc == FHE_OK && hipMemcpyAsync(&sk_max, d_max, sizeof(u64), hipMemcpyDeviceToHost, st) != hipSuccess) rc = FHE_ERR_HIP;
-        hipLaunchKernelGGL(fhe::rns_from_i64_kernel, dim3(grid_for(n)), dim3(256), 0, st, (const u64 *)msk.d, sq, n, 1, (const fhe::Barrett *)r->d_barrett,
-                           (const u64 *)nullptr);
-        if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
+        if (rc == FHE_OK)
+            rc = fhe::launch<fhe::rns_from_i64_kernel>(grid_for(n), 256, 0, st, (const u64 *)msk.d, sq, n, 1, (const fhe::Barrett *)r->d_barrett,
+                                                       (const u64 *)nullptr, (size_t)1);
         if (rc == FHE_OK) rc = fhe::ntt_fwd_multi(r->d_descs, 1, sq, log_n, 1, st, r->mods[0]->pm_b);
         if (rc == FHE_OK) {
             fhe::NttIo io;
@@ -1091,10 +1058,7 @@ int fhe_ckks_ksk_gen(const fhe_rns_ctx *r, const uint64_t *sk, const uint64_t *s
             if (hipMemcpyAsync(sq + n, sq, n * sizeof(u64), hipMemcpyDeviceToDevice, st) != hipSuccess) rc = FHE_ERR_HIP;
             if (rc == FHE_OK) rc = fhe::ntt_inv_multi(r->d_descs, 1, sq + n, log_n, 1, st, r->mods[0]->pm_b, io);
         }
-        if (rc == FHE_OK) {
-            hipLaunchKernelGGL(fhe::centre_to_i64_kernel, dim3(grid_for(n)), dim3(256), 0, st, (const u64 *)(sq + n), sq, n, (u64)r->qs[0]);
-            if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
-        }
+        if (rc == FHE_OK) rc = fhe::launch<fhe::centre_to_i64_kernel>(grid_for(n), 256, 0, st, (const u64 *)(sq + n), sq, n, (u64)r->qs[0]);
         spr = sq;
     }
     // pt = RnsRq::from_i64(qps, sk') * P (ckks.rs:160): P mod p_j = 0, so the p-limbs of pt vanish
@@ -1106,11 +1070,8 @@ int fhe_ckks_ksk_gen(const fhe_rns_ctx *r, const uint64_t *sk, const uint64_t *s
         const fhe::u128 bound = (fhe::u128)n * sk_max * sk_max;
         if (sk_max >> 31 || bound >= (fhe::u128)(r->qs[0] / 2)) rc = FHE_ERR_INVALID;
     }
-    if (rc == FHE_OK) {
-        hipLaunchKernelGGL(fhe::rns_from_i64_kernel, dim3(grid_for(words)), dim3(256), 0, st, spr, pt, n, limbs, (const fhe::Barrett *)r->d_barrett,
-                           (const u64 *)d_pm);
-        if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
-    }
+    if (rc == FHE_OK)
+        rc = fhe::launch<fhe::rns_from_i64_kernel>(grid_for(words), 256, 0, st, spr, pt, n, limbs, (const fhe::Barrett *)r->d_barrett, (const u64 *)d_pm, (size_t)1);
     unsigned long long cursor = 0;
     if (rc == FHE_OK) rc = ckks_sk_encrypt_dev(r, limbs, msk.d, pt, 1, mb.d, ma.d, log_n, 1, fhe::call_key(rng, stream_id, fhe::RNG_CKKS_KSK), &cursor, st);
     if (rc == FHE_OK) rc = mb.sync_out(st);
@@ -1137,9 +1098,8 @@ int fhe_ckks_decrypt(const fhe_rns_ctx *r, const uint64_t *sk, const uint64_t *c
     StreamWs ws((size_t(L) * n + words) * sizeof(u64), st);  // the key's evaluations | a s
     if (ws.rc != FHE_OK) return ws.rc;
     u64 *s_eval = ws.as<u64>(), *as = s_eval + size_t(L) * n;
-    hipLaunchKernelGGL(fhe::rns_from_i64_kernel, dim3(grid_for(n * L)), dim3(256), 0, st, (const u64 *)msk.d, s_eval, n, L, (const fhe::Barrett *)r->d_barrett,
-                       (const u64 *)nullptr, (size_t)1);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::rns_from_i64_kernel>(grid_for(n * L), 256, 0, st, (const u64 *)msk.d, s_eval, n, L, (const fhe::Barrett *)r->d_barrett,
+                                                  (const u64 *)nullptr, (size_t)1));
     rc = fhe::ntt_fwd_multi(r->d_descs, (unsigned)L, s_eval, log_n, L, st, r->all_pm);
     if (rc == FHE_OK) {
         fhe::NttIo src;
@@ -1153,9 +1113,8 @@ int fhe_ckks_decrypt(const fhe_rns_ctx *r, const uint64_t *sk, const uint64_t *c
     }
     if (rc != FHE_OK) return rc;
     // pt = a s + b: formed in the scratch, then moved (pt may be ct_b itself)
-    hipLaunchKernelGGL(fhe::ckks_finish_b_kernel, dim3(grid_for(words)), dim3(256), 0, st, as, (const u64 *)nullptr, (const u64 *)mb.d, n, L, batch, batch,
-                       (const fhe::Barrett *)r->d_barrett, 0);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::ckks_finish_b_kernel>(grid_for(words), 256, 0, st, as, (const u64 *)nullptr, (const u64 *)mb.d, n, L, batch, batch,
+                                                   (const fhe::Barrett *)r->d_barrett, 0));
     HIP_TRY(hipMemcpyAsync(mo.d, as, words * sizeof(u64), hipMemcpyDeviceToDevice, st));
     return mo.sync_out(st);
 }
@@ -1184,29 +1143,26 @@ int fhe_ckks_pk_encrypt(const fhe_rns_ctx *r, const uint64_t *pk_b, const uint64
     u64 *pk_eval = ws.as<u64>(), *u = pk_eval + 2 * kw, *e0 = u + batch * n, *e1 = e0 + batch * n;
     const fhe::ChaChaKey K = fhe::call_key(rng, stream_id, fhe::RNG_CKKS_PK_ENC);
     unsigned long long cursor = 0;
-    hipLaunchKernelGGL(fhe::sample_zo_kernel, dim3(grid_for((batch * n + 7) / 8)), dim3(256), 0, st, u, batch * n, 0.5, K, cursor);
+    FHE_TRY(fhe::launch<fhe::sample_zo_kernel>(grid_for((batch * n + 7) / 8), 256, 0, st, u, batch * n, 0.5, K, cursor));
     cursor += (batch * n + 7) / 8;
-    HIP_TRY(hipGetLastError());
     fhe::DgTable T;
     if (!fhe::make_dg_table(3.2, 6, &T)) return FHE_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(fhe::sample_dg_kernel, dim3(grid_for((2 * batch * n + 7) / 8)), dim3(256), 0, st, e0, 2 * batch * n, (u64)0, T, K, cursor);  // e0 | e1
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::sample_dg_kernel>(grid_for((2 * batch * n + 7) / 8), 256, 0, st, e0, 2 * batch * n, (u64)0, T, K, cursor));  // e0 | e1
     rc = fwd_two_sources(r, mpb.d, mpa.d, pk_eval, log_n, L, st);  // pk.b, pk.a -> evaluation domain
     // u over every limb into both outputs' buffers, forward, then the inverse transforms multiply by pk.b / pk.a on their loads
     for (int half = 0; half < 2 && rc == FHE_OK; ++half) {
         u64 *o = half ? ma.d : mb.d;
-        hipLaunchKernelGGL(fhe::rns_from_i64_kernel, dim3(grid_for(words)), dim3(256), 0, st, (const u64 *)u, o, n, L, (const fhe::Barrett *)r->d_barrett,
-                           (const u64 *)nullptr, batch);
-        if (hipGetLastError() != hipSuccess) { rc = FHE_ERR_HIP; break; }
+        rc = fhe::launch<fhe::rns_from_i64_kernel>(grid_for(words), 256, 0, st, (const u64 *)u, o, n, L, (const fhe::Barrett *)r->d_barrett,
+                                                   (const u64 *)nullptr, batch);
+        if (rc != FHE_OK) break;
         rc = fhe::ntt_fwd_multi(r->d_descs, (unsigned)L, o, log_n, batch * L, st, r->all_pm);
         if (rc != FHE_OK) break;
         fhe::NttIo mul;
         mul.mul = pk_eval + (half ? kw : 0); mul.mul_div = (unsigned)(batch * L); mul.mul_period = (unsigned)L;
         rc = fhe::ntt_inv_multi(r->d_descs, (unsigned)L, o, log_n, batch * L, st, r->all_pm, mul);
         if (rc != FHE_OK) break;
-        hipLaunchKernelGGL(fhe::ckks_finish_b_kernel, dim3(grid_for(words)), dim3(256), 0, st, o, (const u64 *)(half ? e0 : e1),
-                           (const u64 *)(half ? nullptr : (pt ? mpt.d : nullptr)), n, L, batch, batch, (const fhe::Barrett *)r->d_barrett, 0);
-        if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
+        rc = fhe::launch<fhe::ckks_finish_b_kernel>(grid_for(words), 256, 0, st, o, (const u64 *)(half ? e0 : e1),
+                                                    (const u64 *)(half ? nullptr : (pt ? mpt.d : nullptr)), n, L, batch, batch, (const fhe::Barrett *)r->d_barrett, 0);
     }
     if (rc == FHE_OK) rc = mb.sync_out(st);
     if (rc == FHE_OK) rc = ma.sync_out(st);
@@ -1245,9 +1201,8 @@ int fhe_ckks_mul_plain(const fhe_rns_ctx *r, const uint64_t *pt, size_t pt_batch
         rc = fhe::ntt_inv_multi(r->d_descs, (unsigned)L, prod, log_n, 2 * batch * L, st, r->all_pm, mul);
     }
     if (rc != FHE_OK) return rc;
-    launch_rescale(r, true, rescale_in_block(prod, L * n, r->L - 1, 1, n), mob.d, (L - 1) * n, nullptr, 0, n, batch, st);
-    launch_rescale(r, true, rescale_in_block(prod + words, L * n, r->L - 1, 1, n), moa.d, (L - 1) * n, nullptr, 0, n, batch, st);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(launch_rescale(r, true, rescale_in_block(prod, L * n, r->L - 1, 1, n), mob.d, (L - 1) * n, nullptr, 0, n, batch, st));
+    FHE_TRY(launch_rescale(r, true, rescale_in_block(prod + words, L * n, r->L - 1, 1, n), moa.d, (L - 1) * n, nullptr, 0, n, batch, st));
     rc = mob.sync_out(st);
     return rc != FHE_OK ? rc : moa.sync_out(st);
 }

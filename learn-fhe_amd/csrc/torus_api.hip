@@ -80,12 +80,6 @@ template <int LN>
 using TorusRingF = fhe::WaveRing<LN - 1, (LN - 1 <= 8 ? LN - 1 - 6 : 2)>;
 constexpr int TF_MIN_WAVES = 2;
 
-template <class K>
-int set_lds(K kernel, size_t lds) {
-    if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return FHE_OK;
-}
-
 int launch_cmux(const fhe_torus_ctx *t, const fhe_tggsw_key *key, size_t index, u64 *a, u64 *b, size_t batch, const u64 *rot,
                 size_t rot_stride, hipStream_t st) {
     const size_t n = size_t(1) << key->log_n;
@@ -94,47 +88,34 @@ int launch_cmux(const fhe_torus_ctx *t, const fhe_tggsw_key *key, size_t index, 
         const double2 *frows = key->d_rowsf + index * (per / 2);
         TORUS_DISPATCH(key->log_n, {
             typedef TorusRingF<LN> WR;
-            hipLaunchKernelGGL((fhe::torusf_cmux_kernel<WR, TF_MIN_WAVES>), dim3((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS)), dim3(WR::THREADS),
-                               fhe::TorusF<WR>::LDS_BYTES, st, a, b, (unsigned)batch, frows, key->P, rot, rot_stride, (const double2 *)t->d_twf);
+            return fhe::launch<fhe::torusf_cmux_kernel<WR, TF_MIN_WAVES>>((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS, fhe::TorusF<WR>::LDS_BYTES,
+                                                                          st, a, b, (unsigned)batch, frows, key->P, rot, rot_stride, (const double2 *)t->d_twf);
         });
-        HIP_TRY(hipGetLastError());
-        return FHE_OK;
     }
     if (key->d_rowsx3) {  // exact, three key pieces through f64 transforms
         const double2 *xrows = key->d_rowsx3 + index * (per / 2) * 3;
         TORUS_DISPATCH(key->log_n, {
             typedef TorusRingF<LN> WR;
-            const size_t lds = fhe::TorusX3<WR>::lds_bytes(2 * key->d);
-            if (set_lds((fhe::torusx3_cmux_kernel<WR, TF_MIN_WAVES>), lds) != FHE_OK) return FHE_ERR_HIP;
-            hipLaunchKernelGGL((fhe::torusx3_cmux_kernel<WR, TF_MIN_WAVES>), dim3((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS)), dim3(WR::THREADS), lds, st, a, b,
-                               (unsigned)batch, xrows, key->P, rot, rot_stride, (const double2 *)t->d_twf);
+            return fhe::launch<fhe::torusx3_cmux_kernel<WR, TF_MIN_WAVES>>((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS,
+                                                                           fhe::TorusX3<WR>::lds_bytes(2 * key->d), st, a, b, (unsigned)batch, xrows, key->P, rot,
+                                                                           rot_stride, (const double2 *)t->d_twf);
         });
-        HIP_TRY(hipGetLastError());
-        return FHE_OK;
     }
     if (key->d_rows30) {  // three 30-bit primes
         const size_t plane = key->count * per;
         TORUS_DISPATCH(key->log_n, {
             typedef TorusRing30<LN> WR;
-            const size_t lds = WR::TORUS_LDS_BYTES;
-            if (lds > 64 * 1024)
-                HIP_TRY(hipFuncSetAttribute((const void *)fhe::torus30_cmux_kernel<WR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(fhe::torus30_cmux_kernel<WR>, dim3((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS)), dim3(WR::THREADS), lds, st, a, b,
-                               (unsigned)batch, (const unsigned *)(key->d_rows30 + index * per), plane, key->P, rot, rot_stride, t->T30);
+            return fhe::launch<fhe::torus30_cmux_kernel<WR>>((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS, WR::TORUS_LDS_BYTES, st, a, b,
+                                                             (unsigned)batch, (const unsigned *)(key->d_rows30 + index * per), plane, key->P, rot, rot_stride,
+                                                             t->T30);
         });
-        HIP_TRY(hipGetLastError());
-        return FHE_OK;
     }
     const u64 *rows0 = key->d_rows[0] + index * per, *rows1 = key->d_rows[1] + index * per;
     TORUS_DISPATCH(key->log_n, {
-        const size_t lds = TorusRing<LN>::TORUS_LDS_BYTES;
-        if (lds > 64 * 1024)
-            HIP_TRY(hipFuncSetAttribute((const void *)fhe::torus_cmux_kernel<TorusRing<LN>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(fhe::torus_cmux_kernel<TorusRing<LN>>, dim3((unsigned)((batch + TorusRing<LN>::TEAMS - 1) / TorusRing<LN>::TEAMS)), dim3(TorusRing<LN>::THREADS), lds, st, a, b, (unsigned)batch, rows0,
-                           rows1, key->P, rot, rot_stride, t->T);
+        typedef TorusRing<LN> WR;
+        return fhe::launch<fhe::torus_cmux_kernel<WR>>((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS, WR::TORUS_LDS_BYTES, st, a, b,
+                                                       (unsigned)batch, rows0, rows1, key->P, rot, rot_stride, t->T);
     });
-    HIP_TRY(hipGetLastError());
-    return FHE_OK;
 }
 
 }  // namespace
@@ -235,8 +216,7 @@ int fhe_torus_decompose(int log_b, int d, const uint64_t *in, size_t n, size_t p
     hipStream_t st = (hipStream_t)stream;
     Mirror mi(in, n * polys, mem, true, st), mo(out, n * polys * d, mem, false, st);
     if (mi.rc | mo.rc) return FHE_ERR_HIP;
-    hipLaunchKernelGGL(fhe::torus_decompose_kernel, dim3(grid_for(n * polys)), dim3(256), 0, st, mi.d, mo.d, n, polys, P);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::torus_decompose_kernel>(grid_for(n * polys), 256, 0, st, mi.d, mo.d, n, polys, P));
     return mo.sync_out(st);
 }
 
@@ -250,20 +230,13 @@ int torus_mul_dev(const fhe_torus_ctx *t, u64 *a, const u64 *b, size_t b_rows, i
     StreamWs wsp(2 * n * (batch + b_rows) * sizeof(u64), st);
     if (wsp.rc != FHE_OK) return wsp.rc;
     u64 *ra = wsp.as<u64>(), *rb = ra + 2 * n * batch;  // adjacent: one forward launch over both
-    hipLaunchKernelGGL(fhe::torus_residue2_kernel, dim3(grid_for(n * batch)), dim3(256), 0, st, (const u64 *)a, ra, n, batch, t->T.p0, t->T.p1);
-    hipLaunchKernelGGL(fhe::torus_residue2_kernel, dim3(grid_for(n * b_rows)), dim3(256), 0, st, b, rb, n, b_rows, t->T.p0, t->T.p1);
-    int rc = hipGetLastError() == hipSuccess ? FHE_OK : FHE_ERR_HIP;
+    int rc = fhe::launch<fhe::torus_residue2_kernel>(grid_for(n * batch), 256, 0, st, (const u64 *)a, ra, n, batch, t->T.p0, t->T.p1);
+    if (rc == FHE_OK) rc = fhe::launch<fhe::torus_residue2_kernel>(grid_for(n * b_rows), 256, 0, st, b, rb, n, b_rows, t->T.p0, t->T.p1);
     if (rc == FHE_OK) rc = fhe::ntt_fwd_multi(t->d_descs, 2, ra, log_n, 2 * (batch + b_rows), st, 60);
-    if (rc == FHE_OK) {
-        hipLaunchKernelGGL(fhe::torus_pointwise_kernel, dim3(grid_for(2 * n * batch)), dim3(256), 0, st, ra, (const u64 *)rb, n, batch, b_rows, t->T.B0,
-                           t->T.B1);
-        if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
-    }
+    if (rc == FHE_OK)
+        rc = fhe::launch<fhe::torus_pointwise_kernel>(grid_for(2 * n * batch), 256, 0, st, ra, (const u64 *)rb, n, batch, b_rows, t->T.B0, t->T.B1);
     if (rc == FHE_OK) rc = fhe::ntt_inv_multi(t->d_descs, 2, ra, log_n, 2 * batch, st, 60);
-    if (rc == FHE_OK) {
-        hipLaunchKernelGGL(fhe::torus_crt_kernel, dim3(grid_for(n * batch)), dim3(256), 0, st, (const u64 *)ra, a, n, batch, t->T);
-        if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
-    }
+    if (rc == FHE_OK) rc = fhe::launch<fhe::torus_crt_kernel>(grid_for(n * batch), 256, 0, st, (const u64 *)ra, a, n, batch, t->T);
     return rc;
 }
 }  // namespace
@@ -337,37 +310,31 @@ int fhe_tggsw_prepare(const fhe_torus_ctx *t, int log_b, int d, const uint64_t *
         if (rc == FHE_OK) {
             TORUS_DISPATCH(log_n, {
                 typedef TorusRingF<LN> WR;
-                hipLaunchKernelGGL(fhe::torusx3_key_prepare_kernel<WR>, dim3((unsigned)((6 * rows + WR::TEAMS - 1) / WR::TEAMS)), dim3(WR::THREADS),
-                                   fhe::TorusF<WR>::LDS_BYTES, st, (const u64 *)src, (const u64 *)(src + words), rows, (const double2 *)t->d_twf, dstx3);
+                rc = fhe::launch<fhe::torusx3_key_prepare_kernel<WR>>((unsigned)((6 * rows + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS, fhe::TorusF<WR>::LDS_BYTES,
+                                                                      st, (const u64 *)src, (const u64 *)(src + words), rows, (const double2 *)t->d_twf, dstx3);
             });
-            if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
         }
     } else if (rc == FHE_OK && use30) {
         if (hipMalloc((void **)&dst30, 3 * 2 * words * sizeof(unsigned)) != hipSuccess) rc = FHE_ERR_HIP;
         for (int pi = 0; pi < 3 && rc == FHE_OK; ++pi) {
             TORUS_DISPATCH(log_n, {
                 typedef TorusRing30<LN> WR;
-                if (WR::LDS_BYTES > 64 * 1024)
-                    HIP_TRY(hipFuncSetAttribute((const void *)fhe::torus30_key_prepare_kernel<WR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WR::LDS_BYTES));
-                hipLaunchKernelGGL(fhe::torus30_key_prepare_kernel<WR>, dim3((unsigned)((2 * rows + WR::TEAMS - 1) / WR::TEAMS)), dim3(WR::THREADS),
-                                   WR::LDS_BYTES, st, (const u64 *)src, (const u64 *)(src + words), rows, t->T30.descs + pi,
-                                   dst30 + size_t(pi) * 2 * words);
+                rc = fhe::launch<fhe::torus30_key_prepare_kernel<WR>>((unsigned)((2 * rows + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS, WR::LDS_BYTES, st,
+                                                                      (const u64 *)src, (const u64 *)(src + words), rows, t->T30.descs + pi,
+                                                                      dst30 + size_t(pi) * 2 * words);
             });
-            if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
         }
     } else if (rc == FHE_OK) {
         e = hipMalloc((void **)&tmp, 2 * words * sizeof(u64));
         if (e == hipSuccess) e = hipMalloc((void **)&dst, 4 * words * sizeof(u64));  // both primes
         if (e != hipSuccess) { g_last_hip = (int)e; rc = FHE_ERR_HIP; }
         for (int pi = 0; pi < 2 && rc == FHE_OK; ++pi) {
-            hipLaunchKernelGGL(fhe::torus_residue_kernel, dim3(grid_for(2 * words)), dim3(256), 0, st, (const u64 *)src, tmp, 2 * words,
-                               pi ? t->T.p1 : t->T.p0);
-            if (hipGetLastError() != hipSuccess) { rc = FHE_ERR_HIP; break; }
+            rc = fhe::launch<fhe::torus_residue_kernel>(grid_for(2 * words), 256, 0, st, (const u64 *)src, tmp, 2 * words, pi ? t->T.p1 : t->T.p0);
+            if (rc != FHE_OK) break;
             rc = fhe::ntt_fwd_multi(t->d_descs + pi, 1, tmp, log_n, 2 * rows, st, 60);
             if (rc != FHE_OK) break;
-            TORUS_DISPATCH(log_n, hipLaunchKernelGGL(fhe::key_permute_kernel<TorusRing<LN>>, dim3(grid_for(words)), dim3(256), 0, st, (const u64 *)tmp,
-                                                     (const u64 *)(tmp + words), dst + size_t(pi) * 2 * words, rows, 60));
-            if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
+            TORUS_DISPATCH(log_n, rc = fhe::launch<fhe::key_permute_kernel<TorusRing<LN>>>(grid_for(words), 256, 0, st, (const u64 *)tmp,
+                                                                                          (const u64 *)(tmp + words), dst + size_t(pi) * 2 * words, rows, 60));
         }
     }
     if (hipStreamSynchronize(st) != hipSuccess && rc == FHE_OK) rc = FHE_ERR_HIP;
@@ -404,10 +371,10 @@ int fhe_tggsw_prepare_fft64(const fhe_torus_ctx *t, int log_b, int d, const uint
     HIP_TRY(hipMalloc((void **)&dst, 2 * rows * (n / 2) * sizeof(double2)));
     TORUS_DISPATCH(log_n, {
         typedef TorusRingF<LN> WR;
-        hipLaunchKernelGGL(fhe::torusf_key_prepare_kernel<WR>, dim3((unsigned)((2 * rows + WR::TEAMS - 1) / WR::TEAMS)), dim3(WR::THREADS), fhe::TorusF<WR>::LDS_BYTES, st,
-                           (const u64 *)ma.d, (const u64 *)mb.d, rows, (const double2 *)t->d_twf, dst);
+        rc = fhe::launch<fhe::torusf_key_prepare_kernel<WR>>((unsigned)((2 * rows + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS, fhe::TorusF<WR>::LDS_BYTES, st,
+                                                             (const u64 *)ma.d, (const u64 *)mb.d, rows, (const double2 *)t->d_twf, dst);
     });
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { (void)hipFree(dst); return FHE_ERR_HIP; }
+    if (rc != FHE_OK || hipStreamSynchronize(st) != hipSuccess) { (void)hipFree(dst); return FHE_ERR_HIP; }
     fhe_tggsw_key *k = new (std::nothrow) fhe_tggsw_key();
     if (!k) { (void)hipFree(dst); return FHE_ERR_INVALID; }
     k->t = t; k->log_n = log_n; k->log_b = log_b; k->d = d; k->count = count; k->P = P; k->d_rowsf = dst;
@@ -449,15 +416,12 @@ int fhe_tggsw_cmux(const fhe_torus_ctx *t, const fhe_tggsw_key *key, size_t inde
     if (ws.rc != FHE_OK) return ws.rc;
     u64 *da = ws.as<u64>(), *db = da + words;
     const dim3 grid(grid_for(words));
-    hipLaunchKernelGGL(fhe::torus_addsub_kernel, grid, dim3(256), 0, st, (const u64 *)m1a.d, (const u64 *)m0a.d, da, words, 1);
-    hipLaunchKernelGGL(fhe::torus_addsub_kernel, grid, dim3(256), 0, st, (const u64 *)m1b.d, (const u64 *)m0b.d, db, words, 1);
-    HIP_TRY(hipGetLastError());
-    int rc = launch_cmux(t, key, index, da, db, batch, nullptr, 0, st);
-    if (rc != FHE_OK) return rc;
-    hipLaunchKernelGGL(fhe::torus_addsub_kernel, grid, dim3(256), 0, st, (const u64 *)m0a.d, (const u64 *)da, moa.d, words, 0);
-    hipLaunchKernelGGL(fhe::torus_addsub_kernel, grid, dim3(256), 0, st, (const u64 *)m0b.d, (const u64 *)db, mob.d, words, 0);
-    HIP_TRY(hipGetLastError());
-    rc = moa.sync_out(st);
+    FHE_TRY(fhe::launch<fhe::torus_addsub_kernel>(grid, 256, 0, st, (const u64 *)m1a.d, (const u64 *)m0a.d, da, words, 1));
+    FHE_TRY(fhe::launch<fhe::torus_addsub_kernel>(grid, 256, 0, st, (const u64 *)m1b.d, (const u64 *)m0b.d, db, words, 1));
+    FHE_TRY(launch_cmux(t, key, index, da, db, batch, nullptr, 0, st));
+    FHE_TRY(fhe::launch<fhe::torus_addsub_kernel>(grid, 256, 0, st, (const u64 *)m0a.d, (const u64 *)da, moa.d, words, 0));
+    FHE_TRY(fhe::launch<fhe::torus_addsub_kernel>(grid, 256, 0, st, (const u64 *)m0b.d, (const u64 *)db, mob.d, words, 0));
+    int rc = moa.sync_out(st);
     return rc != FHE_OK ? rc : mob.sync_out(st);
 }
 
@@ -474,9 +438,8 @@ int fhe_tglwe_rotate(const uint64_t *ct_a, const uint64_t *ct_b, size_t n, int64
     const size_t words = n * batch;
     Mirror ma(ct_a, words, mem, true, st), mb(ct_b, words, mem, true, st), moa(out_a, words, mem, false, st), mob(out_b, words, mem, false, st);
     if (ma.rc | mb.rc | moa.rc | mob.rc) return FHE_ERR_HIP;
-    hipLaunchKernelGGL(fhe::torus_monomial_kernel, dim3(grid_for(words)), dim3(256), 0, st, (const u64 *)ma.d, moa.d, (unsigned)n, batch, k);
-    hipLaunchKernelGGL(fhe::torus_monomial_kernel, dim3(grid_for(words)), dim3(256), 0, st, (const u64 *)mb.d, mob.d, (unsigned)n, batch, k);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::torus_monomial_kernel>(grid_for(words), 256, 0, st, (const u64 *)ma.d, moa.d, (unsigned)n, batch, k));
+    FHE_TRY(fhe::launch<fhe::torus_monomial_kernel>(grid_for(words), 256, 0, st, (const u64 *)mb.d, mob.d, (unsigned)n, batch, k));
     int rc = moa.sync_out(st);
     return rc != FHE_OK ? rc : mob.sync_out(st);
 }
@@ -491,8 +454,7 @@ int fhe_tfhe_mod_switch(const uint64_t *in, uint64_t *out, size_t count, size_t 
     hipStream_t st = (hipStream_t)stream;
     Mirror mi(in, count, mem, true, st), mo(out, count, mem, false, st);
     if (mi.rc | mo.rc) return FHE_ERR_HIP;
-    hipLaunchKernelGGL(fhe::torus_rounding_shr_kernel, dim3(grid_for(count)), dim3(256), 0, st, (const u64 *)mi.d, mo.d, count, bits);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::torus_rounding_shr_kernel>(grid_for(count), 256, 0, st, (const u64 *)mi.d, mo.d, count, bits));
     return mo.sync_out(st);
 }
 
@@ -517,18 +479,18 @@ int fhe_tfhe_blind_rotate(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, cons
     if (brk->d_rowsf) {  // fft64 mode
         TORUS_DISPATCH(brk->log_n, {
             typedef TorusRingF<LN> WR;
-            hipLaunchKernelGGL((fhe::torusf_blind_rotate_kernel<WR, TF_MIN_WAVES>), dim3((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS)), dim3(WR::THREADS),
-                               fhe::TorusF<WR>::LDS_BYTES, st, (const u64 *)mv.d, (const u64 *)ma.d, (const u64 *)mb.d, (unsigned)n_lwe, (unsigned)batch,
-                               (const double2 *)brk->d_rowsf, brk->P, (const double2 *)t->d_twf, moa.d, mob.d);
+            rc = fhe::launch<fhe::torusf_blind_rotate_kernel<WR, TF_MIN_WAVES>>((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS,
+                                                                                fhe::TorusF<WR>::LDS_BYTES, st, (const u64 *)mv.d, (const u64 *)ma.d,
+                                                                                (const u64 *)mb.d, (unsigned)n_lwe, (unsigned)batch, (const double2 *)brk->d_rowsf,
+                                                                                brk->P, (const double2 *)t->d_twf, moa.d, mob.d);
         });
     } else if (brk->d_rowsx3) {  // exact, three key pieces through f64 transforms
         TORUS_DISPATCH(brk->log_n, {
             typedef TorusRingF<LN> WR;
-            const size_t lds = fhe::TorusX3<WR>::lds_bytes(2 * brk->d);
-            if (set_lds((fhe::torusx3_blind_rotate_kernel<WR, TF_MIN_WAVES>), lds) != FHE_OK) return FHE_ERR_HIP;
-            hipLaunchKernelGGL((fhe::torusx3_blind_rotate_kernel<WR, TF_MIN_WAVES>), dim3((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS)), dim3(WR::THREADS), lds, st,
-                               (const u64 *)mv.d, (const u64 *)ma.d, (const u64 *)mb.d, (unsigned)n_lwe, (unsigned)batch, (const double2 *)brk->d_rowsx3, brk->P,
-                               (const double2 *)t->d_twf, moa.d, mob.d);
+            rc = fhe::launch<fhe::torusx3_blind_rotate_kernel<WR, TF_MIN_WAVES>>((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS,
+                                                                                 fhe::TorusX3<WR>::lds_bytes(2 * brk->d), st, (const u64 *)mv.d, (const u64 *)ma.d,
+                                                                                 (const u64 *)mb.d, (unsigned)n_lwe, (unsigned)batch, (const double2 *)brk->d_rowsx3,
+                                                                                 brk->P, (const double2 *)t->d_twf, moa.d, mob.d);
         });
     } else if (brk->d_rows30) {  // three 30-bit primes
         const size_t plane = brk->count * size_t(2 * brk->d) * 2 * n;
@@ -539,39 +501,27 @@ int fhe_tfhe_blind_rotate(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, cons
         if (packed) {
             TORUS_DISPATCH(brk->log_n, {
                 typedef TorusRing30<LN> WR;
-                const size_t lds = WR::torus_pk_lds_bytes(2 * brk->d);
-                if (lds > 64 * 1024) {
-                    static std::atomic<int> done{0};
-                    if (!done.load(std::memory_order_acquire)) {
-                        HIP_TRY(hipFuncSetAttribute((const void *)fhe::torus30_blind_rotate_pk_kernel<WR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                        done.store(1, std::memory_order_release);
-                    }
-                }
-                hipLaunchKernelGGL(fhe::torus30_blind_rotate_pk_kernel<WR>, dim3((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS)), dim3(WR::THREADS), lds, st,
-                                   (const u64 *)mv.d, (const u64 *)ma.d, (const u64 *)mb.d, (unsigned)n_lwe, (unsigned)batch,
-                                   (const unsigned *)brk->d_rows30, plane, brk->P, t->T30, moa.d, mob.d);
+                rc = fhe::launch<fhe::torus30_blind_rotate_pk_kernel<WR>>((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS,
+                                                                          WR::torus_pk_lds_bytes(2 * brk->d), st, (const u64 *)mv.d, (const u64 *)ma.d,
+                                                                          (const u64 *)mb.d, (unsigned)n_lwe, (unsigned)batch, (const unsigned *)brk->d_rows30, plane,
+                                                                          brk->P, t->T30, moa.d, mob.d);
             });
-        } else
-        TORUS_DISPATCH(brk->log_n, {
-            typedef TorusRing30<LN> WR;
-            const size_t lds = WR::TORUS_LDS_BYTES;
-            if (lds > 64 * 1024)
-                HIP_TRY(hipFuncSetAttribute((const void *)fhe::torus30_blind_rotate_kernel<WR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(fhe::torus30_blind_rotate_kernel<WR>, dim3((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS)), dim3(WR::THREADS), lds, st,
-                               (const u64 *)mv.d, (const u64 *)ma.d, (const u64 *)mb.d, (unsigned)n_lwe, (unsigned)batch,
-                               (const unsigned *)brk->d_rows30, plane, brk->P, t->T30, moa.d, mob.d);
-        });
+        } else {
+            TORUS_DISPATCH(brk->log_n, {
+                typedef TorusRing30<LN> WR;
+                rc = fhe::launch<fhe::torus30_blind_rotate_kernel<WR>>((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS, WR::TORUS_LDS_BYTES, st,
+                                                                       (const u64 *)mv.d, (const u64 *)ma.d, (const u64 *)mb.d, (unsigned)n_lwe, (unsigned)batch,
+                                                                       (const unsigned *)brk->d_rows30, plane, brk->P, t->T30, moa.d, mob.d);
+            });
+        }
     } else {
-    TORUS_DISPATCH(brk->log_n, {
-            const size_t lds = TorusRing<LN>::TORUS_LDS_BYTES;
-            if (lds > 64 * 1024)
-                HIP_TRY(hipFuncSetAttribute((const void *)fhe::torus_blind_rotate_kernel<TorusRing<LN>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(fhe::torus_blind_rotate_kernel<TorusRing<LN>>, dim3((unsigned)((batch + TorusRing<LN>::TEAMS - 1) / TorusRing<LN>::TEAMS)),
-                               dim3(TorusRing<LN>::THREADS), lds, st, (const u64 *)mv.d, (const u64 *)ma.d, (const u64 *)mb.d, (unsigned)n_lwe,
-                               (unsigned)batch, (const u64 *)brk->d_rows[0], (const u64 *)brk->d_rows[1], brk->P, t->T, moa.d, mob.d);
+        TORUS_DISPATCH(brk->log_n, {
+            typedef TorusRing<LN> WR;
+            rc = fhe::launch<fhe::torus_blind_rotate_kernel<WR>>((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS, WR::TORUS_LDS_BYTES, st,
+                                                                 (const u64 *)mv.d, (const u64 *)ma.d, (const u64 *)mb.d, (unsigned)n_lwe, (unsigned)batch,
+                                                                 (const u64 *)brk->d_rows[0], (const u64 *)brk->d_rows[1], brk->P, t->T, moa.d, mob.d);
         });
     }
-    if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
     if (rc == FHE_OK) rc = moa.sync_out(st);
     if (rc == FHE_OK) rc = mob.sync_out(st);
     return rc;
@@ -588,9 +538,8 @@ int fhe_tglwe_sample_extract(const uint64_t *ct_a, const uint64_t *ct_b, size_t 
     Mirror ma(ct_a, n * batch, mem, true, st), mb(ct_b, n * batch, mem, true, st), moa(out_a, n * batch, mem, false, st),
         mob(out_b, batch, mem, false, st);
     if (ma.rc | mb.rc | moa.rc | mob.rc) return FHE_ERR_HIP;
-    hipLaunchKernelGGL(fhe::tglwe_sample_extract_kernel, dim3(grid_for(n * batch)), dim3(256), 0, st, (const u64 *)ma.d, (const u64 *)mb.d,
-                       (unsigned)n, batch, (unsigned)index, moa.d, mob.d);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::tglwe_sample_extract_kernel>(grid_for(n * batch), 256, 0, st, (const u64 *)ma.d, (const u64 *)mb.d, (unsigned)n, batch,
+                                                          (unsigned)index, moa.d, mob.d));
     int rc = moa.sync_out(st);
     return rc != FHE_OK ? rc : mob.sync_out(st);
 }
@@ -628,15 +577,16 @@ int fhe_tlwe_key_switch(int log_b, int d, const uint64_t *ksk_a, const uint64_t 
         HIP_TRY(hipMemsetAsync(moa.d, 0, n_out * batch * sizeof(u64), st));
         HIP_TRY(hipMemsetAsync(mob.d, 0, batch * sizeof(u64), st));
         const size_t lds = size_t(P.d) * chunk * WIDE_TILE;
-        hipLaunchKernelGGL(fhe::tlwe_key_switch_split<WIDE_TILE>, dim3(tiles, colb, z), dim3(fhe::KS_THREADS), lds, st, (const u64 *)ma.d, (const u64 *)mb.d,
-                           (unsigned)n_in, (unsigned)n_out, (unsigned)batch, (const u64 *)mka.d, (const u64 *)mkb.d, P, moa.d, mob.d, chunk);
+        rc = fhe::launch<fhe::tlwe_key_switch_split<WIDE_TILE>>(dim3(tiles, colb, z), fhe::KS_THREADS, lds, st, (const u64 *)ma.d, (const u64 *)mb.d,
+                                                                (unsigned)n_in, (unsigned)n_out, (unsigned)batch, (const u64 *)mka.d, (const u64 *)mkb.d, P,
+                                                                moa.d, mob.d, chunk);
     } else if (tile && batch < (size_t(1) << 31)) {
-        if (fhe::launch_key_switch_tiled(fhe::KsTorus{P}, ma.d, mb.d, n_in, n_out, batch, mka.d, mkb.d, moa.d, mob.d, tile, st)) return FHE_ERR_HIP;
+        rc = fhe::launch_key_switch_tiled(fhe::KsTorus{P}, ma.d, mb.d, n_in, n_out, batch, mka.d, mkb.d, moa.d, mob.d, tile, st);
     } else {
-        hipLaunchKernelGGL(fhe::tlwe_key_switch_kernel, dim3(grid_for((n_out + 1) * batch)), dim3(256), 0, st, (const u64 *)ma.d,
-                           (const u64 *)mb.d, (unsigned)n_in, (unsigned)n_out, batch, (const u64 *)mka.d, (const u64 *)mkb.d, P, moa.d, mob.d);
+        rc = fhe::launch<fhe::tlwe_key_switch_kernel>(grid_for((n_out + 1) * batch), 256, 0, st, (const u64 *)ma.d, (const u64 *)mb.d, (unsigned)n_in,
+                                                      (unsigned)n_out, batch, (const u64 *)mka.d, (const u64 *)mkb.d, P, moa.d, mob.d);
     }
-    HIP_TRY(hipGetLastError());
+    if (rc != FHE_OK) return rc;
     rc = moa.sync_out(st);
     return rc != FHE_OK ? rc : mob.sync_out(st);
 }
@@ -682,8 +632,7 @@ namespace {
 inline unsigned long long tdg_blocks(size_t count) { return (count + 3) / 4; }
 inline unsigned long long word_blocks(size_t count) { return (count + 7) / 8; }
 int sample_tdg_dev(double std_dev, const fhe::ChaChaKey &K, unsigned long long first, u64 *out, size_t count, hipStream_t st) {
-    hipLaunchKernelGGL(fhe::sample_tdg_kernel, dim3(grid_for(tdg_blocks(count))), dim3(256), 0, st, out, count, std_dev, K, first);
-    return hipGetLastError() == hipSuccess ? FHE_OK : FHE_ERR_HIP;
+    return fhe::launch<fhe::sample_tdg_kernel>(grid_for(tdg_blocks(count)), 256, 0, st, out, count, std_dev, K, first);
 }
 // scheme/tfhe/src/tglwe.rs:91-103 (k = 1) for `rows` ciphertexts on device buffers: a uniform, e <- tdg, b = a s + e + pt
 // (pt [pt_rows][n] cycled, or null = encryptions of zero); sk [n], binary
@@ -693,17 +642,13 @@ int tglwe_sk_encrypt_dev(const fhe_torus_ctx *t, const u64 *sk, const u64 *pt, s
     StreamWs we(count * sizeof(u64), st);
     if (we.rc != FHE_OK) return we.rc;
     u64 *e = we.as<u64>();
-    hipLaunchKernelGGL(fhe::sample_u64_kernel, dim3(grid_for(word_blocks(count))), dim3(256), 0, st, ct_a, count, K, *cursor);
+    int rc = fhe::launch<fhe::sample_u64_kernel>(grid_for(word_blocks(count)), 256, 0, st, ct_a, count, K, *cursor);
     *cursor += word_blocks(count);
-    int rc = hipGetLastError() == hipSuccess ? FHE_OK : FHE_ERR_HIP;
     if (rc == FHE_OK) rc = sample_tdg_dev(std_dev, K, *cursor, e, count, st);
     *cursor += tdg_blocks(count);
     if (rc == FHE_OK && hipMemcpyAsync(ct_b, ct_a, count * sizeof(u64), hipMemcpyDeviceToDevice, st) != hipSuccess) rc = FHE_ERR_HIP;
     if (rc == FHE_OK) rc = torus_mul_dev(t, ct_b, sk, 1, log_n, rows, st);  // a binary key: |s_i| <= 1, far inside the exact range
-    if (rc == FHE_OK) {
-        hipLaunchKernelGGL(fhe::torus_add3_kernel, dim3(grid_for(count)), dim3(256), 0, st, ct_b, (const u64 *)e, pt, count, pt ? pt_rows * n : 1);
-        if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
-    }
+    if (rc == FHE_OK) rc = fhe::launch<fhe::torus_add3_kernel>(grid_for(count), 256, 0, st, ct_b, (const u64 *)e, pt, count, pt ? pt_rows * n : 1);
     return rc;
 }
 int torus_ring_ok(const fhe_torus_ctx *t, size_t n) {
@@ -737,8 +682,7 @@ int fhe_sample_binary(const fhe_rng *rng, uint64_t stream_id, uint64_t *out, siz
     hipStream_t st = (hipStream_t)stream;
     Mirror mo(out, count, mem, false, st);
     if (mo.rc != FHE_OK) return mo.rc;
-    hipLaunchKernelGGL(fhe::sample_binary_kernel, dim3(grid_for((count + 511) / 512)), dim3(64), 0, st, mo.d, count, fhe::call_key(rng, stream_id, fhe::RNG_SAMPLE_BINARY), 0ull);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::sample_binary_kernel>(grid_for((count + 511) / 512), 64, 0, st, mo.d, count, fhe::call_key(rng, stream_id, fhe::RNG_SAMPLE_BINARY), 0ull));
     return mo.sync_out(st);
 }
 
@@ -756,14 +700,11 @@ int fhe_tlwe_sk_encrypt(const uint64_t *sk, const uint64_t *pt, size_t n, size_t
     StreamWs we(rows * sizeof(u64), st);
     if (we.rc != FHE_OK) return we.rc;
     const fhe::ChaChaKey K = fhe::call_key(rng, stream_id, fhe::RNG_TLWE_ENC);
-    hipLaunchKernelGGL(fhe::sample_u64_kernel, dim3(grid_for(word_blocks(rows * n))), dim3(256), 0, st, ma.d, rows * n, K, 0ull);
-    int rc = hipGetLastError() == hipSuccess ? FHE_OK : FHE_ERR_HIP;
+    int rc = fhe::launch<fhe::sample_u64_kernel>(grid_for(word_blocks(rows * n)), 256, 0, st, ma.d, rows * n, K, 0ull);
     if (rc == FHE_OK) rc = sample_tdg_dev(std_dev, K, word_blocks(rows * n), we.as<u64>(), rows, st);
-    if (rc == FHE_OK) {
-        hipLaunchKernelGGL(fhe::tlwe_encrypt_kernel, dim3(grid_for(rows)), dim3(256), 0, st, (const u64 *)ma.d, (const u64 *)msk.d, (const u64 *)we.as<u64>(),
-                           pt ? (const u64 *)mpt.d : nullptr, mb.d, n, rows, (const u64 *)nullptr, (size_t)1, 0, 0);
-        if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
-    }
+    if (rc == FHE_OK)
+        rc = fhe::launch<fhe::tlwe_encrypt_kernel>(grid_for(rows), 256, 0, st, (const u64 *)ma.d, (const u64 *)msk.d, (const u64 *)we.as<u64>(),
+                                                   pt ? (const u64 *)mpt.d : nullptr, mb.d, n, rows, (const u64 *)nullptr, (size_t)1, 0, 0);
     if (rc == FHE_OK) rc = ma.sync_out(st);
     if (rc == FHE_OK) rc = mb.sync_out(st);
     return rc;
@@ -783,14 +724,11 @@ int fhe_tlwe_ksk_gen(int log_b, int d, const uint64_t *sk0, size_t n0, const uin
     StreamWs we(rows * sizeof(u64), st);
     if (we.rc != FHE_OK) return we.rc;
     const fhe::ChaChaKey K = fhe::call_key(rng, stream_id, fhe::RNG_TLWE_KSK);
-    hipLaunchKernelGGL(fhe::sample_u64_kernel, dim3(grid_for(word_blocks(rows * n0))), dim3(256), 0, st, ma.d, rows * n0, K, 0ull);
-    int rc = hipGetLastError() == hipSuccess ? FHE_OK : FHE_ERR_HIP;
+    int rc = fhe::launch<fhe::sample_u64_kernel>(grid_for(word_blocks(rows * n0)), 256, 0, st, ma.d, rows * n0, K, 0ull);
     if (rc == FHE_OK) rc = sample_tdg_dev(std_dev, K, word_blocks(rows * n0), we.as<u64>(), rows, st);
-    if (rc == FHE_OK) {
-        hipLaunchKernelGGL(fhe::tlwe_encrypt_kernel, dim3(grid_for(rows)), dim3(256), 0, st, (const u64 *)ma.d, (const u64 *)m0.d, (const u64 *)we.as<u64>(),
-                           (const u64 *)nullptr, mb.d, n0, rows, (const u64 *)m1.d, n1, 64 - log_b * d, log_b);
-        if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
-    }
+    if (rc == FHE_OK)
+        rc = fhe::launch<fhe::tlwe_encrypt_kernel>(grid_for(rows), 256, 0, st, (const u64 *)ma.d, (const u64 *)m0.d, (const u64 *)we.as<u64>(),
+                                                   (const u64 *)nullptr, mb.d, n0, rows, (const u64 *)m1.d, n1, 64 - log_b * d, log_b);
     if (rc == FHE_OK) rc = ma.sync_out(st);
     if (rc == FHE_OK) rc = mb.sync_out(st);
     return rc;
@@ -832,11 +770,8 @@ int fhe_tggsw_encrypt(const fhe_torus_ctx *t, int log_b, int d, const uint64_t *
     if (msk.rc | mpt.rc | ma.rc | mb.rc) return FHE_ERR_HIP;
     unsigned long long cursor = 0;
     rc = tglwe_sk_encrypt_dev(t, msk.d, nullptr, 0, ma.d, mb.d, ilog2(n), rows, std_dev, fhe::call_key(rng, stream_id, fhe::RNG_TGGSW_ENC), &cursor, st);
-    if (rc == FHE_OK) {
-        hipLaunchKernelGGL(fhe::tggsw_add_gadget_kernel, dim3(grid_for(count * d * n)), dim3(256), 0, st, ma.d, mb.d, (const u64 *)mpt.d, n, count, d,
-                           64 - log_b * d, log_b);
-        if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
-    }
+    if (rc == FHE_OK)
+        rc = fhe::launch<fhe::tggsw_add_gadget_kernel>(grid_for(count * d * n), 256, 0, st, ma.d, mb.d, (const u64 *)mpt.d, n, count, d, 64 - log_b * d, log_b);
     if (rc == FHE_OK) rc = ma.sync_out(st);
     if (rc == FHE_OK) rc = mb.sync_out(st);
     return rc;

@@ -1,5 +1,5 @@
 // What the torus entry points share (torus_api.hip: k = 1, fused kernels; torusk_api.hip: any rank k, composed kernels): the
-// context and prepared-key structures and two small host helpers.
+// context and prepared-key structures and a small host helper.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -46,10 +46,5 @@ inline int make_tdecomp(int log_b, int d, fhe::TDecomp *P) {
     P->d = d;
     P->rb = rb;
     return FHE_OK;
-}
-
-inline unsigned grid_for(size_t total) {
-    size_t b = (total + 255) / 256;
-    return (unsigned)(b > 16384 ? 16384 : (b ? b : 1));
 }
 }  // namespace

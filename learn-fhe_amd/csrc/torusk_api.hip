@@ -51,27 +51,20 @@ struct DotDst {
 int limb_dot(const fhe_torus_ctx *t, const fhe::TDecomp &P, const DotSrc &S, const u64 *key_eval, unsigned cols, const DotDst &D, size_t batch, int log_n,
              const DotWs &W, hipStream_t st) {
     const unsigned n = 1u << log_n, rows = S.polys * (P.d > 0 ? (unsigned)P.d : 1u);
-    hipLaunchKernelGGL(fhe::torusk_limbs_kernel, dim3(grid_for(size_t(n) * S.polys * batch)), dim3(256), 0, st, S.src, S.sub, W.limbs, n, S.polys, S.src_polys,
-                       batch, P, t->T.p0, t->T.p1, S.rot, S.rot_stride);
-    HIP_TRY(hipGetLastError());
-    int rc = fhe::ntt_fwd_multi(t->d_descs, 2, W.limbs, log_n, 2 * batch * rows, st, 60);
-    if (rc != FHE_OK) return rc;
-    hipLaunchKernelGGL(fhe::torusk_mac_kernel, dim3(grid_for(size_t(2) * n * cols * batch)), dim3(256), 0, st, (const u64 *)W.limbs, key_eval, W.sums, n, rows,
-                       cols, batch, t->T.B0, t->T.B1);
-    HIP_TRY(hipGetLastError());
-    rc = fhe::ntt_inv_multi(t->d_descs, 2, W.sums, log_n, 2 * batch * cols, st, 60);
-    if (rc != FHE_OK) return rc;
-    hipLaunchKernelGGL(fhe::torusk_crt_kernel, dim3(grid_for(size_t(n) * cols * batch)), dim3(256), 0, st, (const u64 *)W.sums, D.out, n, cols, D.out_polys,
-                       D.out_off, batch, t->T, D.same, D.e, D.pt, D.pt_rows);
-    HIP_TRY(hipGetLastError());
-    return FHE_OK;
+    FHE_TRY(fhe::launch<fhe::torusk_limbs_kernel>(grid_for(size_t(n) * S.polys * batch), 256, 0, st, S.src, S.sub, W.limbs, n, S.polys, S.src_polys, batch,
+                                                  P, t->T.p0, t->T.p1, S.rot, S.rot_stride));
+    FHE_TRY(fhe::ntt_fwd_multi(t->d_descs, 2, W.limbs, log_n, 2 * batch * rows, st, 60));
+    FHE_TRY(fhe::launch<fhe::torusk_mac_kernel>(grid_for(size_t(2) * n * cols * batch), 256, 0, st, (const u64 *)W.limbs, key_eval, W.sums, n, rows, cols,
+                                                batch, t->T.B0, t->T.B1));
+    FHE_TRY(fhe::ntt_inv_multi(t->d_descs, 2, W.sums, log_n, 2 * batch * cols, st, 60));
+    return fhe::launch<fhe::torusk_crt_kernel>(grid_for(size_t(n) * cols * batch), 256, 0, st, (const u64 *)W.sums, D.out, n, cols, D.out_polys, D.out_off,
+                                               batch, t->T, D.same, D.e, D.pt, D.pt_rows);
 }
 
 // signed polynomials [polys][n] -> evaluations [polys][2][n] (in `out`)
 int eval_polys(const fhe_torus_ctx *t, const u64 *in, u64 *out, int log_n, size_t polys, hipStream_t st) {
     const size_t n = size_t(1) << log_n;
-    hipLaunchKernelGGL(fhe::torus_residue2_kernel, dim3(grid_for(n * polys)), dim3(256), 0, st, in, out, n, polys, t->T.p0, t->T.p1);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::torus_residue2_kernel>(grid_for(n * polys), 256, 0, st, in, out, n, polys, t->T.p0, t->T.p1));
     return fhe::ntt_fwd_multi(t->d_descs, 2, out, log_n, 2 * polys, st, 60);
 }
 
@@ -92,10 +85,8 @@ int tglwek_encrypt_dev(const fhe_torus_ctx *t, int k, const u64 *sk_eval, const 
     StreamWs ws((rows * n + DotWs::words(rows, k, 1, n)) * sizeof(u64), st);
     if (ws.rc != FHE_OK) return ws.rc;
     u64 *e = ws.as<u64>();
-    hipLaunchKernelGGL(fhe::sample_u64_kernel, dim3(grid_for(word_blocks(words))), dim3(256), 0, st, ct, words, K, 0ull);  // the b slots are overwritten below
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(fhe::sample_tdg_kernel, dim3(grid_for(tdg_blocks(rows * n))), dim3(256), 0, st, e, rows * n, std_dev, K, word_blocks(words));
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::sample_u64_kernel>(grid_for(word_blocks(words)), 256, 0, st, ct, words, K, 0ull));  // the b slots are overwritten below
+    FHE_TRY(fhe::launch<fhe::sample_tdg_kernel>(grid_for(tdg_blocks(rows * n)), 256, 0, st, e, rows * n, std_dev, K, word_blocks(words)));
     fhe::TDecomp plain{};  // d = 0: the mask polynomials themselves
     DotSrc S; S.src = ct; S.polys = (unsigned)k; S.src_polys = (unsigned)k + 1;
     DotDst D; D.out = ct; D.out_polys = (unsigned)k + 1; D.out_off = (unsigned)k; D.e = e; D.pt = pt; D.pt_rows = pt ? pt_rows : 1;
@@ -199,8 +190,7 @@ int fhe_tglwek_rotate(const uint64_t *ct, int k, size_t n, int64_t i, uint64_t *
     const size_t polys = batch * (size_t)(k + 1);
     Mirror mi(ct, polys * n, mem, true, st), mo(out, polys * n, mem, false, st);
     if (mi.rc | mo.rc) return FHE_ERR_HIP;
-    hipLaunchKernelGGL(fhe::torus_monomial_kernel, dim3(grid_for(polys * n)), dim3(256), 0, st, (const u64 *)mi.d, mo.d, (unsigned)n, polys, r);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::torus_monomial_kernel>(grid_for(polys * n), 256, 0, st, (const u64 *)mi.d, mo.d, (unsigned)n, polys, r));
     return mo.sync_out(st);
 }
 
@@ -213,9 +203,8 @@ int fhe_tglwek_sample_extract(const uint64_t *ct, int k, size_t n, size_t index,
     hipStream_t st = (hipStream_t)stream;
     Mirror mi(ct, n * (k + 1) * batch, mem, true, st), moa(out_a, n * k * batch, mem, false, st), mob(out_b, batch, mem, false, st);
     if (mi.rc | moa.rc | mob.rc) return FHE_ERR_HIP;
-    hipLaunchKernelGGL(fhe::tglwek_sample_extract_kernel, dim3(grid_for(n * k * batch)), dim3(256), 0, st, (const u64 *)mi.d, (unsigned)n, (unsigned)k, batch,
-                       (unsigned)index, moa.d, mob.d);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::tglwek_sample_extract_kernel>(grid_for(n * k * batch), 256, 0, st, (const u64 *)mi.d, (unsigned)n, (unsigned)k, batch,
+                                                           (unsigned)index, moa.d, mob.d));
     int rc = moa.sync_out(st);
     return rc != FHE_OK ? rc : mob.sync_out(st);
 }
@@ -237,8 +226,7 @@ int fhe_tfhek_blind_rotate(const fhe_torus_ctx *t, const fhe_tggswk_key *brk, co
     StreamWs ws(DotWs::words(batch, rows, k1, n) * sizeof(u64), st);
     if (ws.rc != FHE_OK) return ws.rc;
     const DotWs W(ws.as<u64>(), batch, rows, n);
-    hipLaunchKernelGGL(fhe::torusk_init_acc_kernel, dim3(grid_for(n * k1 * batch)), dim3(256), 0, st, (const u64 *)mv.d, (const u64 *)mb.d, mo.d, (unsigned)n, k1, batch);
-    HIP_TRY(hipGetLastError());
+    FHE_TRY(fhe::launch<fhe::torusk_init_acc_kernel>(grid_for(n * k1 * batch), 256, 0, st, (const u64 *)mv.d, (const u64 *)mb.d, mo.d, (unsigned)n, k1, batch));
     for (size_t i = 0; i < n_lwe; ++i) {  // acc <- acc + brk_i (.) (acc X^{a_i} - acc)   (tggsw.rs:114-121 with ct0 = acc, ct1 = acc.rotate(a_i))
         DotSrc S; S.src = mo.d; S.rot = ma.d + i; S.rot_stride = n_lwe; S.polys = S.src_polys = k1;
         DotDst D; D.out = mo.d; D.out_polys = k1; D.same = mo.d;
@@ -317,11 +305,9 @@ int fhe_tggswk_encrypt(const fhe_torus_ctx *t, int k, int log_b, int d, const ui
     if (ske.rc != FHE_OK) return ske.rc;
     rc = eval_polys(t, msk.d, ske.as<u64>(), log_n, k, st);
     if (rc == FHE_OK) rc = tglwek_encrypt_dev(t, k, ske.as<u64>(), nullptr, 0, mr.d, log_n, cts, std_dev, fhe::call_key(rng, stream_id, fhe::RNG_TGGSWK_ENC), st);
-    if (rc == FHE_OK) {
-        hipLaunchKernelGGL(fhe::tggswk_add_gadget_kernel, dim3(grid_for(count * (k + 1) * d * n)), dim3(256), 0, st, mr.d, (const u64 *)mpt.d, (unsigned)n,
-                           (unsigned)k + 1, count, d, 64 - log_b * d, log_b);
-        if (hipGetLastError() != hipSuccess) rc = FHE_ERR_HIP;
-    }
+    if (rc == FHE_OK)
+        rc = fhe::launch<fhe::tggswk_add_gadget_kernel>(grid_for(count * (k + 1) * d * n), 256, 0, st, mr.d, (const u64 *)mpt.d, (unsigned)n, (unsigned)k + 1,
+                                                        count, d, 64 - log_b * d, log_b);
     return rc == FHE_OK ? mr.sync_out(st) : rc;
 }
 
