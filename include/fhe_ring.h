@@ -53,7 +53,8 @@ int fhe_trim(void);
  * getenv on a call path.  Names: "NO_EDGE" (key switch at N = 2^15 on whole transforms), "NO_LIMB_MAJOR" (linear dispatch order over
  * several moduli), "NO_W12" (2^12 / 2^13 rings on the generic kernels), "NO_FUSED_MUL" (ring product as forward + multiplying
  * inverse), "SMALL_BATCH" (FHEW: 4 coefficients per lane up to this batch, 8 above; -1 = the library's rule), "NO_F64_EXACT" (TFHE: eligible keys on the three-prime integer path instead of the three-piece f64 one), "NO_PACKED_DIGITS" (TFHE blind
- * rotation: digits decomposed once per prime instead of once per CMUX).  Unknown name:
+ * rotation: digits decomposed once per prime instead of once per CMUX), "FHEW_COMPOSED" (FHEW keys prepared while it is set run the
+ * composed route at n = 128 .. 2048 too, instead of the fused kernels).  Unknown name:
  * FHE_ERR_INVALID. */
 int fhe_set_option(const char *name, long value);
 
@@ -115,10 +116,13 @@ int fhe_monomial_mul(uint64_t q, int64_t k, const uint64_t *in, uint64_t *out, s
 /* ---- prepared gadget keys (device resident, evaluation domain) ---------------------------------------- */
 typedef struct fhe_key fhe_key;
 /* `count` RGSW ciphertexts (scheme/fhew/src/rgsw.rs:37-47, 84-105): rows_a / rows_b = the a / b polynomials of the
- * 2d RLWE rows of each, [count][2d][n], coefficient domain.  n = 128 .. 2048. */
+ * 2d RLWE rows of each, [count][2d][n], coefficient domain.  n = any power of two 1 .. 2^ctx's table size (2^17 at most; FHE_ERR_NO_ROOT
+ * above the modulus's two-adicity): 128 .. 2048 run the fused kernels, every other n (and every n of a key prepared while the lab
+ * switch "FHEW_COMPOSED" is set) whole-batch launches -- digits, transforms, multiply-accumulate -- over chunks of the batch.  The
+ * gadget products, key switches, automorphisms and blind rotations below take the sizes of their keys. */
 int fhe_rgsw_prepare(const fhe_ctx *ctx, int log_b, int d, const uint64_t *rows_a, const uint64_t *rows_b, size_t n,
                      size_t count, fhe_mem mem, fhe_key **out);
-/* `count` RLWE key-switching / automorphism keys (scheme/fhew/src/rlwe.rs:43-66, 109-132): [count][d][n]. */
+/* `count` RLWE key-switching / automorphism keys (scheme/fhew/src/rlwe.rs:43-66, 109-132): [count][d][n], n as above. */
 int fhe_ksk_prepare(const fhe_ctx *ctx, int log_b, int d, const uint64_t *rows_a, const uint64_t *rows_b, size_t n,
                     size_t count, fhe_mem mem, fhe_key **out);
 void fhe_key_destroy(fhe_key *key);
@@ -145,7 +149,9 @@ int fhe_rlwe_automorphism(const fhe_ctx *ctx, const fhe_key *ak, size_t index, i
 typedef struct fhe_bootstrap_key fhe_bootstrap_key;
 /* scheme/fhew/src/bootstrapping.rs:93-113 `BootstrappingKey{brk, ak}` (the LWE ksk belongs to the "next" row):
  * brk = n_lwe prepared RGSW ciphertexts, ak = w+1 prepared automorphism keys with exponents ak_t[0..w]
- * (= [-g, g, g^2, .., g^w] mod 2n, bootstrapping.rs:86-89).  The handles must outlive the bootstrap key. */
+ * (= [-g, g, g^2, .., g^w] mod 2n, bootstrapping.rs:86-89).  The handles must outlive the bootstrap key.  n >= 2: at n = 1 the
+ * reference panics (an empty i_minus, bootstrapping.rs:191, 215), here FHE_ERR_INVALID; so are brk and ak prepared for different
+ * routes (one with the lab switch "FHEW_COMPOSED", one without, at n = 128 .. 2048). */
 int fhe_bootstrap_key_create(const fhe_ctx *ctx, const fhe_key *brk, const fhe_key *ak, const int64_t *ak_t, int w,
                              fhe_bootstrap_key **out);
 void fhe_bootstrap_key_destroy(fhe_bootstrap_key *bk);

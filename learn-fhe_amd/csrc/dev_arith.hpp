@@ -66,14 +66,18 @@ inline Barrett make_barrett(u64 q) {
     return B;
 }
 
-// a, b in [0, q)  ->  a*b mod q in [0, q)
-__device__ __forceinline__ u64 mulmod_barrett(u64 a, u64 b, const Barrett &B) {
+// a, b in [0, q)  ->  a*b mod q in [0, 3q) (the quotient estimate before its corrections)
+__device__ __forceinline__ u64 mulmod_barrett_lazy(u64 a, u64 b, const Barrett &B) {
     u64 lo = a * b, hi = __umul64hi(a, b);
     u64 A = (hi << (64 - B.sh1)) | (lo >> B.sh1);  // floor(P / 2^(n-1)) < 2^(n+1)
     u64 plo = A * B.mu, phi = __umul64hi(A, B.mu);
     u64 qhat = (phi << (64 - B.sh2)) | (plo >> B.sh2);  // true quotient - {0,1,2}
-    u64 r = lo - qhat * B.q;                            // in [0, 3q)
-    return csub(csub(r, B.q), B.q);
+    return lo - qhat * B.q;                             // in [0, 3q)
+}
+
+// a, b in [0, q)  ->  a*b mod q in [0, q)
+__device__ __forceinline__ u64 mulmod_barrett(u64 a, u64 b, const Barrett &B) {
+    return csub(csub(mulmod_barrett_lazy(a, b, B), B.q), B.q);
 }
 
 }  // namespace fhe

@@ -8,12 +8,14 @@
 
 #include "api_common.hpp"
 #include "ctx.hpp"
+#include "fhew_composed_kernels.hpp"
 #include "fhew_kernels.hpp"
 #include "lwe_kernels.hpp"
 
 // defined in ring_api.hip
 namespace fhe {
 int ntt_fwd_device(const fhe_ctx *c, u64 *a, int log_n, size_t batch, hipStream_t st);
+int ntt_inv_device(const fhe_ctx *c, u64 *a, int log_n, size_t batch, hipStream_t st);
 }
 
 struct fhe_key {
@@ -22,7 +24,10 @@ struct fhe_key {
     int log_b = 0, d = 0;
     int rows_per_ct = 0;  // 2d (RGSW) or d (key-switching key)
     size_t count = 0;
-    u64 *d_rows = nullptr;  // [count][rows_per_ct][2][N], evaluation domain, key_perm layout
+    bool composed = false;  // route: the composed launches (fhew_composed_kernels.hpp) or the fused kernels (N = 128 .. 2048)
+    // fused: [count][rows_per_ct][2][N], evaluation domain, key_perm layout
+    // composed: [2][count][rows_per_ct][N] (every a row, then every b row), evaluation domain in ntt_fwd_device's order
+    u64 *d_rows = nullptr;
     u64 *d_rows_small = nullptr;  // N >= 1024: the same rows in the layout of the small-batch kernels (4 coefficients per lane)
     fhe::DecompParams P{};
 };
@@ -97,7 +102,8 @@ int key_prepare(const fhe_ctx *ctx, int log_b, int d, int rows_per_ct, const uin
     if (ctx->device < 0) return FHE_ERR_NO_DEVICE;
     const int log_n = ilog2(n);
     if (log_n > ctx->s - 1) return FHE_ERR_NO_ROOT;
-    if (log_n < 7 || log_n > 11) return FHE_ERR_UNSUPPORTED;
+    if (log_n > ctx->log_cap) return FHE_ERR_UNSUPPORTED;
+    const bool composed = log_n < 7 || log_n > 11 || fhe::opt(fhe::OPT_FHEW_COMPOSED) != 0;  // lab switch (api_common.hpp)
     fhe::DecompParams P;
     int rc = make_decomp(ctx->q, log_b, d, &P);
     if (rc != FHE_OK) return rc;
@@ -108,14 +114,23 @@ int key_prepare(const fhe_ctx *ctx, int log_b, int d, int rows_per_ct, const uin
     u64 *ta = nullptr, *tb = nullptr, *dst = nullptr;
     HIP_TRY(hipMalloc((void **)&ta, 2 * words * sizeof(u64)));
     tb = ta + words;
-    hipError_t e = hipMalloc((void **)&dst, 2 * words * sizeof(u64));
+    hipError_t e = composed ? hipSuccess : hipMalloc((void **)&dst, 2 * words * sizeof(u64));
     hipMemcpyKind kind = mem == FHE_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     if (e == hipSuccess) e = hipMemcpyAsync(ta, rows_a, words * sizeof(u64), kind, st);
     if (e == hipSuccess) e = hipMemcpyAsync(tb, rows_b, words * sizeof(u64), kind, st);
     rc = e == hipSuccess ? FHE_OK : FHE_ERR_HIP;
     if (e != hipSuccess) g_last_hip = (int)e;
     // rows -> evaluation domain once (what Rgsw::internal_product does per call, rgsw.rs:136-138)
-    if (rc == FHE_OK) rc = fhe::ntt_fwd_device(ctx, ta, log_n, 2 * rows, st);
+    if (rc == FHE_OK && log_n > 0) rc = fhe::ntt_fwd_device(ctx, ta, log_n, 2 * rows, st);
+    if (composed) {  // the transformed rows are the key as they stand
+        if (hipStreamSynchronize(st) != hipSuccess && rc == FHE_OK) rc = FHE_ERR_HIP;
+        fhe_key *k = rc == FHE_OK ? new (std::nothrow) fhe_key() : nullptr;
+        if (!k) { (void)hipFree(ta); return rc == FHE_OK ? FHE_ERR_INVALID : rc; }
+        k->ctx = ctx; k->log_n = log_n; k->log_b = log_b; k->d = d; k->rows_per_ct = rows_per_ct; k->count = count;
+        k->composed = true; k->d_rows = ta; k->P = P;
+        *out = k;
+        return FHE_OK;
+    }
     if (rc == FHE_OK) {
         FHEW_DISPATCH(log_n, rc = fhe::launch<fhe::key_permute_kernel<fhe::WaveRing<LN>>>(fhew_grid(words), 256, 0, st, ta, tb, dst, rows,
                                                                                            fhew_pm(ctx, log_n)));
@@ -164,6 +179,47 @@ fhe::FhewKey key_view(const fhe_key *k, bool small = false) {
     v.rows_per_ct = k->rows_per_ct;
     v.P = k->P;
     return v;
+}
+
+// composed route: a chunk of ciphertexts at a time under a fixed workspace, whatever the batch
+constexpr size_t COMPOSED_WS_BYTES = size_t(256) << 20;
+
+fhe::ComposedKey composed_view(const fhe_key *k) {
+    fhe::ComposedKey v;
+    v.rows = k->d_rows;
+    v.b_off = k->count * k->rows_per_ct * (size_t(1) << k->log_n);
+    v.rows_per_ct = k->rows_per_ct;
+    v.P = k->P;
+    return v;
+}
+
+// `steps` composed gadget products of every ciphertext of ct_a, ct_b [batch][N] in place (O.step = 0 .. steps - 1; with an op list a
+// ciphertext whose list has ended is left as it is).  rows: digit rows per ciphertext, the most any op of the call needs.
+// Per chunk and step: digits -> forward transforms -> multiply-accumulate -> inverse transforms -> epilogue.
+int composed_run(const fhe_ctx *ctx, fhe::ComposedOps O, int log_n, unsigned rows, size_t steps, u64 *ct_a, u64 *ct_b, size_t batch,
+                 hipStream_t st) {
+    const size_t n = size_t(1) << log_n, per_ct = (rows + 3) * n;  // digits | acc (a, b) | kept b
+    size_t chunk = COMPOSED_WS_BYTES / (per_ct * sizeof(u64));
+    if (chunk < 1) chunk = 1;
+    if (chunk > batch) chunk = batch;
+    StreamWs wsp(chunk * per_ct * sizeof(u64), st);
+    if (wsp.rc != FHE_OK) return wsp.rc;
+    u64 *dig = wsp.as<u64>(), *acc = dig + chunk * rows * n, *kept = acc + chunk * 2 * n;
+    for (size_t c0 = 0; c0 < batch; c0 += chunk) {
+        const size_t cnt = batch - c0 < chunk ? batch - c0 : chunk;
+        u64 *a = ct_a + c0 * n, *b = ct_b + c0 * n;
+        O.ct0 = c0;
+        for (size_t s = 0; s < steps; ++s) {
+            O.step = (unsigned)s;
+            FHE_TRY(fhe::launch<fhe::composed_digits_kernel>(fhew_grid(n * cnt), 256, 0, st, a, b, dig, kept, (unsigned)n, rows, cnt, O));
+            if (log_n > 0) FHE_TRY(fhe::ntt_fwd_device(ctx, dig, log_n, cnt * rows, st));
+            if (log_n > 0) FHE_TRY(fhe::launch<fhe::composed_mac_kernel<2>>(fhew_grid(n / 2 * cnt), 256, 0, st, dig, acc, (unsigned)n, rows, cnt, O, ctx->barrett));
+            else FHE_TRY(fhe::launch<fhe::composed_mac_kernel<1>>(fhew_grid(cnt), 256, 0, st, dig, acc, (unsigned)n, rows, cnt, O, ctx->barrett));
+            if (log_n > 0) FHE_TRY(fhe::ntt_inv_device(ctx, acc, log_n, 2 * cnt, st));
+            FHE_TRY(fhe::launch<fhe::composed_epilogue_kernel>(fhew_grid(n * cnt), 256, 0, st, acc, kept, a, b, (unsigned)n, cnt, O, (u64)ctx->q));
+        }
+    }
+    return FHE_OK;
 }
 
 int check_ct_call(const fhe_ctx *ctx, const fhe_key *key, size_t index, const void *a, const void *b, size_t batch) {
@@ -265,6 +321,16 @@ static int gadget_entry(const fhe_ctx *ctx, const fhe_key *key, size_t index, bo
     }
     Mirror ma(ct_a, n * batch, mem, true, st), mb(ct_b, n * batch, mem, true, st);
     if (ma.rc != FHE_OK || mb.rc != FHE_OK) return FHE_ERR_HIP;
+    if (key->composed) {
+        fhe::ComposedOps O{};
+        O.ep = O.ks = composed_view(key);
+        O.t_fix = tt;
+        O.fixed = (unsigned)index | (both ? 0u : fhe::BR_OP_AK);
+        rc = composed_run(ctx, O, key->log_n, (unsigned)key->rows_per_ct, 1, ma.d, mb.d, batch, st);
+        if (rc != FHE_OK) return rc;
+        rc = ma.sync_out(st);
+        return rc != FHE_OK ? rc : mb.sync_out(st);
+    }
     const bool small = small_shape(key->log_n, batch);
 #define GP_LAUNCH_W(AR, WR)                                                                                                    \
     rc = fhe::launch<fhe::gadget_product_kernel<AR, WR>>((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS, WR::LDS_BYTES, st, \
@@ -423,6 +489,8 @@ int fhe_bootstrap_key_create(const fhe_ctx *ctx, const fhe_key *brk, const fhe_k
     if (brk->ctx != ctx || ak->ctx != ctx) return FHE_ERR_MODULUS;
     if (brk->log_n != ak->log_n || ak->count != (size_t)w + 1 || brk->rows_per_ct != 2 * brk->d || ak->rows_per_ct != ak->d)
         return FHE_ERR_INVALID;
+    if (brk->composed != ak->composed) return FHE_ERR_INVALID;  // one route for both halves of the key
+    if (brk->log_n == 0) return FHE_ERR_INVALID;  // N = 1 has no i_minus / i_plus buckets (the reference panics: bootstrapping.rs:191, 215)
     if (ctx->device < 0) return FHE_ERR_NO_DEVICE;
     const unsigned n = 1u << brk->log_n, q2 = 2 * n;
     std::vector<unsigned> t(w + 1), dlog(q2, 0xffffffffu);
@@ -508,49 +576,72 @@ int fhe_blind_rotate(const fhe_bootstrap_key *bk, const uint64_t *lwe_a, const u
     rc = fhe::launch<fhe::blind_rotate_schedule_kernel>((unsigned)batch, 64, 3 * n_lwe * sizeof(unsigned), st, ma.d, (unsigned)n_lwe,
                                                          (unsigned)batch, (unsigned)n, (unsigned)bk->w, bk->d_dlog, d_ops, d_nops, max_ops, d_err);
     if (rc != FHE_OK) return fail(rc);
-    fhe::BlindRotateParams BR;
-    const bool small = small_shape(log_n, batch);
-    BR.brk = key_view(bk->brk, small);
-    BR.ak = key_view(bk->ak, small);
-    BR.ak_t = bk->d_ak_t;
-    BR.ops = d_ops;
-    BR.nops = d_nops;
-    BR.max_ops = max_ops;
-    BR.lwe_b = mb.d;
-    BR.f = mf.d;
-    BR.f_stride = f_stride;
+    if (bk->brk->composed) {
+        // acc for the whole batch, then the walk as a host loop of S steps: S bounds every ciphertext's op count from (n_lwe, N, w)
+        // alone (no device read): at most n_lwe external products, per half at most min(n_lwe, N/2 - 1) + floor((N/2 - 1) / w) + 1
+        // automorphisms (one per run between occupied levels, plus the whole runs of w), and the one between the halves
+        rc = fhe::launch<fhe::composed_br_init_kernel>(fhew_grid(n * batch), 256, 0, st, mf.d, f_stride, mb.d, moa.d, mob.d, (unsigned)n, batch,
+                                                       (u64)ctx->q);
+        if (rc != FHE_OK) return fail(rc);
+        const size_t half = n / 2, lv = half - 1;
+        const size_t per_half = (n_lwe < lv ? n_lwe : lv) + lv / (size_t)bk->w + 1;
+        size_t steps = n_lwe + 2 * per_half + 1;
+        if (steps > max_ops) steps = max_ops;
+        fhe::ComposedOps O{};
+        O.ep = composed_view(bk->brk);
+        O.ks = composed_view(bk->ak);
+        O.ak_t = bk->d_ak_t;
+        O.ops = d_ops;
+        O.nops = d_nops;
+        O.max_ops = max_ops;
+        const unsigned rows = (unsigned)(bk->brk->rows_per_ct > bk->ak->rows_per_ct ? bk->brk->rows_per_ct : bk->ak->rows_per_ct);
+        rc = composed_run(ctx, O, log_n, rows, steps, moa.d, mob.d, batch, st);
+        if (rc != FHE_OK) return fail(rc);
+    } else {
+        fhe::BlindRotateParams BR;
+        const bool small = small_shape(log_n, batch);
+        BR.brk = key_view(bk->brk, small);
+        BR.ak = key_view(bk->ak, small);
+        BR.ak_t = bk->d_ak_t;
+        BR.ops = d_ops;
+        BR.nops = d_nops;
+        BR.max_ops = max_ops;
+        BR.lwe_b = mb.d;
+        BR.f = mf.d;
+        BR.f_stride = f_stride;
 #define BR_LAUNCH_W(AR, WR)                                                                                                  \
-    rc = fhe::launch<fhe::blind_rotate_kernel<AR, WR>>((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS, WR::LDS_BYTES, st, \
-                                                       BR, moa.d, mob.d, (unsigned)batch, ring_consts(ctx, 0));
+        rc = fhe::launch<fhe::blind_rotate_kernel<AR, WR>>((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS, WR::LDS_BYTES, st, \
+                                                           BR, moa.d, mob.d, (unsigned)batch, ring_consts(ctx, 0));
 #define BR_CASE(AR, LN) case LN: { typedef fhe::WaveRing<LN> WD; BR_LAUNCH_W(AR, WD) break; }
 #define BR_CASE_BIG(AR, LN)                                                                  \
-    case LN: {                                                                               \
-        if (small) { typedef fhe::WaveRing<LN, 2> WS; BR_LAUNCH_W(AR, WS) }                  \
-        else { typedef fhe::WaveRing<LN> WD; BR_LAUNCH_W(AR, WD) }                           \
-        break;                                                                               \
-    }
-    const int pmv = fhew_pm(ctx, log_n);
-    if (pmv == 54) {
-        switch (log_n) {
-            BR_CASE(FHEW_POLICY54, 9) BR_CASE_BIG(FHEW_POLICY54, 10) BR_CASE_BIG(FHEW_POLICY54, 11)
-            default: return fail(FHE_ERR_UNSUPPORTED);
+        case LN: {                                                                               \
+            if (small) { typedef fhe::WaveRing<LN, 2> WS; BR_LAUNCH_W(AR, WS) }                  \
+            else { typedef fhe::WaveRing<LN> WD; BR_LAUNCH_W(AR, WD) }                           \
+            break;                                                                               \
         }
-    } else if (pmv == 55) {
-        switch (log_n) {
-            BR_CASE(FHEW_POLICY55, 9) BR_CASE_BIG(FHEW_POLICY55, 10) BR_CASE_BIG(FHEW_POLICY55, 11)
-            default: return fail(FHE_ERR_UNSUPPORTED);
+        const int pmv = fhew_pm(ctx, log_n);
+        if (pmv == 54) {
+            switch (log_n) {
+                BR_CASE(FHEW_POLICY54, 9) BR_CASE_BIG(FHEW_POLICY54, 10) BR_CASE_BIG(FHEW_POLICY54, 11)
+                default: return fail(FHE_ERR_UNSUPPORTED);
+            }
+        } else if (pmv == 55) {
+            switch (log_n) {
+                BR_CASE(FHEW_POLICY55, 9) BR_CASE_BIG(FHEW_POLICY55, 10) BR_CASE_BIG(FHEW_POLICY55, 11)
+                default: return fail(FHE_ERR_UNSUPPORTED);
+            }
+        } else {
+            switch (log_n) {
+                BR_CASE(fhe::ArithShoup, 7) BR_CASE(fhe::ArithShoup, 8) BR_CASE(fhe::ArithShoup, 9) BR_CASE_BIG(fhe::ArithShoup, 10)
+                BR_CASE_BIG(fhe::ArithShoup, 11)
+                default: return fail(FHE_ERR_UNSUPPORTED);
+            }
         }
-    } else {
-        switch (log_n) {
-            BR_CASE(fhe::ArithShoup, 7) BR_CASE(fhe::ArithShoup, 8) BR_CASE(fhe::ArithShoup, 9) BR_CASE_BIG(fhe::ArithShoup, 10)
-            BR_CASE_BIG(fhe::ArithShoup, 11)
-            default: return fail(FHE_ERR_UNSUPPORTED);
-        }
-    }
 #undef BR_CASE_BIG
 #undef BR_LAUNCH_W
 #undef BR_CASE
-    if (rc != FHE_OK) return fail(rc);
+        if (rc != FHE_OK) return fail(rc);
+    }
     if (async) return FHE_OK;  // (the workspace is stream ordered: released after the kernels above)
     int h_err = 0;
     if (hipMemcpyAsync(&h_err, d_err, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) return fail(FHE_ERR_HIP);

@@ -48,15 +48,22 @@ FHE_HEADER_KERNEL void decompose_kernel(const u64 *__restrict__ in, u64 *__restr
 }
 
 // ---- automorphism X -> X^t (util/src/avec.rs:34-50) and monomial multiply (util/src/ring.rs:299-313) ----
+// the index map: X^i -> +-X^(i t mod N), neg when i t mod 2N >= N
+__device__ __forceinline__ unsigned auto_target(unsigned i, unsigned t, unsigned n, bool &neg) {
+    const unsigned it = unsigned((u64(i) * t) & (2 * n - 1));
+    neg = it >= n;
+    return neg ? it - n : it;
+}
+
 FHE_HEADER_KERNEL void automorphism_kernel(const u64 *__restrict__ in, u64 *__restrict__ out, unsigned n, size_t batch, unsigned t, u64 q) {
     const size_t total = size_t(n) * batch;
     for (size_t idx = blockIdx.x * size_t(blockDim.x) + threadIdx.x; idx < total; idx += size_t(gridDim.x) * blockDim.x) {
         const size_t p = idx / n;
         const unsigned i = unsigned(idx - p * n);
-        const unsigned it = unsigned((u64(i) * t) & (2 * n - 1));
+        bool neg;
+        const unsigned it = auto_target(i, t, n, neg);
         const u64 v = in[idx];
-        if (it < n) out[p * n + it] = v;
-        else out[p * n + it - n] = v ? q - v : 0;
+        out[p * n + it] = neg ? (v ? q - v : 0) : v;
     }
 }
 
