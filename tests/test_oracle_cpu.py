@@ -283,3 +283,24 @@ def test_ckks_mul_rotate_c_vs_python():
         eb, ea = cref.ckks_rotate(qs, ps, kb, ka, t, cts[0], cts[1])
         pb, pa = P.ckks_rotate(qs, ps, ints(kb), ints(ka), t, ints(cts[0]), ints(cts[1]))
         assert ints(eb) == pb and ints(ea) == pa, t
+
+
+def test_edge_prime_table():
+    """tests/test_modulus_edges_gpu.py's edge primes: prime, two-adic enough for their ring, tagged with the route ctx_build_host
+    picks (pseudo-Mersenne iff q = 2^B - c, 34 <= B <= 60, c <= 2^(B-33)), and each the extreme of its side of the bound: no prime of
+    the same two-adicity step between the largest eligible c and the bound, nor between the bound and the smallest c above it"""
+    from test_modulus_edges_gpu import BARRETT_WORST, EDGE_PRIMES, PM_BOUNDARY, TOP_62, pm_eligible, two_adicity
+    assert len(EDGE_PRIMES) == 2 * len(PM_BOUNDARY) + len(TOP_62) + len(BARRETT_WORST) + 2
+    for q, log_n, route in EDGE_PRIMES:
+        assert R.is_prime(q) and two_adicity(q) >= log_n + 1, (q, log_n)
+        assert pm_eligible(q) == (route == "pm"), (q, route)
+    for b, log_n, c_pm, c_sh in PM_BOUNDARY:
+        step, bound = 1 << (log_n + 1), 1 << (b - 33)
+        assert c_pm <= bound < c_sh and (c_sh - c_pm) % step == 0
+        assert not any(R.is_prime((1 << b) - c) for c in range(c_pm + step, c_sh, step)), (b, log_n)
+    for log_n, c in TOP_62:
+        assert R.two_adic_primes(62, log_n + 1, 1) == [(1 << 62) - c]
+    for b, log_n, c in BARRETT_WORST:  # 2^(2B) mod q within 0.3 % of q: floor(2^(2B) / q) drops almost a whole unit
+        q = (1 << b) - c
+        assert q.bit_length() == b and (1 << (2 * b)) % q > q - q // 300, b
+    assert not pm_eligible(1 << 61 | 1) and not pm_eligible((1 << 33) - 1) and pm_eligible((1 << 34) - 1)
