@@ -85,7 +85,13 @@ int fhe_ntt_fwd(const fhe_ctx *ctx, uint64_t *a, size_t n, size_t batch, fhe_mem
 /* util/src/ring/fft/zq.rs:32-36 `nega_cyclic_intt_in_place` (= ring.rs:180-184 `to_coefficient`). */
 int fhe_ntt_inv(const fhe_ctx *ctx, uint64_t *a, size_t n, size_t batch, fhe_mem mem, void *stream);
 /* util/src/ring/fft/zq.rs:14-19 `nega_cyclic_ntt_mul_assign` (= ring.rs:256-264 `Rq *= &Rq`):
- * a[k] <- a[k] * b[k] in Z_q[X]/(X^n+1), coefficient domain in and out. */
+ * a[k] <- a[k] * b[k] in Z_q[X]/(X^n+1), coefficient domain in and out.
+ * Device memory, n = 2^12 .. 2^15 (and the two 2^14 halves a 2^15 RNS transform is split into): the transforms read and write
+ * every polynomial 16 bytes per lane, so `a` and `b` must be 16-byte aligned (any allocation and any whole-polynomial offset
+ * into one is); a pointer that is not is rejected with FHE_ERR_INVALID before anything is written.  That holds for fhe_ntt_fwd /
+ * fhe_ntt_inv / fhe_ntt_mul and for every entry point that hands a FHE_MEM_DEVICE operand to these transforms (in place, or out
+ * of place as `b` here and the fhe_rns_* / fhe_ckks_* products and key preparation).  Rings above 2^15 read their operands
+ * 8 bytes per lane in a first pass of their own and carry no such requirement. */
 int fhe_ntt_mul(const fhe_ctx *ctx, uint64_t *a, const uint64_t *b, size_t n, size_t batch, fhe_mem mem,
                 void *stream);
 /* util/src/ring.rs:328-358 `Rq` + / - / unary - and 359-366 scalar `*= Zq` (zq.rs:156-196), element-wise over `len`

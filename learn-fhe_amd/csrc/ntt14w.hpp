@@ -8,9 +8,10 @@
 // (the wave's own LDS region, ordered by its own lgkmcnt), so the eight waves of a workgroup drift apart and one wave's
 // exchange latency hides behind another wave's butterflies.  4 barriers per transform instead of 12.
 //
-//   wave w0 = i[8:6] , lane = i[5:0]                                            (i = coefficient index, 14 bits)
-//   pass 0: regs {13,12,11 | 10,9}   layers 0..2    HBM side: 8-byte coalesced accesses; twiddles wave-uniform (SGPRs)
-//   ---- X01: across waves, two rounds split by bit 10, lanes keep i[5:0] ------------------------------------------------
+//   wave w0 = i[9:7] , lane = i[6:1]                                            (i = coefficient index, 14 bits)
+//   pass 0: regs {13,12,11 | 10,0}   layers 0..2    a thread owns the pairs (i, i + 1): HBM side 16 bytes per lane, 1 KiB
+//                                                   contiguous per wave-instruction; twiddles wave-uniform (SGPRs)
+//   ---- X01: across waves, two rounds split by bit 10; pass-0 side 16 bytes per lane, pass-1 side lanes keep i[5:0] ----------
 //   wave w = i[13:11] from here on
 //   pass 1: regs {10,9,8,7 | 6}      lane = i[5:0]                  layers 3..6     twiddles wave-uniform (SGPRs)
 //   ---- X12: wave-private, split by bit 6 -----------------------------------------------------------------------------
@@ -22,7 +23,10 @@
 // The passive register bits (after the bar) sit BELOW the bits a pass processes in passes 0..2, so its replicas share their
 // twiddles.  Forward = passes 0 -> 3 (Cooley-Tukey, util/src/ring/fft.rs:40-54), inverse = 3 -> 0 (Gentleman-Sande, 59-77, n^-1
 // folded into the last layer).  Natural-order coefficients <-> bit-reversed evaluations, twiddle tw[2^layer + block], exactly
-// as the reference.  LDS layouts are conflict free for ds_write_b64 / ds_read_b64 (tools/lds_bank_sim.py).
+// as the reference.  LDS layouts are conflict free for ds_write_b64 / ds_read_b64, the pass-0 side of X01 for ds_write_b128 /
+// ds_read_b128 (tools/lds_bank_sim.py).  Pass 0's twiddles depend only on the bits ABOVE a butterfly's bit, so which low bits
+// are passive is free: 2^12 / 2^13 (R0 = 1 / 2) replace their lowest passive bit by i0 the same way, 2^15 (R0 = 4: one passive
+// bit, 1024 threads = i[9:0]) keeps one coefficient per access.
 #pragma once
 #include <type_traits>
 #include "ntt_kernels.hpp"
@@ -61,6 +65,16 @@ __device__ __forceinline__ void wave_sync() {
 #define W14_PRIO_DOWN()
 #endif
 
+// The pass-0 side deals a thread coefficient PAIRS (i, i + 1): 16-byte HBM and LDS accesses (R0 <= 3; see the table above).
+// Lab switch: a policy that declares W14_OLD_DEAL gets the earlier dealing (thread = i[5 + R0:0], 8-byte accesses) for its own
+// instantiations, so tools/ntt_lab2.hip runs both interleaved in one process.
+template <class A, class = void> struct w14_old_deal { static constexpr bool value = false; };
+template <class A> struct w14_old_deal<A, decltype((void)A::W14_OLD_DEAL)> { static constexpr bool value = true; };
+template <class A, int R0>
+__device__ __host__ constexpr bool w14_pairs() {
+    return R0 <= 3 && !w14_old_deal<A>::value;
+}
+
 #ifdef NTT14_STAMPS
 __device__ unsigned long long g_stamps[4096][16];
 #define STAMP_DECL unsigned long long stamps_[12]
@@ -92,13 +106,14 @@ __device__ unsigned long long g_stamps[4096][16];
 #endif
 
 // ---- register naming -----------------------------------------------------------------------------------------------
-//   pass 0: x[(s2 << 3) | n3]    n3 = i[13:11], s2 = i[10:9]
+//   pass 0: x[(s2 << 3) | n3]    n3 = i[13:11], s2 = (i10, i0)
 //   pass 1: x[(s << 4) | n4]     n4 = i[10:7],  s = i[6]
 //   pass 2: x[(s << 4) | n4]     n4 = i[6:3],   s = i[2]
 //   pass 3: x[(ab << 3) | n3]    n3 = i[2:0],   ab = i[10:9]
 
 // pass 0 -> pass 1 (across waves; round h moves the coefficients with i[10] = h).  Pass-0 register (pass, n): n = the top R0 index
-// bits, pass = the 5 - R0 bits below them (i[10] first; R0 = 3: (i10, i9), R0 = 4: i10); thread t = the remaining low bits.
+// bits, pass = the 5 - R0 passive bits, i[10] first.  PAIRS: the last passive bit is i0 (R0 = 3: (i10, i0)), thread t = i[6 + R0:1];
+// otherwise they are the bits below bit 11 (R0 = 3: (i10, i9), R0 = 4: i10) and thread t = the remaining low bits.
 // Slot of a coefficient in the half image (bit 10 removed): (n << 10) | i[9:0]; lanes keep i[5:0]: conflict free unpadded.
 #ifdef W14_LAB_NO_BARRIER  // developer lab only: what do the workgroup barriers of the cross-wave exchange cost? (results wrong)
 #define W14_SYNC() wave_sync()
@@ -106,18 +121,28 @@ __device__ unsigned long long g_stamps[4096][16];
 #define W14_SYNC() __syncthreads()
 #endif
 
-template <int R0>
+template <int R0, bool PAIRS>
 __device__ __forceinline__ void xchg_01(u64 (&x)[32], int t, int w, u64 *lds) {
     constexpr int PB = 5 - R0, NLOW = 1 << (PB - 1);  // register bits below bit 10 (i9 for R0 = 3, none for R0 = 4)
-    u64 *wp = lds + t, *rp = lds + (w << 10) + (t & 63);  // constant offsets from here on: immediates of the ds instructions
+    u64 *wp = lds + (PAIRS ? 2 * t : t), *rp = lds + (w << 10) + (t & 63);  // constant offsets from here on: immediates of the ds instructions
     u64 y[32];
     W14_PRIO_UP();
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
+        if constexpr (PAIRS) {  // pass = (i10 = h, lo, i0): the pair (i0 = 0, 1) leaves as one ds_write_b128 at slot (n << 10) | (lo << (7 + R0)) | 2 t
 #pragma unroll
-        for (int lo = 0; lo < NLOW; ++lo)
+            for (int lo = 0; lo < NLOW / 2; ++lo)
 #pragma unroll
-            for (int n = 0; n < (1 << R0); ++n) wp[(n << 10) | (lo << (10 - (PB - 1)))] = x[((((h << (PB - 1)) | lo)) << R0) | n];
+                for (int n = 0; n < (1 << R0); ++n) {
+                    const int r = ((((h * (NLOW / 2)) | lo) << 1) << R0) | n;
+                    *reinterpret_cast<ulonglong2 *>(wp + ((n << 10) | (lo << (7 + R0)))) = make_ulonglong2(x[r], x[r + (1 << R0)]);
+                }
+        } else {
+#pragma unroll
+            for (int lo = 0; lo < NLOW; ++lo)
+#pragma unroll
+                for (int n = 0; n < (1 << R0); ++n) wp[(n << 10) | (lo << (10 - (PB - 1)))] = x[((((h << (PB - 1)) | lo)) << R0) | n];
+        }
         W14_SYNC();
 #pragma unroll
         for (int m = 0; m < 16; ++m) {  // m = (i9 i8 i7 i6)
@@ -131,10 +156,10 @@ __device__ __forceinline__ void xchg_01(u64 (&x)[32], int t, int w, u64 *lds) {
     for (int r = 0; r < 32; ++r) x[r] = y[r];
 }
 
-template <int R0>
+template <int R0, bool PAIRS>
 __device__ __forceinline__ void xchg_10(u64 (&x)[32], int t, int w, u64 *lds) {
     constexpr int PB = 5 - R0, NLOW = 1 << (PB - 1);
-    u64 *rp = lds + t, *wp = lds + (w << 10) + (t & 63);
+    u64 *rp = lds + (PAIRS ? 2 * t : t), *wp = lds + (w << 10) + (t & 63);
     u64 y[32];
     W14_PRIO_UP();
     W14_SYNC();  // every wave has left its private region
@@ -146,10 +171,21 @@ __device__ __forceinline__ void xchg_10(u64 (&x)[32], int t, int w, u64 *lds) {
             wp[m << 6] = x[(s << 4) | n4];
         }
         W14_SYNC();
+        if constexpr (PAIRS) {  // one ds_read_b128 per pair, the slots of xchg_01
 #pragma unroll
-        for (int lo = 0; lo < NLOW; ++lo)
+            for (int lo = 0; lo < NLOW / 2; ++lo)
 #pragma unroll
-            for (int n = 0; n < (1 << R0); ++n) y[((((h << (PB - 1)) | lo)) << R0) | n] = rp[(n << 10) | (lo << (10 - (PB - 1)))];
+                for (int n = 0; n < (1 << R0); ++n) {
+                    const int r = ((((h * (NLOW / 2)) | lo) << 1) << R0) | n;
+                    const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(rp + ((n << 10) | (lo << (7 + R0))));
+                    y[r] = v.x; y[r + (1 << R0)] = v.y;
+                }
+        } else {
+#pragma unroll
+            for (int lo = 0; lo < NLOW; ++lo)
+#pragma unroll
+                for (int n = 0; n < (1 << R0); ++n) y[((((h << (PB - 1)) | lo)) << R0) | n] = rp[(n << 10) | (lo << (10 - (PB - 1)))];
+        }
         if (h == 0) W14_SYNC();
     }
     W14_PRIO_DOWN();
@@ -270,8 +306,10 @@ __device__ __forceinline__ void tw7_load(Tw7<A> &b, int t3, const typename A::K 
     tw_load<A, INV, P3<R0, 2, AB>>(b.l2, t3, k);
 }
 
-// HBM side of pass 0: register (pass, n) <-> coefficient (n << 11) | (pass << (6 + R0)) | t, consecutive lanes on consecutive words
-template <int R0>
+// HBM side of pass 0.  PAIRS: register (hi, i0, n) <-> coefficient (n << 11) | (hi << (7 + R0)) | (t << 1) | i0: one 16-byte load
+// per (hi, n), a wave-instruction covers 1 KiB contiguous (g is 16-byte aligned).  Otherwise register (pass, n) <-> coefficient
+// (n << 11) | (pass << (6 + R0)) | t, consecutive lanes on consecutive words.
+template <int R0, bool PAIRS>
 __device__ __forceinline__ void load_p0(u64 (&x)[32], const u64 *__restrict__ g, int t) {
 #pragma unroll
     for (int r = 0; r < 32; ++r) {
@@ -279,7 +317,13 @@ __device__ __forceinline__ void load_p0(u64 (&x)[32], const u64 *__restrict__ g,
 #ifdef W14_ABLATE_NO_GLOBAL  // developer lab only: no HBM traffic
         x[r] = (u64)(t + r) * 0x9E3779B97F4A7C15ull >> 5;
 #else
-        x[r] = g[(n << 11) | (pass << (6 + R0)) | t];
+        if constexpr (PAIRS) {
+            if (pass & 1) continue;
+            const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(g + ((n << 11) | ((pass >> 1) << (7 + R0)) | (t << 1)));
+            x[r] = v.x; x[r + (1 << R0)] = v.y;
+        } else {
+            x[r] = g[(n << 11) | (pass << (6 + R0)) | t];
+        }
 #endif
     }
 }
@@ -371,7 +415,7 @@ __device__ __forceinline__ void fwd_one(u64 (&x)[32], u64 *__restrict__ g, const
     Tw b0[1], b1[2], b2[4], b3[8];  // pass 1: wave-uniform as well (block prefix = w): fetched behind the barriers of X01
     tw_load<A, false, P1<R0, 0>>(b0, w, k); tw_load<A, false, P1<R0, 1>>(b1, w, k); tw_load<A, false, P1<R0, 2>>(b2, w, k); tw_load<A, false, P1<R0, 3>>(b3, w, k);
     STAMP(2);
-    xchg_01<R0>(x, t, w, lds);
+    xchg_01<R0, w14_pairs<A, R0>()>(x, t, w, lds);
     STAMP(3);
     if constexpr (A::PASS_FOLD) {
 #pragma unroll
@@ -590,7 +634,7 @@ __device__ __forceinline__ void inv_one(u64 (&x)[32], Tw7<A> (&d)[2], u64 *__res
     if constexpr (R0 >= 3) tw_load<A, true, P0<R0, (R0 >= 3 ? 2 : 0)>>(a2, 0, k);
     if constexpr (R0 >= 2) tw_load<A, true, P0<R0, (R0 >= 2 ? 1 : 0)>>(a1, 0, k);
     if constexpr (PFX) tw_load<A, true, P0<R0, 0>>(a0, 0, k);
-    xchg_10<R0>(x, t, w, lds);
+    xchg_10<R0, w14_pairs<A, R0>()>(x, t, w, lds);
     STAMP(6);
     if constexpr (R0 == 4) {
         FHE_SCHED_FENCE();
@@ -611,18 +655,42 @@ __device__ __forceinline__ void inv_one(u64 (&x)[32], Tw7<A> (&d)[2], u64 *__res
     if constexpr (PFX) wlast = A::prep(a0[0]);
     constexpr int LAST_PH = A::GS_SPAN > 0 ? (10 + R0) % (A::GS_SPAN > 0 ? A::GS_SPAN : 1) : 1;  // layers since the sums were last folded
     constexpr int HALF = 1 << (R0 - 1), REPS = 32 >> R0, CH = HALF < 4 ? HALF : 4;
-    static_for<0, REPS * (HALF / CH)>([&](auto cc) {  // (up to) four butterflies at a time, stored as they finish
-        constexpr int pass = decltype(cc)::value / (HALF / CH), j0 = (decltype(cc)::value % (HALF / CH)) * CH;
-        FHE_SCHED_FENCE();
+    if constexpr (w14_pairs<A, R0>()) {
+        // the replicas (hi, i0 = 0) and (hi, 1) of a butterfly finish together and leave as two 16-byte stores; (up to) four
+        // butterflies at a time, stored as they finish
+        constexpr int CHP = CH < 2 ? 1 : CH / 2;
+        static_for<0, (REPS / 2) * (HALF / CHP)>([&](auto cc) {
+            constexpr int hi = decltype(cc)::value / (HALF / CHP), j0 = (decltype(cc)::value % (HALF / CHP)) * CHP;
+            FHE_SCHED_FENCE();
 #pragma unroll
-        for (int j = j0; j < j0 + CH; ++j) {
-            const int o = (pass << R0) + j;
-            if constexpr (PFX) A::template gs_last_plain<LAST_PH>(x[o], x[o + HALF], wlast, k);
-            else A::template gs_last_scaled<LAST_PH>(x[o], x[o + HALF], k);
-            g[(j << 11) | (pass << (6 + R0)) | t] = x[o];
-            g[((j + HALF) << 11) | (pass << (6 + R0)) | t] = x[o + HALF];
-        }
-    });
+            for (int j = j0; j < j0 + CHP; ++j) {
+                const int o = ((2 * hi) << R0) + j, o1 = o + (1 << R0);
+                if constexpr (PFX) {
+                    A::template gs_last_plain<LAST_PH>(x[o], x[o + HALF], wlast, k);
+                    A::template gs_last_plain<LAST_PH>(x[o1], x[o1 + HALF], wlast, k);
+                } else {
+                    A::template gs_last_scaled<LAST_PH>(x[o], x[o + HALF], k);
+                    A::template gs_last_scaled<LAST_PH>(x[o1], x[o1 + HALF], k);
+                }
+                u64 *p = g + ((hi << (7 + R0)) | (t << 1));
+                *reinterpret_cast<ulonglong2 *>(p + (j << 11)) = make_ulonglong2(x[o], x[o1]);
+                *reinterpret_cast<ulonglong2 *>(p + ((j + HALF) << 11)) = make_ulonglong2(x[o + HALF], x[o1 + HALF]);
+            }
+        });
+    } else {
+        static_for<0, REPS * (HALF / CH)>([&](auto cc) {  // (up to) four butterflies at a time, stored as they finish
+            constexpr int pass = decltype(cc)::value / (HALF / CH), j0 = (decltype(cc)::value % (HALF / CH)) * CH;
+            FHE_SCHED_FENCE();
+#pragma unroll
+            for (int j = j0; j < j0 + CH; ++j) {
+                const int o = (pass << R0) + j;
+                if constexpr (PFX) A::template gs_last_plain<LAST_PH>(x[o], x[o + HALF], wlast, k);
+                else A::template gs_last_scaled<LAST_PH>(x[o], x[o + HALF], k);
+                g[(j << 11) | (pass << (6 + R0)) | t] = x[o];
+                g[((j + HALF) << 11) | (pass << (6 + R0)) | t] = x[o + HALF];
+            }
+        });
+    }
     STAMP(8);
 #ifdef NTT14_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -663,7 +731,7 @@ __global__ __launch_bounds__(w14::threads<R0>(), 4) void ntt14w_fwd_kernel(u64 *
     u64 *g = data + (size_t(sub) << LOG_N);
     const u64 *gs = ntt_src(io, sub, LOG_N, g);
     u64 x[32];
-    w14::load_p0<R0>(x, gs, t);
+    w14::load_p0<R0, w14::w14_pairs<A, R0>()>(x, gs, t);
     w14::fwd_one<A, R0>(x, g, k, lds, lds + w * w14::WSLOTS, t, lane, w STAMP_ENTRY_ARG);
 }
 
@@ -734,7 +802,7 @@ __global__ __launch_bounds__(w14::threads<R0>(), 4) void ntt14w_mul_kernel(u64 *
     u64 *g = data + (size_t(sub) << LOG_N);
     const u64 *mul_poly = io.mul + ((size_t(sub / io.mul_div) * io.mul_period + sub % io.mul_period) << LOG_N);  // wave uniform
     u64 x[32];
-    w14::load_p0<R0>(x, g, t);
+    w14::load_p0<R0, w14::w14_pairs<A, R0>()>(x, g, t);
     w14::fwd_one<A, R0, true>(x, g, k, lds, lds + w * w14::WSLOTS, t, lane, w STAMP_ENTRY_ARG);
     // the inverse half sees the thread index as a fresh value: its ~100 addresses (LDS slots, twiddle entries, stores) would otherwise
     // be computed at the top of the kernel and live -- spilled -- through the whole forward half

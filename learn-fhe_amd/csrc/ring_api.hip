@@ -74,6 +74,8 @@ inline bool limb_major_disabled() { return fhe::opt(fhe::OPT_NO_LIMB_MAJOR) != 0
 inline bool wave_local_small_disabled() { return fhe::opt(fhe::OPT_NO_W12) != 0; }       // 2^12 / 2^13 on the generic kernels
 // a launch of the two-workgroups-per-CU kernels spans several generations of workgroups from this size on
 inline size_t several_generations() { return size_t(8) * (size_t)fhe::current_cu_count(); }
+template <class... P>
+inline bool aligned16(const P *...p) { return ((... | (uintptr_t)p) % 16) == 0; }
 template <class AF, class AI, int R0 = 3>
 int launch14(bool inv, const fhe::ModDesc *d, unsigned nd, u64 *a, size_t subs, int pb, hipStream_t st, fhe::NttIo io) {
     // several moduli: modulus-major dispatch order (ntt14w.hpp, sub_of_block)
@@ -82,6 +84,12 @@ int launch14(bool inv, const fhe::ModDesc *d, unsigned nd, u64 *a, size_t subs, 
     // measured 3 % slower at cfg4 batch 8)
     const bool by_mod = nd > 1 && nd <= 65535 && polys % nd == 0 && subs >= several_generations() && !limb_major_disabled();
     const dim3 grid = by_mod ? dim3((unsigned)(subs / nd), nd) : dim3((unsigned)subs);
+    // every polynomial is read and written 16 bytes per lane (ntt14w.hpp); since the pass-0 side deals coefficient pairs that
+    // includes the source of an out-of-place forward at 2^12 .. 2^14
+    if (!aligned16(a, io.mul, io.dst2)) return FHE_ERR_INVALID;
+    if constexpr (R0 <= 3) {
+        if (!inv && !aligned16(io.src, io.src2, io.src3, io.src4)) return FHE_ERR_INVALID;
+    }
 #define W14(K) fhe::launch<K>(grid, fhe::w14::threads<R0>(), fhe::w14::lds_bytes<R0>(), st, a, d, nd, (unsigned)subs, pb, io)
     if (!inv) return pb ? W14((fhe::ntt14w_fwd_kernel<AF, true, R0>)) : W14((fhe::ntt14w_fwd_kernel<AF, false, R0>));
     if (pb) return io.mul ? W14((fhe::ntt14w_inv_kernel<AI, true, true, R0>)) : W14((fhe::ntt14w_inv_kernel<AI, true, false, R0>));
@@ -92,6 +100,7 @@ int launch14(bool inv, const fhe::ModDesc *d, unsigned nd, u64 *a, size_t subs, 
 // the fused ring product (ntt14w_mul_kernel): a <- inverse(forward(a) (.) io.mul), 2^13 .. 2^15
 template <class A, int R0>
 int launch_mul14(const fhe::ModDesc *d, unsigned nd, u64 *a, size_t subs, hipStream_t st, fhe::NttIo io) {
+    if (!aligned16(a, io.mul)) return FHE_ERR_INVALID;  // 16 bytes per lane on both sides (ntt14w.hpp)
     const bool by_mod = nd > 1 && nd <= 65535 && subs % nd == 0 && subs >= several_generations() && !limb_major_disabled();
     const dim3 grid = by_mod ? dim3((unsigned)(subs / nd), nd) : dim3((unsigned)subs);
     return fhe::launch<fhe::ntt14w_mul_kernel<A, R0>>(grid, fhe::w14::threads<R0>(), fhe::w14::lds_bytes<R0>(), st, a, d, nd, (unsigned)subs, 0, io);

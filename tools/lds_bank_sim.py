@@ -121,3 +121,8 @@ if __name__ == "__main__":
         # reader: lane l reads the pair at 128 k + 2 l
         check128("stage read b128, " + name, "read128", lambda lane, k, pad=pad: pad(128 * k + 2 * lane), range(4))
         check("stage write b64, " + name, "write64", lambda lane, j, pad=pad: pad(8 * lane + j), range(8))
+    print("-- ntt14w.hpp X01, pass-0 side: a thread's pair (i, i + 1) at slot (n << 10) + 2 t --")
+    for r0 in (1, 2, 3):
+        for wave in range(1 << r0):
+            check128("X01 pass-0 write b128, R0 = %d wave %d" % (r0, wave), "write128", lambda lane, n, wave=wave: (n << 10) + 2 * (64 * wave + lane), range(1 << r0))
+            check128("X10 pass-0 read b128, R0 = %d wave %d" % (r0, wave), "read128", lambda lane, n, wave=wave: (n << 10) + 2 * (64 * wave + lane), range(1 << r0))

@@ -14,6 +14,9 @@ using namespace fhe;
 
 constexpr int N14_THREADS = w14::THREADS;
 constexpr size_t N14_LDS_BYTES = w14::LDS_BYTES;
+struct DSOld : ArithDS<60> {  // the pass-0 side as it was dealt before the coefficient pairs: thread = i[8:0], 8-byte HBM and LDS accesses (same results)
+    static constexpr bool W14_OLD_DEAL = true;
+};
 struct DSNoTw : ArithDS<60> {  // ablation: butterflies with a computed twiddle, no twiddle loads (wrong results, same work)
     template <bool INV> static __device__ __forceinline__ TwRaw fetch(const K &k, int idx) { return uint4{k.ninv.x + (unsigned)idx, k.ninv.y, k.ninv.z ^ (unsigned)idx, k.ninv.w}; }
 };
@@ -137,6 +140,7 @@ int main(int argc, char **argv) {
     V vs[] = {
         {"wave-local, PM60", ntt14w_fwd_kernel<ArithPM<60>, false>, ntt14w_inv_kernel<ArithPM<60>, false>, 0, 0, 1},
         {"wave-local, DS60", ntt14w_fwd_kernel<ArithDS<60>, false>, ntt14w_inv_kernel<ArithDS<60>, false>, 0, 0, 1},
+        {"DS60, 8-byte pass-0 side (old)", ntt14w_fwd_kernel<DSOld, false>, ntt14w_inv_kernel<DSOld, false>, 0, 0, 1},
         {"wave-local, Shoup", ntt14w_fwd_kernel<ArithShoup, false>, ntt14w_inv_kernel<ArithShoup, false>, 0, 0, 1},
         {"wave-local DS60, no twiddle loads", ntt14w_fwd_kernel<DSNoTw, false>, ntt14w_inv_kernel<DSNoTw, false>, 0, 0, 1},
         {"DS60, pass-3 twiddles computed", ntt14w_fwd_kernel<DSSkip<0x3800>, false>, ntt14w_inv_kernel<DSSkip<0x3800>, false>, 0, 0, 1},
@@ -195,7 +199,7 @@ int main(int argc, char **argv) {
         printf("%-32s fwd %.4f ms %5.0f GB/s (%.3f of 8 TB/s) | inv %.4f ms %5.0f GB/s (%.3f)\n", v.name, v.sf / reps, bytes / (v.sf / reps * 1e-3) / 1e9,
                bytes / (v.sf / reps * 1e-3) / 8e12, v.si / reps, bytes / (v.si / reps * 1e-3) / 1e9, bytes / (v.si / reps * 1e-3) / 8e12);
 #ifdef NTT14_STAMPS
-    for (int vi : {0, 1, 3})
+    for (int vi : {0, 1, 2})  // PM60, DS60 (coefficient pairs), DS60 with the 8-byte pass-0 side
     for (int dir : {0, 1}) {   // where does a workgroup spend its life?
         auto &v = vs[vi];
         for (int r = 0; r < 40; ++r) hipLaunchKernelGGL(dir ? v.i : v.f, dim3(GRID(v)), dim3(N14_THREADS), N14_LDS_BYTES, 0, d, (const ModDesc *)d_desc, 1u, (unsigned)batch, 0, NttIo());
@@ -215,7 +219,13 @@ int main(int argc, char **argv) {
             if (hs[b][9] > t1) t1 = hs[b][9];
         }
         printf("%s %s: stamps (s_memtime ticks, avg over %d workgroups; lifetime %.0f; kernel span %llu ticks)\n", v.name, dir ? "INVERSE" : "forward", cnt, life / cnt, t1 - t0);
-        for (int p2 = 0; p2 < 9; ++p2) printf("  %-20s %8.0f (%4.1f%%)\n", names[p2], sum[p2] / cnt, 100.0 * sum[p2] / life);
+        for (int p2 = 0; p2 < 9; ++p2) {  // stamp p2 -> stamp p2 + 1: average, share of the lifetime, median over the workgroups
+            std::vector<double> iv;
+            for (int b = 0; b < batch && b < 4096; ++b)
+                if (hs[b][9] > hs[b][0]) iv.push_back(double(hs[b][p2 + 1] - hs[b][p2]));
+            std::nth_element(iv.begin(), iv.begin() + iv.size() / 2, iv.end());
+            printf("  %d->%d %-20s %8.0f (%4.1f%%)  median %8.0f\n", p2, p2 + 1, names[p2], sum[p2] / cnt, 100.0 * sum[p2] / life, iv.empty() ? 0.0 : iv[iv.size() / 2]);
+        }
         {
             double ck = 0; int c2 = 0; unsigned long long r0 = ~0ull, r1 = 0;
             for (int b = 0; b < batch && b < 4096; ++b) {
