@@ -36,7 +36,8 @@ enum {
     FHE_ERR_MODULUS = 4,      /* operands over different moduli (zq.rs:145/177/185/193 assert_eq) */
     FHE_ERR_HIP = 5,          /* a HIP runtime call failed; fhe_last_hip_error() has the code */
     FHE_ERR_UNSUPPORTED = 6,  /* valid in the reference, outside what this build implements (q >= 2^62, n > 2^17) */
-    FHE_ERR_NO_DEVICE = 7     /* compute call on a host-only context */
+    FHE_ERR_NO_DEVICE = 7,    /* compute call on a host-only context */
+    FHE_ERR_TIMEOUT = 8       /* a bounded wait between the workgroups of one launch ran out (split FHEW blind rotation): no output written */
 };
 
 typedef enum { FHE_MEM_HOST = 0, FHE_MEM_DEVICE = 1 } fhe_mem;
@@ -54,8 +55,10 @@ int fhe_trim(void);
  * several moduli), "NO_W12" (2^12 / 2^13 rings on the generic kernels), "NO_FUSED_MUL" (ring product as forward + multiplying
  * inverse), "SMALL_BATCH" (FHEW: 4 coefficients per lane up to this batch, 8 above; -1 = the library's rule), "NO_F64_EXACT" (TFHE: eligible keys on the three-prime integer path instead of the three-piece f64 one), "NO_PACKED_DIGITS" (TFHE blind
  * rotation: digits decomposed once per prime instead of once per CMUX), "FHEW_COMPOSED" (FHEW keys prepared while it is set run the
- * composed route at n = 128 .. 2048 too, instead of the fused kernels).  Unknown name:
- * FHE_ERR_INVALID. */
+ * composed route at n = 128 .. 2048 too, instead of the fused kernels), "BR_SPLIT" (FHEW blind rotation: workgroups per ciphertext;
+ * -1 = the library's rule, 0 = never split, 2 / 4 / 8 = that many wherever the call admits it -- fused route, n = 1024 or 2048,
+ * batch x value <= compute units of the device -- and one workgroup per ciphertext elsewhere; any other value: FHE_ERR_INVALID;
+ * fhe_blind_rotate_split tells what a call will run).  Unknown name: FHE_ERR_INVALID. */
 int fhe_set_option(const char *name, long value);
 
 /* Entry points that take a modulus instead of a context (fhe_rq_*, fhe_decompose, fhe_automorphism, fhe_monomial_mul,
@@ -162,9 +165,15 @@ int fhe_bootstrap_key_create(const fhe_ctx *ctx, const fhe_key *brk, const fhe_k
                              fhe_bootstrap_key **out);
 void fhe_bootstrap_key_destroy(fhe_bootstrap_key *bk);
 /* Waits for everything enqueued on `stream`, then FHE_ERR_INVALID if an asynchronous (device-memory) fhe_blind_rotate /
- * fhe_fhew_bootstrap on this key met an LWE coefficient that is not an odd residue mod 2n since the word was last cleared, else
- * FHE_OK; clear != 0 resets the word. */
+ * fhe_fhew_bootstrap on this key met an LWE coefficient that is not an odd residue mod 2n since the word was last cleared,
+ * FHE_ERR_TIMEOUT if a split blind rotation gave up a wait (fhe_blind_rotate_split), else FHE_OK; clear != 0 resets the word. */
 int fhe_bootstrap_key_status(const fhe_bootstrap_key *bk, void *stream, int clear);
+/* Workgroups per ciphertext (*g_out = 1, 2, 4 or 8) that fhe_blind_rotate / fhe_fhew_bootstrap would use for this key and batch
+ * under the current options ("BR_SPLIT") on the context's device.  Above 1 a cluster of workgroups shares the digit transforms of
+ * every step of one ciphertext's walk and hands partial sums over inside the launch: lower latency at batches that leave the chip
+ * idle, bit-identical results.  Its waits are bounded: one that runs out writes no output and the call reports FHE_ERR_TIMEOUT
+ * (host-memory calls in their return value, device-memory calls through fhe_bootstrap_key_status). */
+int fhe_blind_rotate_split(const fhe_bootstrap_key *bk, size_t batch, int *g_out);
 /* scheme/fhew/src/bootstrapping.rs:158-209 `blind_rotate(param, brk, ak, f, LweCiphertext(a, b))` for a batch:
  * lwe_a [batch][n_lwe] and lwe_b [batch] are taken mod 2n (after mod_switch_odd); f = LUT polynomial(s),
  * f_stride = 0 (one f) or n (one per ciphertext); out_a/out_b [batch][n] = the rotated accumulator.

@@ -11,7 +11,7 @@ _SO = os.environ.get("FHE_RING_LIB") or os.path.join(_HERE, "lib", "libfhe_ring.
 _lib = None
 
 STATUS = {0: "FHE_OK", 1: "FHE_ERR_INVALID", 2: "FHE_ERR_NOT_PRIME", 3: "FHE_ERR_NO_ROOT", 4: "FHE_ERR_MODULUS",
-          5: "FHE_ERR_HIP", 6: "FHE_ERR_UNSUPPORTED", 7: "FHE_ERR_NO_DEVICE"}
+          5: "FHE_ERR_HIP", 6: "FHE_ERR_UNSUPPORTED", 7: "FHE_ERR_NO_DEVICE", 8: "FHE_ERR_TIMEOUT"}
 MEM_HOST, MEM_DEVICE = 0, 1
 
 
@@ -85,6 +85,7 @@ def lib():
         L.fhe_bootstrap_key_destroy.argtypes = [vp]
         L.fhe_bootstrap_key_destroy.restype = None
         L.fhe_bootstrap_key_status.argtypes = [vp, vp, ci]
+        L.fhe_blind_rotate_split.argtypes = [vp, sz, C.POINTER(ci)]
         L.fhe_blind_rotate.argtypes = [vp, vp, vp, vp, sz, vp, vp, sz, ci, vp, u32p, u32p]
         L.fhe_rns_ctx_create.argtypes = [u64p, ci, u64p, ci, ci, C.POINTER(vp)]
         L.fhe_rns_ctx_destroy.argtypes = [vp]

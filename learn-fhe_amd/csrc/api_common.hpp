@@ -101,10 +101,12 @@ inline hipMemPool_t private_pool(int dev) {
 // looks at any of them) and afterwards only changes through fhe_set_option(): no getenv on any call path.
 namespace fhe {
 // FHEW_COMPOSED: FHEW keys prepared while it is set run the composed route (fhew_composed_kernels.hpp) at N = 128 .. 2048 as well.
+// BR_SPLIT: workgroups per ciphertext of the FHEW blind rotation (fhew_split_kernels.hpp): -1 the library's rule, 0 never split, 2 / 4 / 8.
 enum Opt { OPT_NO_EDGE = 0, OPT_NO_LIMB_MAJOR, OPT_NO_W12, OPT_NO_FUSED_MUL, OPT_SMALL_BATCH, OPT_NO_PACKED_DIGITS, OPT_NO_F64_EXACT, OPT_FHEW_COMPOSED,
-           OPT_COUNT };
+           OPT_BR_SPLIT, OPT_COUNT };
 inline const char *const OPT_NAMES[OPT_COUNT] = {"NO_EDGE", "NO_LIMB_MAJOR", "NO_W12", "NO_FUSED_MUL", "SMALL_BATCH", "NO_PACKED_DIGITS", "NO_F64_EXACT",
-                                                 "FHEW_COMPOSED"};
+                                                 "FHEW_COMPOSED", "BR_SPLIT"};
+inline bool br_split_value_ok(long v) { return v == -1 || v == 0 || v == 2 || v == 4 || v == 8; }
 struct Options {
     std::atomic<long> v[OPT_COUNT];
     Options() {
@@ -112,7 +114,9 @@ struct Options {
             char name[64] = "FHE_RING_";
             std::strncat(name, OPT_NAMES[i], sizeof(name) - 10);
             const char *e = std::getenv(name);
-            v[i].store(e ? std::atol(e) : (i == OPT_SMALL_BATCH ? -1L : 0L), std::memory_order_relaxed);
+            long val = e ? std::atol(e) : ((i == OPT_SMALL_BATCH || i == OPT_BR_SPLIT) ? -1L : 0L);
+            if (i == OPT_BR_SPLIT && !br_split_value_ok(val)) val = -1L;
+            v[i].store(val, std::memory_order_relaxed);
         }
     }
 };

@@ -10,6 +10,7 @@
 #include "ctx.hpp"
 #include "fhew_composed_kernels.hpp"
 #include "fhew_kernels.hpp"
+#include "fhew_split_kernels.hpp"
 #include "lwe_kernels.hpp"
 
 // defined in ring_api.hip
@@ -171,6 +172,33 @@ inline bool small_shape(int log_n, size_t batch) {
     const size_t cus = (size_t)fhe::current_cu_count();
     if (log_n == 10) return batch <= 3 * cus || batch > 4 * cus;
     return log_n >= 10 && batch <= 2 * cus;
+}
+
+// Workgroups per ciphertext of a blind rotation (fhew_split_kernels.hpp): 1 = blind_rotate_kernel, 2 / 4 / 8 = a cluster.
+// Admissible: fused route, N = 1024 or 2048 (the 4-coefficients-per-lane rows exist), and every workgroup of the launch certainly
+// resident together -- one cluster member per compute unit: batch * G <= compute units.  "BR_SPLIT" = 2 / 4 / 8 forces that G where
+// admissible, 0 never splits, -1 is the rule below.
+// Measured at cfg3's parameters (d = 9, n_lwe = 100, w = 10; tools/fhew_shape_lab.py --split, blind rotations/s, medians of five
+// interleaved rounds in one process, 256 compute units; "-": batch * G exceeds them), G = 1 | 2 | 4 | 8:
+//   N = 1024  batch 1: 134 | 194 | 258 | 285        2: 263 | 386 | 512 | 576          4: 527 | 771 | 1008 | 1150
+//             8: 1049 | 1517 | 1988 | 2267          16: 2097 | 3057 | 3997 | 4517     32: 4220 | 6085 | 7918 | 8768
+//             64: 8460 | 12058 | 15546 | -          128: 16789 | 23366 | - | -
+//   N = 2048  batch 1: 73 | 106 | 139 | 148         2: 144 | 208 | 273 | 296          4: 288 | 420 | 545 | 598
+//             8: 573 | 832 | 1069 | 1172            16: 1150 | 1650 | 2133 | 2358     32: 2280 | 3302 | 4261 | 4557
+//             64: 4592 | 6569 | 8440 | -            128: 9159 | 12947 | - | -
+// Every admissible G beats the one-workgroup shape by 39 % or more (the run-to-run spread of that shape is below 1 %), and the
+// largest admissible G is the fastest in every row: the rule takes it at both sizes, so it covers batches up to half the compute
+// units and changes nothing above (batch 1024 and 4096 run what they ran).  A step takes 13.8 us under G = 8 at N = 1024 against 29.4
+// in one workgroup (DESIGN.md section 4.4a says where it goes).
+inline int split_g(const fhe_bootstrap_key *bk, size_t batch) {
+    const long lab = fhe::opt(fhe::OPT_BR_SPLIT);
+    const fhe_key *brk = bk->brk, *ak = bk->ak;
+    if (lab == 0 || batch == 0 || brk->composed || brk->log_n < 10 || brk->log_n > 11 || !brk->d_rows_small || !ak->d_rows_small) return 1;
+    const size_t cus = (size_t)fhe::cu_count(bk->ctx->device);
+    if (lab > 0) return batch * (size_t)lab <= cus ? (int)lab : 1;
+    for (int g = fhe::SPLIT_MAX_G; g >= 2; g >>= 1)
+        if (batch * (size_t)g <= cus) return g;
+    return 1;
 }
 
 fhe::FhewKey key_view(const fhe_key *k, bool small = false) {
@@ -599,7 +627,8 @@ int fhe_blind_rotate(const fhe_bootstrap_key *bk, const uint64_t *lwe_a, const u
         if (rc != FHE_OK) return fail(rc);
     } else {
         fhe::BlindRotateParams BR;
-        const bool small = small_shape(log_n, batch);
+        const int split = split_g(bk, batch);
+        const bool small = split > 1 || small_shape(log_n, batch);
         BR.brk = key_view(bk->brk, small);
         BR.ak = key_view(bk->ak, small);
         BR.ak_t = bk->d_ak_t;
@@ -620,7 +649,28 @@ int fhe_blind_rotate(const fhe_bootstrap_key *bk, const uint64_t *lwe_a, const u
             break;                                                                               \
         }
         const int pmv = fhew_pm(ctx, log_n);
-        if (pmv == 54) {
+        if (split > 1) {
+            // polled words | slabs, in a stream-ordered workspace of this call; the polled words are zeroed in front of the launch
+            const size_t ctl_bytes = batch * fhe::SPLIT_CTL_WORDS * sizeof(unsigned);  // a multiple of 16 at the allocation's start
+            const size_t slab_words = 2 * batch * (size_t)split * 2 * n;
+            StreamWs sws(ctl_bytes + slab_words * sizeof(u64), st);
+            if (sws.rc != FHE_OK) return fail(sws.rc);
+            fhe::SplitWs S;
+            S.ctl = sws.as<unsigned>();
+            S.slabs = reinterpret_cast<u64 *>(sws.as<unsigned char>() + ctl_bytes);
+            S.status = d_err;
+            if (hipMemsetAsync(S.ctl, 0, ctl_bytes, st) != hipSuccess) return fail(FHE_ERR_HIP);
+#define BRS_LAUNCH(AR, LN)                                                                                                          \
+            {                                                                                                                        \
+                typedef fhe::WaveRing<LN, 2> WS;                                                                                     \
+                rc = fhe::launch<fhe::blind_rotate_split_kernel<AR, WS>>((unsigned)(batch * split), WS::THREADS, fhe::split_lds_bytes<WS>(), st, \
+                                                                         BR, S, moa.d, mob.d, (unsigned)batch, split, ring_consts(ctx, 0)); \
+            }
+            if (pmv == 54) { if (log_n == 10) BRS_LAUNCH(FHEW_POLICY54, 10) else BRS_LAUNCH(FHEW_POLICY54, 11) }
+            else if (pmv == 55) { if (log_n == 10) BRS_LAUNCH(FHEW_POLICY55, 10) else BRS_LAUNCH(FHEW_POLICY55, 11) }
+            else { if (log_n == 10) BRS_LAUNCH(fhe::ArithShoup, 10) else BRS_LAUNCH(fhe::ArithShoup, 11) }
+#undef BRS_LAUNCH
+        } else if (pmv == 54) {
             switch (log_n) {
                 BR_CASE(FHEW_POLICY54, 9) BR_CASE_BIG(FHEW_POLICY54, 10) BR_CASE_BIG(FHEW_POLICY54, 11)
                 default: return fail(FHE_ERR_UNSUPPORTED);
@@ -653,7 +703,8 @@ int fhe_blind_rotate(const fhe_bootstrap_key *bk, const uint64_t *lwe_a, const u
     rc = moa.sync_out(st);
     if (rc == FHE_OK) rc = mob.sync_out(st);
     if (hipStreamSynchronize(st) != hipSuccess && rc == FHE_OK) rc = FHE_ERR_HIP;  // h_err (and ops_out) must have arrived
-    if (rc == FHE_OK && h_err) rc = FHE_ERR_INVALID;  // an LWE coefficient outside the odd residues mod 2N (bootstrapping.rs:221)
+    if (rc == FHE_OK && h_err == fhe::BR_STATUS_TIMEOUT) rc = FHE_ERR_TIMEOUT;  // a cluster gave up a wait: its output was not written
+    else if (rc == FHE_OK && h_err) rc = FHE_ERR_INVALID;  // an LWE coefficient outside the odd residues mod 2N (bootstrapping.rs:221)
     return rc;
 }
 
@@ -670,7 +721,14 @@ int fhe_bootstrap_key_status(const fhe_bootstrap_key *bk, void *stream, int clea
     HIP_TRY(hipMemcpyAsync(&h, bk->d_status, sizeof(int), hipMemcpyDeviceToHost, st));
     if (clear) HIP_TRY(hipMemsetAsync(bk->d_status, 0, sizeof(int), st));
     HIP_TRY(hipStreamSynchronize(st));
-    return h ? FHE_ERR_INVALID : FHE_OK;
+    return h == fhe::BR_STATUS_TIMEOUT ? FHE_ERR_TIMEOUT : h ? FHE_ERR_INVALID : FHE_OK;
+}
+
+int fhe_blind_rotate_split(const fhe_bootstrap_key *bk, size_t batch, int *g_out) {
+    if (!bk || !g_out) return FHE_ERR_INVALID;
+    if (bk->ctx->device < 0) return FHE_ERR_NO_DEVICE;
+    *g_out = split_g(bk, batch);
+    return FHE_OK;
 }
 
 // scheme/fhew/src/bootstrapping.rs:149-155 `Bootstrapping::bootstrap(bk, f, ct)` for a batch, everything device side:

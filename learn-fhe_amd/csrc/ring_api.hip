@@ -291,7 +291,11 @@ int fhe_set_option(const char *name, long value) {
     for (int i = 0; i < fhe::OPT_COUNT; ++i) {
         const char *a = name, *b = fhe::OPT_NAMES[i];
         while (*a && *b && (*a == *b || *a - 32 == *b)) { ++a; ++b; }
-        if (!*a && !*b) { fhe::options().v[i].store(value, std::memory_order_relaxed); return FHE_OK; }
+        if (!*a && !*b) {
+            if (i == fhe::OPT_BR_SPLIT && !fhe::br_split_value_ok(value)) return FHE_ERR_INVALID;
+            fhe::options().v[i].store(value, std::memory_order_relaxed);
+            return FHE_OK;
+        }
     }
     return FHE_ERR_INVALID;
 }

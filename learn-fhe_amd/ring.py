@@ -301,9 +301,17 @@ class BootstrapKey:
 
     def check(self, like=None, clear=True):
         """fhe_bootstrap_key_status: device-memory blind rotations / bootstraps are asynchronous; this waits for the stream `like`
-        lives on (torch's current stream for a CUDA tensor) and raises if one of them met an even LWE coefficient."""
+        lives on (torch's current stream for a CUDA tensor) and raises if one of them met an even LWE coefficient (FHE_ERR_INVALID) or a
+        split blind rotation gave up a wait (FHE_ERR_TIMEOUT)."""
         st = _buf(like)[3] if like is not None else None
         L.check(L.lib().fhe_bootstrap_key_status(self._h, st, int(clear)), "fhe_bootstrap_key_status")
+
+    def split(self, batch: int) -> int:
+        """fhe_blind_rotate_split: workgroups per ciphertext (1, 2, 4 or 8) that blind_rotate / bootstrap would use for this batch
+        under the current options (set_option("BR_SPLIT", v)); above 1 the low-latency cluster kernel runs."""
+        g = C.c_int(0)
+        L.check(L.lib().fhe_blind_rotate_split(self._h, int(batch), C.byref(g)), "fhe_blind_rotate_split")
+        return int(g.value)
 
     def blind_rotate(self, lwe_a, lwe_b, f, want_schedule=False):
         """scheme/fhew/src/bootstrapping.rs:158-209 for a batch: lwe_a [batch][n_lwe], lwe_b [batch], f [n] or [batch][n].
