@@ -30,6 +30,11 @@ using fhe::u64;
 namespace {
 inline bool is_pow2(size_t n) { return n && !(n & (n - 1)); }
 inline int ilog2(size_t n) { return 63 - __builtin_clzll((unsigned long long)n); }
+// t.rem_euclid(2n): the exponent of X^t in Z[X] / (X^n + 1)
+inline unsigned rem_euclid_2n(int64_t t, size_t n) {
+    const int64_t two_n = 2 * (int64_t)n;
+    return (unsigned)(((t % two_n) + two_n) % two_n);
+}
 
 struct DeviceGuard {
     int prev = -1;

@@ -8,6 +8,7 @@
 
 #include "api_common.hpp"
 #include "ctx.hpp"
+#include "dispatch.hpp"
 #include "fhew_composed_kernels.hpp"
 #include "fhew_kernels.hpp"
 #include "fhew_split_kernels.hpp"
@@ -63,37 +64,48 @@ int make_decomp(uint64_t q, int log_b, int d, fhe::DecompParams *P) {
 // the grid-stride launches of this unit stop at 8192 blocks (api_common.hpp grid_for: 16384)
 inline unsigned fhew_grid(size_t total) { return grid_for(total, 8192); }
 
-fhe::RingConsts ring_consts(const fhe_ctx *c, int) {
+fhe::RingConsts ring_consts(const fhe_ctx *c) {
     fhe::RingConsts K;
     K.desc = c->d_desc;
     K.B = c->barrett;
     return K;
 }
 
-// fused kernels are instantiated for Shoup arithmetic (any prime) at every supported degree and for the 54-bit
-// pseudo-Mersenne primes (BASELINE config 3's modulus) at N = 512 .. 2048
-// arithmetic of the fused kernels on cfg3's 54-bit moduli: -DFHE_FHEW_DS=0 keeps the single-operand product (A/B switch)
-#ifndef FHE_FHEW_DS
-#define FHE_FHEW_DS 1
-#endif
-#if FHE_FHEW_DS
-#define FHEW_POLICY54 fhe::ArithDS<54>
-#else
-#define FHEW_POLICY54 fhe::ArithPM<54>
-#endif
-// ... and on the 55-bit ones of the reference's own parameter sets (scheme/fhew/examples/multi_key_uint8.rs:15-29: log_q = 55)
-#define FHEW_POLICY55 fhe::ArithDS<55>
-inline int fhew_pm(const fhe_ctx *c, int log_n) { return ((c->pm_b == 54 || c->pm_b == 55) && log_n >= 9) ? c->pm_b : 0; }
+// The fused kernels are instantiated for Shoup arithmetic (any prime) at every supported degree, N = 128 .. 2048, and for the
+// two-operand pseudo-Mersenne product (ArithDS; on cfg3's 54-bit moduli it replaced the single-operand ArithPM<54>) at N = 512 .. 2048:
+// the 54-bit primes of BASELINE config 3 and the 55-bit ones of the reference's own parameter sets
+// (scheme/fhew/examples/multi_key_uint8.rs:15-29: log_q = 55).
+template <class AR>
+constexpr int FUSED_MIN_LOG_N = std::is_same_v<AR, fhe::ArithShoup> ? 7 : 9;
+inline int fhew_pm(const fhe_ctx *c, int log_n) {
+    return ((c->pm_b == 54 || c->pm_b == 55) && log_n >= FUSED_MIN_LOG_N<fhe::ArithDS<54>>) ? c->pm_b : 0;
+}
 
-#define FHEW_DISPATCH(log_n, ...)                                          \
-    switch (log_n) {                                                       \
-        case 7: { constexpr int LN = 7; __VA_ARGS__; break; }              \
-        case 8: { constexpr int LN = 8; __VA_ARGS__; break; }              \
-        case 9: { constexpr int LN = 9; __VA_ARGS__; break; }              \
-        case 10: { constexpr int LN = 10; __VA_ARGS__; break; }            \
-        case 11: { constexpr int LN = 11; __VA_ARGS__; break; }            \
-        default: return FHE_ERR_UNSUPPORTED;                               \
-    }
+// f(Type<WR>{}) with the team shape of a ring of 2^log_n, MIN_LOG_N <= log_n <= 11: WaveRing<LN>, and from N = 1024 up a second shape
+// with 4 coefficients per lane, WaveRing<LN, 2>, that `small` selects.  SMALL_ONLY: kernels that exist in the second shape alone.
+template <int MIN_LOG_N, bool SMALL_ONLY = false, class F>
+int with_shape(int log_n, bool small, F &&f) {
+    return fhe::with_int<7, 8, 9, 10, 11>(log_n, [&](auto ln) {
+        constexpr int LN = decltype(ln)::value;
+        if constexpr (LN < MIN_LOG_N) {
+            return (int)FHE_ERR_UNSUPPORTED;
+        } else {
+            if constexpr (LN >= 10) {
+                if (small) return f(fhe::Type<fhe::WaveRing<LN, 2>>{});
+            }
+            if constexpr (SMALL_ONLY) return (int)FHE_ERR_UNSUPPORTED;
+            else return f(fhe::Type<fhe::WaveRing<LN>>{});
+        }
+    });
+}
+// f(Type<AR>{}, Type<WR>{}): the arithmetic policy of the context's modulus and the shape of the ring
+template <bool SMALL_ONLY = false, class F>
+int with_fused(const fhe_ctx *ctx, int log_n, bool small, F &&f) {
+    return fhe::with_policy<fhe::ArithDS, 54, 55>(fhew_pm(ctx, log_n), [&](auto pol) {
+        using AR = typename decltype(pol)::type;
+        return with_shape<FUSED_MIN_LOG_N<AR>, SMALL_ONLY>(log_n, small, [&](auto wr) { return f(pol, wr); });
+    });
+}
 
 int key_prepare(const fhe_ctx *ctx, int log_b, int d, int rows_per_ct, const uint64_t *rows_a, const uint64_t *rows_b, size_t n,
                 size_t count, fhe_mem mem, fhe_key **out) {
@@ -132,18 +144,17 @@ int key_prepare(const fhe_ctx *ctx, int log_b, int d, int rows_per_ct, const uin
         *out = k;
         return FHE_OK;
     }
-    if (rc == FHE_OK) {
-        FHEW_DISPATCH(log_n, rc = fhe::launch<fhe::key_permute_kernel<fhe::WaveRing<LN>>>(fhew_grid(words), 256, 0, st, ta, tb, dst, rows,
-                                                                                           fhew_pm(ctx, log_n)));
-    }
+    auto permute_to = [&](u64 *to) {
+        return [&, to](auto wr) {
+            using WR = typename decltype(wr)::type;
+            return fhe::launch<fhe::key_permute_kernel<WR>>(fhew_grid(words), 256, 0, st, ta, tb, to, rows, fhew_pm(ctx, log_n));
+        };
+    };
+    if (rc == FHE_OK) rc = with_shape<7>(log_n, false, permute_to(dst));
     u64 *dst_small = nullptr;
     if (rc == FHE_OK && log_n >= 10) {
         if (hipMalloc((void **)&dst_small, 2 * words * sizeof(u64)) != hipSuccess) rc = FHE_ERR_HIP;
-        if (rc == FHE_OK) {
-            const int pm = fhew_pm(ctx, log_n);
-            if (log_n == 10) rc = fhe::launch<fhe::key_permute_kernel<fhe::WaveRing<10, 2>>>(fhew_grid(words), 256, 0, st, ta, tb, dst_small, rows, pm);
-            else rc = fhe::launch<fhe::key_permute_kernel<fhe::WaveRing<11, 2>>>(fhew_grid(words), 256, 0, st, ta, tb, dst_small, rows, pm);
-        }
+        if (rc == FHE_OK) rc = with_shape<7, true>(log_n, true, permute_to(dst_small));
     }
     if (hipStreamSynchronize(st) != hipSuccess && rc == FHE_OK) rc = FHE_ERR_HIP;
     (void)hipFree(ta);
@@ -285,8 +296,7 @@ int fhe_automorphism(uint64_t q, int64_t t, const uint64_t *in, uint64_t *out, s
     if (!pguard.ok) return FHE_ERR_HIP;
     if (q < 2 || !is_pow2(n) || n > (1u << 30) || ((!in || !out) && batch) || in == out) return FHE_ERR_INVALID;
     if (batch == 0) return FHE_OK;
-    const int64_t two_n = 2 * (int64_t)n;
-    const unsigned tt = (unsigned)(((t % two_n) + two_n) % two_n);  // t.rem_euclid(2n), avec.rs:38
+    const unsigned tt = rem_euclid_2n(t, n);  // avec.rs:38
     hipStream_t st = (hipStream_t)stream;
     Mirror mi(in, n * batch, mem, true, st), mo(out, n * batch, mem, true, st);  // copy_in: untouched slots keep `in` values
     if (mi.rc != FHE_OK || mo.rc != FHE_OK) return FHE_ERR_HIP;
@@ -302,8 +312,7 @@ int fhe_monomial_mul(uint64_t q, int64_t k, const uint64_t *in, uint64_t *out, s
     if (!pguard.ok) return FHE_ERR_HIP;
     if (q < 2 || !is_pow2(n) || n > (1u << 30) || ((!in || !out) && batch) || in == out) return FHE_ERR_INVALID;
     if (batch == 0) return FHE_OK;
-    const int64_t two_n = 2 * (int64_t)n;
-    const unsigned kk = (unsigned)(((k % two_n) + two_n) % two_n);  // rem_euclid(2n), ring.rs:305
+    const unsigned kk = rem_euclid_2n(k, n);  // ring.rs:305
     hipStream_t st = (hipStream_t)stream;
     Mirror mi(in, n * batch, mem, true, st), mo(out, n * batch, mem, false, st);
     if (mi.rc != FHE_OK || mo.rc != FHE_OK) return FHE_ERR_HIP;
@@ -343,8 +352,7 @@ static int gadget_entry(const fhe_ctx *ctx, const fhe_key *key, size_t index, bo
     const size_t n = size_t(1) << key->log_n;
     unsigned tt = 1;
     if (is_auto) {
-        const int64_t two_n = 2 * (int64_t)n;
-        tt = (unsigned)(((t % two_n) + two_n) % two_n);
+        tt = rem_euclid_2n(t, n);
         if ((tt & 1) == 0) return FHE_ERR_INVALID;  // only odd t are ring automorphisms
     }
     Mirror ma(ct_a, n * batch, mem, true, st), mb(ct_b, n * batch, mem, true, st);
@@ -360,44 +368,12 @@ static int gadget_entry(const fhe_ctx *ctx, const fhe_key *key, size_t index, bo
         return rc != FHE_OK ? rc : mb.sync_out(st);
     }
     const bool small = small_shape(key->log_n, batch);
-#define GP_LAUNCH_W(AR, WR)                                                                                                    \
-    rc = fhe::launch<fhe::gadget_product_kernel<AR, WR>>((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS, WR::LDS_BYTES, st, \
-                                                         ma.d, mb.d, (unsigned)batch, key_view(key, small), (unsigned)index, both ? 1u : 0u, \
-                                                         tt, ring_consts(ctx, 0));
-#define GP_LAUNCH(AR, LN) GP_LAUNCH_W(AR, fhe::WaveRing<LN>)
-#define GP_LAUNCH_BIG(AR, LN)                                                                \
-    {                                                                                        \
-        if (small) { typedef fhe::WaveRing<LN, 2> WS; GP_LAUNCH_W(AR, WS) }                  \
-        else { typedef fhe::WaveRing<LN> WD; GP_LAUNCH_W(AR, WD) }                           \
-    }
-    const int pmv = fhew_pm(ctx, key->log_n);
-    if (pmv == 54) {
-        switch (key->log_n) {
-            case 9: GP_LAUNCH(FHEW_POLICY54, 9) break;
-            case 10: GP_LAUNCH_BIG(FHEW_POLICY54, 10) break;
-            case 11: GP_LAUNCH_BIG(FHEW_POLICY54, 11) break;
-            default: return FHE_ERR_UNSUPPORTED;
-        }
-    } else if (pmv == 55) {
-        switch (key->log_n) {
-            case 9: GP_LAUNCH(FHEW_POLICY55, 9) break;
-            case 10: GP_LAUNCH_BIG(FHEW_POLICY55, 10) break;
-            case 11: GP_LAUNCH_BIG(FHEW_POLICY55, 11) break;
-            default: return FHE_ERR_UNSUPPORTED;
-        }
-    } else {
-        switch (key->log_n) {
-            case 7: GP_LAUNCH(fhe::ArithShoup, 7) break;
-            case 8: GP_LAUNCH(fhe::ArithShoup, 8) break;
-            case 9: GP_LAUNCH(fhe::ArithShoup, 9) break;
-            case 10: GP_LAUNCH_BIG(fhe::ArithShoup, 10) break;
-            case 11: GP_LAUNCH_BIG(fhe::ArithShoup, 11) break;
-            default: return FHE_ERR_UNSUPPORTED;
-        }
-    }
-#undef GP_LAUNCH_BIG
-#undef GP_LAUNCH_W
-#undef GP_LAUNCH
+    rc = with_fused(ctx, key->log_n, small, [&](auto pol, auto wr) {
+        using AR = typename decltype(pol)::type;
+        using WR = typename decltype(wr)::type;
+        return fhe::launch_teams<fhe::gadget_product_kernel<AR, WR>, WR>(batch, WR::LDS_BYTES, st, ma.d, mb.d, (unsigned)batch, key_view(key, small),
+                                                                          (unsigned)index, both ? 1u : 0u, tt, ring_consts(ctx));
+    });
     if (rc != FHE_OK) return rc;
     rc = ma.sync_out(st);
     return rc != FHE_OK ? rc : mb.sync_out(st);
@@ -523,9 +499,8 @@ int fhe_bootstrap_key_create(const fhe_ctx *ctx, const fhe_key *brk, const fhe_k
     const unsigned n = 1u << brk->log_n, q2 = 2 * n;
     std::vector<unsigned> t(w + 1), dlog(q2, 0xffffffffu);
     for (int i = 0; i <= w; ++i) {
-        int64_t v = ((ak_t[i] % (int64_t)q2) + q2) % q2;
-        if ((v & 1) == 0) return FHE_ERR_INVALID;
-        t[i] = (unsigned)v;
+        t[i] = rem_euclid_2n(ak_t[i], n);
+        if ((t[i] & 1) == 0) return FHE_ERR_INVALID;
     }
     unsigned x = 1;  // log_g_map (bootstrapping.rs:228-231): +-5^l -> l, l < n/2
     for (unsigned l = 0; l < n / 2; ++l) {
@@ -599,18 +574,17 @@ int fhe_blind_rotate(const fhe_bootstrap_key *bk, const uint64_t *lwe_a, const u
     const bool async = mem == FHE_MEM_DEVICE && !(ops_out && nops_out);
     int *d_err = async ? bk->d_status : (int *)(d_nops + batch);
     int rc = FHE_OK;
-    auto fail = [&](int code) { return code; };
-    if (!async && hipMemsetAsync(d_err, 0, sizeof(int), st) != hipSuccess) return fail(FHE_ERR_HIP);
+    if (!async && hipMemsetAsync(d_err, 0, sizeof(int), st) != hipSuccess) return FHE_ERR_HIP;
     rc = fhe::launch<fhe::blind_rotate_schedule_kernel>((unsigned)batch, 64, 3 * n_lwe * sizeof(unsigned), st, ma.d, (unsigned)n_lwe,
                                                          (unsigned)batch, (unsigned)n, (unsigned)bk->w, bk->d_dlog, d_ops, d_nops, max_ops, d_err);
-    if (rc != FHE_OK) return fail(rc);
+    if (rc != FHE_OK) return rc;
     if (bk->brk->composed) {
         // acc for the whole batch, then the walk as a host loop of S steps: S bounds every ciphertext's op count from (n_lwe, N, w)
         // alone (no device read): at most n_lwe external products, per half at most min(n_lwe, N/2 - 1) + floor((N/2 - 1) / w) + 1
         // automorphisms (one per run between occupied levels, plus the whole runs of w), and the one between the halves
         rc = fhe::launch<fhe::composed_br_init_kernel>(fhew_grid(n * batch), 256, 0, st, mf.d, f_stride, mb.d, moa.d, mob.d, (unsigned)n, batch,
                                                        (u64)ctx->q);
-        if (rc != FHE_OK) return fail(rc);
+        if (rc != FHE_OK) return rc;
         const size_t half = n / 2, lv = half - 1;
         const size_t per_half = (n_lwe < lv ? n_lwe : lv) + lv / (size_t)bk->w + 1;
         size_t steps = n_lwe + 2 * per_half + 1;
@@ -624,7 +598,7 @@ int fhe_blind_rotate(const fhe_bootstrap_key *bk, const uint64_t *lwe_a, const u
         O.max_ops = max_ops;
         const unsigned rows = (unsigned)(bk->brk->rows_per_ct > bk->ak->rows_per_ct ? bk->brk->rows_per_ct : bk->ak->rows_per_ct);
         rc = composed_run(ctx, O, log_n, rows, steps, moa.d, mob.d, batch, st);
-        if (rc != FHE_OK) return fail(rc);
+        if (rc != FHE_OK) return rc;
     } else {
         fhe::BlindRotateParams BR;
         const int split = split_g(bk, batch);
@@ -638,67 +612,39 @@ int fhe_blind_rotate(const fhe_bootstrap_key *bk, const uint64_t *lwe_a, const u
         BR.lwe_b = mb.d;
         BR.f = mf.d;
         BR.f_stride = f_stride;
-#define BR_LAUNCH_W(AR, WR)                                                                                                  \
-        rc = fhe::launch<fhe::blind_rotate_kernel<AR, WR>>((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS, WR::LDS_BYTES, st, \
-                                                           BR, moa.d, mob.d, (unsigned)batch, ring_consts(ctx, 0));
-#define BR_CASE(AR, LN) case LN: { typedef fhe::WaveRing<LN> WD; BR_LAUNCH_W(AR, WD) break; }
-#define BR_CASE_BIG(AR, LN)                                                                  \
-        case LN: {                                                                               \
-            if (small) { typedef fhe::WaveRing<LN, 2> WS; BR_LAUNCH_W(AR, WS) }                  \
-            else { typedef fhe::WaveRing<LN> WD; BR_LAUNCH_W(AR, WD) }                           \
-            break;                                                                               \
-        }
-        const int pmv = fhew_pm(ctx, log_n);
         if (split > 1) {
             // polled words | slabs, in a stream-ordered workspace of this call; the polled words are zeroed in front of the launch
             const size_t ctl_bytes = batch * fhe::SPLIT_CTL_WORDS * sizeof(unsigned);  // a multiple of 16 at the allocation's start
             const size_t slab_words = 2 * batch * (size_t)split * 2 * n;
             StreamWs sws(ctl_bytes + slab_words * sizeof(u64), st);
-            if (sws.rc != FHE_OK) return fail(sws.rc);
+            if (sws.rc != FHE_OK) return sws.rc;
             fhe::SplitWs S;
             S.ctl = sws.as<unsigned>();
             S.slabs = reinterpret_cast<u64 *>(sws.as<unsigned char>() + ctl_bytes);
             S.status = d_err;
-            if (hipMemsetAsync(S.ctl, 0, ctl_bytes, st) != hipSuccess) return fail(FHE_ERR_HIP);
-#define BRS_LAUNCH(AR, LN)                                                                                                          \
-            {                                                                                                                        \
-                typedef fhe::WaveRing<LN, 2> WS;                                                                                     \
-                rc = fhe::launch<fhe::blind_rotate_split_kernel<AR, WS>>((unsigned)(batch * split), WS::THREADS, fhe::split_lds_bytes<WS>(), st, \
-                                                                         BR, S, moa.d, mob.d, (unsigned)batch, split, ring_consts(ctx, 0)); \
-            }
-            if (pmv == 54) { if (log_n == 10) BRS_LAUNCH(FHEW_POLICY54, 10) else BRS_LAUNCH(FHEW_POLICY54, 11) }
-            else if (pmv == 55) { if (log_n == 10) BRS_LAUNCH(FHEW_POLICY55, 10) else BRS_LAUNCH(FHEW_POLICY55, 11) }
-            else { if (log_n == 10) BRS_LAUNCH(fhe::ArithShoup, 10) else BRS_LAUNCH(fhe::ArithShoup, 11) }
-#undef BRS_LAUNCH
-        } else if (pmv == 54) {
-            switch (log_n) {
-                BR_CASE(FHEW_POLICY54, 9) BR_CASE_BIG(FHEW_POLICY54, 10) BR_CASE_BIG(FHEW_POLICY54, 11)
-                default: return fail(FHE_ERR_UNSUPPORTED);
-            }
-        } else if (pmv == 55) {
-            switch (log_n) {
-                BR_CASE(FHEW_POLICY55, 9) BR_CASE_BIG(FHEW_POLICY55, 10) BR_CASE_BIG(FHEW_POLICY55, 11)
-                default: return fail(FHE_ERR_UNSUPPORTED);
-            }
+            if (hipMemsetAsync(S.ctl, 0, ctl_bytes, st) != hipSuccess) return FHE_ERR_HIP;
+            rc = with_fused<true>(ctx, log_n, true, [&](auto pol, auto wr) {
+                using AR = typename decltype(pol)::type;
+                using WS = typename decltype(wr)::type;
+                return fhe::launch<fhe::blind_rotate_split_kernel<AR, WS>>((unsigned)(batch * split), WS::THREADS, fhe::split_lds_bytes<WS>(), st, BR, S,
+                                                                           moa.d, mob.d, (unsigned)batch, split, ring_consts(ctx));
+            });
         } else {
-            switch (log_n) {
-                BR_CASE(fhe::ArithShoup, 7) BR_CASE(fhe::ArithShoup, 8) BR_CASE(fhe::ArithShoup, 9) BR_CASE_BIG(fhe::ArithShoup, 10)
-                BR_CASE_BIG(fhe::ArithShoup, 11)
-                default: return fail(FHE_ERR_UNSUPPORTED);
-            }
+            rc = with_fused(ctx, log_n, small, [&](auto pol, auto wr) {
+                using AR = typename decltype(pol)::type;
+                using WR = typename decltype(wr)::type;
+                return fhe::launch_teams<fhe::blind_rotate_kernel<AR, WR>, WR>(batch, WR::LDS_BYTES, st, BR, moa.d, mob.d, (unsigned)batch, ring_consts(ctx));
+            });
         }
-#undef BR_CASE_BIG
-#undef BR_LAUNCH_W
-#undef BR_CASE
-        if (rc != FHE_OK) return fail(rc);
+        if (rc != FHE_OK) return rc;
     }
     if (async) return FHE_OK;  // (the workspace is stream ordered: released after the kernels above)
     int h_err = 0;
-    if (hipMemcpyAsync(&h_err, d_err, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) return fail(FHE_ERR_HIP);
+    if (hipMemcpyAsync(&h_err, d_err, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) return FHE_ERR_HIP;
     if (ops_out && nops_out) {
         if (hipMemcpyAsync(ops_out, d_ops, batch * max_ops * sizeof(unsigned), hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipMemcpyAsync(nops_out, d_nops, batch * sizeof(unsigned), hipMemcpyDeviceToHost, st) != hipSuccess)
-            return fail(FHE_ERR_HIP);
+            return FHE_ERR_HIP;
     }
     rc = moa.sync_out(st);
     if (rc == FHE_OK) rc = mob.sync_out(st);

@@ -281,6 +281,9 @@ FHE_HEADER_KERNEL void sample_tdg_kernel(u64 *__restrict__ out, size_t count, do
         }
     }
 }
+// generator blocks that `count` values take: sample_tdg_kernel draws 4 per block, sample_u64_kernel 8 (the host's launch sizes and cursors)
+inline unsigned long long tdg_blocks(size_t count) { return (count + 3) / 4; }
+inline unsigned long long word_blocks(size_t count) { return (count + 7) / 8; }
 // util/src/misc/distribution.rs `binary()`: uniform bits, one per output word (scheme/tfhe/src/tlwe.rs:96-98 `sk_gen`)
 FHE_HEADER_KERNEL void sample_binary_kernel(u64 *__restrict__ out, size_t count, ChaChaKey K, unsigned long long first) {
     for (size_t blk = blockIdx.x * size_t(blockDim.x) + threadIdx.x; blk * 512 < count; blk += size_t(gridDim.x) * blockDim.x) {

@@ -5,7 +5,7 @@
 // element fetched from L2 serves TILE ciphertexts and no digit is recomputed per column (the one-thread-per-output kernels
 // this replaces did both: 1.96 ms per 1024 cfg3 ciphertexts, 8.5 % of a gate bootstrap).
 #pragma once
-#include "api_common.hpp"  // launch(): launch_key_switch_tiled
+#include "dispatch.hpp"  // launch(), with_int(): launch_key_switch_tiled
 #include "fhew_kernels.hpp"
 #include "torus_kernels.hpp"
 
@@ -147,11 +147,11 @@ template <class DEC>
 int launch_key_switch_tiled(const DEC &dec, const u64 *ct_a, const u64 *ct_b, size_t n_in, size_t n_out, size_t batch, const u64 *ksk_a,
                             const u64 *ksk_b, u64 *out_a, u64 *out_b, int tile, hipStream_t st) {
     const size_t lds = n_in * dec.P.d * tile * 4;
-#define KS_LAUNCH(T)                                                                                                             \
-    launch<lwe_key_switch_tiled<DEC, T>>((unsigned)((batch + T - 1) / T), KS_THREADS, lds, st, ct_a, ct_b, (unsigned)n_in, (unsigned)n_out, \
-                                         (unsigned)batch, ksk_a, ksk_b, dec, out_a, out_b)
-    return tile == 4 ? KS_LAUNCH(4) : tile == 2 ? KS_LAUNCH(2) : KS_LAUNCH(1);
-#undef KS_LAUNCH
+    return with_int<4, 2, 1>(tile, [&](auto t) {
+        constexpr int T = decltype(t)::value;
+        return launch<lwe_key_switch_tiled<DEC, T>>((unsigned)((batch + T - 1) / T), KS_THREADS, lds, st, ct_a, ct_b, (unsigned)n_in, (unsigned)n_out,
+                                                    (unsigned)batch, ksk_a, ksk_b, dec, out_a, out_b);
+    });
 }
 
 }  // namespace fhe

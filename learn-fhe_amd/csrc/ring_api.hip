@@ -11,6 +11,7 @@
 #include "../../include/fhe_ring.h"
 #include "api_common.hpp"
 #include "ctx.hpp"
+#include "dispatch.hpp"
 #include "ntt_kernels.hpp"
 #include "ntt14w.hpp"
 
@@ -27,48 +28,44 @@ int check_transform(const fhe_ctx *ctx, const void *a, size_t n, size_t batch) {
     return FHE_OK;
 }
 
-template <class A, int LOG_N, int LOG_E, int PPW, bool PFX = false>
-int launch_gen(bool inverse, const fhe::ModDesc *descs, unsigned n_desc, u64 *a, size_t subs, int pb, hipStream_t st, fhe::NttIo io) {
+// Which policy serves a modulus, by `pm` = the common bit length of pseudo-Mersenne eligible moduli (anything else: Shoup).  The lists
+// are what is instantiated:
+template <class F>
+int with_wave_policy(int pm, F &&f) { return fhe::with_policy<fhe::ArithDS, 60, 54, 55>(pm, f); }  // the wave-local transforms (ntt14w.hpp)
+template <class F>
+int with_gen_policy(int pm, F &&f) { return fhe::with_policy<fhe::ArithPM, 60, 54, 55>(pm, f); }  // the generic kernels from N = 2^10 up
+// the fused ring product has no 55-bit instantiation: 55-bit moduli take its Shoup kernel
+template <class F>
+int with_mul_policy(int pm, F &&f) { return fhe::with_policy<fhe::ArithDS, 60, 54>(pm, f); }
+// (55 bits: the reference's own parameter sets, scheme/fhew/examples/multi_key_uint8.rs:15-29, util/src/ring/rns.rs:373-386)
+
+// the generic kernels' shape per ring size, LOG_N -> (LOG_E, PPW): 16 coefficients per thread from N = 128 up; small rings pack many
+// polynomials into one 64..256-thread workgroup
+struct GenShape { int log_e, ppw; };
+constexpr GenShape GEN_SHAPE[14] = {{0, 0}, {1, 64}, {2, 64}, {3, 64}, {4, 64}, {3, 16}, {3, 16}, {4, 16}, {4, 16}, {4, 8}, {4, 4}, {4, 2}, {4, 1}, {4, 1}};
+
+template <class A, int LOG_N>
+int launch_gen(bool inverse, const fhe::ModDesc *descs, unsigned n_desc, u64 *a, size_t subs, hipStream_t st, fhe::NttIo io) {
+    constexpr int LOG_E = GEN_SHAPE[LOG_N].log_e, PPW = GEN_SHAPE[LOG_N].ppw;
     using C = fhe::NttCfg<LOG_N, LOG_E, PPW>;
     // measured on MI355X (tools/ntt_lab.hip): staging through LDS wins for the forward stores, direct 16-byte loads win
     // for the inverse
     const unsigned grid = (unsigned)((subs + PPW - 1) / PPW);
     if (inverse)
-        return fhe::launch<fhe::ntt_inv_kernel<A, LOG_N, LOG_E, PPW, PFX, true>>(grid, C::THREADS, C::LDS_BYTES, st, a, descs, n_desc, (unsigned)subs, pb, io);
-    return fhe::launch<fhe::ntt_fwd_kernel<A, LOG_N, LOG_E, PPW, PFX, false>>(grid, C::THREADS, C::LDS_BYTES, st, a, descs, n_desc, (unsigned)subs, pb, io);
+        return fhe::launch<fhe::ntt_inv_kernel<A, LOG_N, LOG_E, PPW, false, true>>(grid, C::THREADS, C::LDS_BYTES, st, a, descs, n_desc, (unsigned)subs, 0, io);
+    return fhe::launch<fhe::ntt_fwd_kernel<A, LOG_N, LOG_E, PPW, false, false>>(grid, C::THREADS, C::LDS_BYTES, st, a, descs, n_desc, (unsigned)subs, 0, io);
 }
-
-// (LOG_N -> LOG_E, PPW): 16 coefficients per thread from N = 128 up; small rings pack many polynomials
-// into one 64..256-thread workgroup
+// Shoup arithmetic at every size N = 2 .. 2^13, the pseudo-Mersenne policies from 2^10 up
 template <class A>
-int dispatch_small(bool inv, int log_n, const fhe::ModDesc *d, unsigned nd, u64 *a, size_t subs, hipStream_t st, fhe::NttIo io) {
-    switch (log_n) {
-        case 1: return launch_gen<A, 1, 1, 64>(inv, d, nd, a, subs, 0, st, io);
-        case 2: return launch_gen<A, 2, 2, 64>(inv, d, nd, a, subs, 0, st, io);
-        case 3: return launch_gen<A, 3, 3, 64>(inv, d, nd, a, subs, 0, st, io);
-        case 4: return launch_gen<A, 4, 4, 64>(inv, d, nd, a, subs, 0, st, io);
-        case 5: return launch_gen<A, 5, 3, 16>(inv, d, nd, a, subs, 0, st, io);
-        case 6: return launch_gen<A, 6, 3, 16>(inv, d, nd, a, subs, 0, st, io);
-        case 7: return launch_gen<A, 7, 4, 16>(inv, d, nd, a, subs, 0, st, io);
-        case 8: return launch_gen<A, 8, 4, 16>(inv, d, nd, a, subs, 0, st, io);
-        case 9: return launch_gen<A, 9, 4, 8>(inv, d, nd, a, subs, 0, st, io);
-        default: return FHE_ERR_UNSUPPORTED;
-    }
-}
-template <class A>
-int dispatch_large(bool inv, int log_n, const fhe::ModDesc *d, unsigned nd, u64 *a, size_t subs, int pb, hipStream_t st, fhe::NttIo io) {
-    switch (log_n) {
-        case 10: return launch_gen<A, 10, 4, 4>(inv, d, nd, a, subs, 0, st, io);
-        case 11: return launch_gen<A, 11, 4, 2>(inv, d, nd, a, subs, 0, st, io);
-        case 12: return launch_gen<A, 12, 4, 1>(inv, d, nd, a, subs, 0, st, io);
-        case 13: return launch_gen<A, 13, 4, 1>(inv, d, nd, a, subs, 0, st, io);
-        default: return FHE_ERR_UNSUPPORTED;
-    }
+int dispatch_gen(bool inv, int log_n, const fhe::ModDesc *d, unsigned nd, u64 *a, size_t subs, hipStream_t st, fhe::NttIo io) {
+    auto size = [&](auto ln) { return launch_gen<A, decltype(ln)::value>(inv, d, nd, a, subs, st, io); };
+    if constexpr (std::is_same_v<A, fhe::ArithShoup>) return fhe::with_int<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13>(log_n, size);
+    else return fhe::with_int<10, 11, 12, 13>(log_n, size);
 }
 
 // N = 2^14 (and the 2^14 sub-transforms of larger rings): the register-resident, wave-local kernels of ntt14w.hpp, two
-// workgroups per CU.  AF / AI: the arithmetic policy of each direction (measured, tools/ntt_lab2.hip, 4096 transforms at 60 bits:
-// forward 0.274 ms with the two-operand twiddles (ArithDS) against 0.300 with the 8-byte ones (ArithPM); inverse 0.296 against
+// workgroups per CU.  Both directions run the two-operand twiddles (measured, tools/ntt_lab2.hip, 4096 transforms at 60 bits:
+// forward 0.274 ms with ArithDS against 0.300 with the 8-byte ones (ArithPM); inverse 0.296 against
 // 0.320 since its first pass runs in diagonal form and nothing spills: ntt14w.hpp).
 inline bool limb_major_disabled() { return fhe::opt(fhe::OPT_NO_LIMB_MAJOR) != 0; }       // lab switch (api_common.hpp)
 inline bool wave_local_small_disabled() { return fhe::opt(fhe::OPT_NO_W12) != 0; }       // 2^12 / 2^13 on the generic kernels
@@ -76,76 +73,55 @@ inline bool wave_local_small_disabled() { return fhe::opt(fhe::OPT_NO_W12) != 0;
 inline size_t several_generations() { return size_t(8) * (size_t)fhe::current_cu_count(); }
 template <class... P>
 inline bool aligned16(const P *...p) { return ((... | (uintptr_t)p) % 16) == 0; }
-template <class AF, class AI, int R0 = 3>
-int launch14(bool inv, const fhe::ModDesc *d, unsigned nd, u64 *a, size_t subs, int pb, hipStream_t st, fhe::NttIo io) {
-    // several moduli: modulus-major dispatch order (ntt14w.hpp, sub_of_block)
-    const size_t polys = subs >> pb;
-    // (only launches of several generations of workgroups: when the whole launch is resident at once the order is irrelevant, and
-    // measured 3 % slower at cfg4 batch 8)
+// grid of a wave-local launch over `subs` blocks of `polys` polynomials.  Several moduli: modulus-major dispatch order (ntt14w.hpp,
+// sub_of_block) -- only launches of several generations of workgroups: when the whole launch is resident at once the order is
+// irrelevant, and measured 3 % slower at cfg4 batch 8
+inline dim3 grid14(unsigned nd, size_t polys, size_t subs) {
     const bool by_mod = nd > 1 && nd <= 65535 && polys % nd == 0 && subs >= several_generations() && !limb_major_disabled();
-    const dim3 grid = by_mod ? dim3((unsigned)(subs / nd), nd) : dim3((unsigned)subs);
+    return by_mod ? dim3((unsigned)(subs / nd), nd) : dim3((unsigned)subs);
+}
+// workgroup and LDS size of a wave-local kernel follow from R0 (ntt14w.hpp: pass 0 has R0 layers, 2^R0 waves; N = 2^(11 + R0))
+template <auto K, int R0>
+int launch_w14(const fhe::ModDesc *d, unsigned nd, u64 *a, size_t subs, int pb, hipStream_t st, fhe::NttIo io) {
+    return fhe::launch<K>(grid14(nd, subs >> pb, subs), fhe::w14::threads<R0>(), fhe::w14::lds_bytes<R0>(), st, a, d, nd, (unsigned)subs, pb, io);
+}
+template <class A, int R0>
+int launch14(bool inv, const fhe::ModDesc *d, unsigned nd, u64 *a, size_t subs, int pb, hipStream_t st, fhe::NttIo io) {
     // every polynomial is read and written 16 bytes per lane (ntt14w.hpp); since the pass-0 side deals coefficient pairs that
     // includes the source of an out-of-place forward at 2^12 .. 2^14
     if (!aligned16(a, io.mul, io.dst2)) return FHE_ERR_INVALID;
     if constexpr (R0 <= 3) {
         if (!inv && !aligned16(io.src, io.src2, io.src3, io.src4)) return FHE_ERR_INVALID;
     }
-#define W14(K) fhe::launch<K>(grid, fhe::w14::threads<R0>(), fhe::w14::lds_bytes<R0>(), st, a, d, nd, (unsigned)subs, pb, io)
-    if (!inv) return pb ? W14((fhe::ntt14w_fwd_kernel<AF, true, R0>)) : W14((fhe::ntt14w_fwd_kernel<AF, false, R0>));
-    if (pb) return io.mul ? W14((fhe::ntt14w_inv_kernel<AI, true, true, R0>)) : W14((fhe::ntt14w_inv_kernel<AI, true, false, R0>));
-    return io.mul ? W14((fhe::ntt14w_inv_kernel<AI, false, true, R0>)) : W14((fhe::ntt14w_inv_kernel<AI, false, false, R0>));
-#undef W14
+    return fhe::with_bool(pb != 0, [&](auto pfx) {
+        constexpr bool PFX = decltype(pfx)::value;
+        if (!inv) return launch_w14<fhe::ntt14w_fwd_kernel<A, PFX, R0>, R0>(d, nd, a, subs, pb, st, io);
+        return fhe::with_bool(io.mul != nullptr, [&](auto mul) {
+            return launch_w14<fhe::ntt14w_inv_kernel<A, PFX, decltype(mul)::value, R0>, R0>(d, nd, a, subs, pb, st, io);
+        });
+    });
 }
 
 // the fused ring product (ntt14w_mul_kernel): a <- inverse(forward(a) (.) io.mul), 2^13 .. 2^15
 template <class A, int R0>
 int launch_mul14(const fhe::ModDesc *d, unsigned nd, u64 *a, size_t subs, hipStream_t st, fhe::NttIo io) {
     if (!aligned16(a, io.mul)) return FHE_ERR_INVALID;  // 16 bytes per lane on both sides (ntt14w.hpp)
-    const bool by_mod = nd > 1 && nd <= 65535 && subs % nd == 0 && subs >= several_generations() && !limb_major_disabled();
-    const dim3 grid = by_mod ? dim3((unsigned)(subs / nd), nd) : dim3((unsigned)subs);
-    return fhe::launch<fhe::ntt14w_mul_kernel<A, R0>>(grid, fhe::w14::threads<R0>(), fhe::w14::lds_bytes<R0>(), st, a, d, nd, (unsigned)subs, 0, io);
-}
-template <class A>
-int dispatch_mul14(int log_n, const fhe::ModDesc *d, unsigned nd, u64 *a, size_t subs, hipStream_t st, fhe::NttIo io) {
-    switch (log_n) {
-        case 13: return launch_mul14<A, 2>(d, nd, a, subs, st, io);
-        case 14: return launch_mul14<A, 3>(d, nd, a, subs, st, io);
-        case 15: return launch_mul14<A, 4>(d, nd, a, subs, st, io);
-        default: return FHE_ERR_UNSUPPORTED;
-    }
+    return launch_w14<fhe::ntt14w_mul_kernel<A, R0>, R0>(d, nd, a, subs, 0, st, io);
 }
 
-// pm = common bit length of pseudo-Mersenne eligible moduli; kernels are instantiated for 60, 55 and 54 bits (anything else: Shoup)
 int sub_transform(bool inv, const fhe::ModDesc *d, unsigned nd, u64 *a, int log_n, size_t subs, int pb, int pm, hipStream_t st, fhe::NttIo io) {
     if (pb && log_n != 14) return FHE_ERR_UNSUPPORTED;
-    if (log_n == 15) {  // whole 2^15 rings in one pass over HBM (ntt14w.hpp, R0 = 4): one workgroup of 1024 threads per CU
-        if (pm == 60) return launch14<fhe::ArithDS<60>, fhe::ArithDS<60>, 4>(inv, d, nd, a, subs, 0, st, io);
-        if (pm == 54) return launch14<fhe::ArithDS<54>, fhe::ArithDS<54>, 4>(inv, d, nd, a, subs, 0, st, io);
-        if (pm == 55) return launch14<fhe::ArithDS<55>, fhe::ArithDS<55>, 4>(inv, d, nd, a, subs, 0, st, io);
-        return launch14<fhe::ArithShoup, fhe::ArithShoup, 4>(inv, d, nd, a, subs, 0, st, io);
-    }
-    if ((log_n == 12 || log_n == 13) && !wave_local_small_disabled()) {
-        // 2^12 / 2^13 rings in the wave-local form as well (R0 = 1 / 2: two / four waves, each owning a 2^11 block; eight / four
-        // workgroups per CU): at 60 bits forward 3.3 -> 4.0 and 2.8 -> 4.1 TB/s, inverse 2.9 -> 4.2 and 2.5 -> 3.9
-        if (pm == 60) return log_n == 13 ? launch14<fhe::ArithDS<60>, fhe::ArithDS<60>, 2>(inv, d, nd, a, subs, 0, st, io)
-                                         : launch14<fhe::ArithDS<60>, fhe::ArithDS<60>, 1>(inv, d, nd, a, subs, 0, st, io);
-        if (pm == 54) return log_n == 13 ? launch14<fhe::ArithDS<54>, fhe::ArithDS<54>, 2>(inv, d, nd, a, subs, 0, st, io)
-                                         : launch14<fhe::ArithDS<54>, fhe::ArithDS<54>, 1>(inv, d, nd, a, subs, 0, st, io);
-        if (pm == 55) return log_n == 13 ? launch14<fhe::ArithDS<55>, fhe::ArithDS<55>, 2>(inv, d, nd, a, subs, 0, st, io)
-                                         : launch14<fhe::ArithDS<55>, fhe::ArithDS<55>, 1>(inv, d, nd, a, subs, 0, st, io);
-        return log_n == 13 ? launch14<fhe::ArithShoup, fhe::ArithShoup, 2>(inv, d, nd, a, subs, 0, st, io)
-                           : launch14<fhe::ArithShoup, fhe::ArithShoup, 1>(inv, d, nd, a, subs, 0, st, io);
-    }
-    if (log_n < 10) return dispatch_small<fhe::ArithShoup>(inv, log_n, d, nd, a, subs, st, io);
-    if (pm == 60) return log_n == 14 ? launch14<fhe::ArithDS<60>, fhe::ArithDS<60>>(inv, d, nd, a, subs, pb, st, io)
-                                     : dispatch_large<fhe::ArithPM<60>>(inv, log_n, d, nd, a, subs, pb, st, io);
-    if (pm == 54) return log_n == 14 ? launch14<fhe::ArithDS<54>, fhe::ArithDS<54>>(inv, d, nd, a, subs, pb, st, io)
-                                     : dispatch_large<fhe::ArithPM<54>>(inv, log_n, d, nd, a, subs, pb, st, io);
-    // the reference's own 55-bit parameter sets (scheme/fhew/examples/multi_key_uint8.rs:15-29, util/src/ring/rns.rs:373-386)
-    if (pm == 55) return log_n == 14 ? launch14<fhe::ArithDS<55>, fhe::ArithDS<55>>(inv, d, nd, a, subs, pb, st, io)
-                                     : dispatch_large<fhe::ArithPM<55>>(inv, log_n, d, nd, a, subs, pb, st, io);
-    return log_n == 14 ? launch14<fhe::ArithShoup, fhe::ArithShoup>(inv, d, nd, a, subs, pb, st, io)
-                       : dispatch_large<fhe::ArithShoup>(inv, log_n, d, nd, a, subs, pb, st, io);
+    // Wave-local form (ntt14w.hpp), R0 = log_n - 11.  2^15: whole rings in one pass over HBM, one workgroup of 1024 threads per CU.
+    // 2^12 / 2^13 (two / four waves, each owning a 2^11 block; eight / four workgroups per CU): at 60 bits forward 3.3 -> 4.0 and
+    // 2.8 -> 4.1 TB/s, inverse 2.9 -> 4.2 and 2.5 -> 3.9
+    if (log_n == 14 || log_n == 15 || ((log_n == 12 || log_n == 13) && !wave_local_small_disabled()))
+        return with_wave_policy(pm, [&](auto pol) {
+            using A = typename decltype(pol)::type;
+            return fhe::with_int<1, 2, 3, 4>(log_n - 11, [&](auto r0) { return launch14<A, decltype(r0)::value>(inv, d, nd, a, subs, pb, st, io); });
+        });
+    return with_gen_policy(log_n < 10 ? 0 : pm, [&](auto pol) {  // (below 2^10: Shoup arithmetic only)
+        return dispatch_gen<typename decltype(pol)::type>(inv, log_n, d, nd, a, subs, st, io);
+    });
 }
 int sub_fwd(const fhe::ModDesc *d, unsigned nd, u64 *a, int log_n, size_t subs, int pb, int pm, hipStream_t st, fhe::NttIo io) {
     return sub_transform(false, d, nd, a, log_n, subs, pb, pm, st, io);
@@ -166,13 +142,10 @@ int ntt_fwd_multi(const ModDesc *descs, unsigned n_desc, u64 *a, int log_n, size
     if (io.src_group) return FHE_ERR_UNSUPPORTED;  // several sources: single-pass rings only (callers fall back to one launch each)
     const int pb = log_n - 14;
     const size_t cols = batch << 14;
-    int rc = FHE_OK;
-    switch (pb) {  // the opening pass reads the source, everything after it runs in place
-        case 1: rc = launch<ntt_big_fwd_pass<1>>(grid_for(cols), 256, 0, st, a, descs, n_desc, (unsigned)batch, log_n, io.src, io.src_mod); break;
-        case 2: rc = launch<ntt_big_fwd_pass<2>>(grid_for(cols), 256, 0, st, a, descs, n_desc, (unsigned)batch, log_n, io.src, io.src_mod); break;
-        case 3: rc = launch<ntt_big_fwd_pass<3>>(grid_for(cols), 256, 0, st, a, descs, n_desc, (unsigned)batch, log_n, io.src, io.src_mod); break;
-        default: return FHE_ERR_UNSUPPORTED;
-    }
+    // the opening pass reads the source, everything after it runs in place
+    const int rc = with_int<1, 2, 3>(pb, [&](auto p) {
+        return launch<ntt_big_fwd_pass<decltype(p)::value>>(grid_for(cols), 256, 0, st, a, descs, n_desc, (unsigned)batch, log_n, io.src, io.src_mod);
+    });
     if (rc != FHE_OK) return rc;
     return sub_fwd(descs, n_desc, a, 14, batch << pb, pb, pm, st, NttIo());
 }
@@ -186,13 +159,9 @@ int ntt_inv_multi(const ModDesc *descs, unsigned n_desc, u64 *a, int log_n, size
     int rc = sub_inv(descs, n_desc, a, 14, batch << pb, pb, pm, st, sub_io);
     if (rc != FHE_OK) return rc;
     const size_t cols = batch << 14;
-    switch (pb) {
-        case 1: rc = launch<ntt_big_inv_pass<1>>(grid_for(cols), 256, 0, st, a, descs, n_desc, (unsigned)batch, log_n); break;
-        case 2: rc = launch<ntt_big_inv_pass<2>>(grid_for(cols), 256, 0, st, a, descs, n_desc, (unsigned)batch, log_n); break;
-        case 3: rc = launch<ntt_big_inv_pass<3>>(grid_for(cols), 256, 0, st, a, descs, n_desc, (unsigned)batch, log_n); break;
-        default: return FHE_ERR_UNSUPPORTED;
-    }
-    return rc;
+    return with_int<1, 2, 3>(pb, [&](auto p) {
+        return launch<ntt_big_inv_pass<decltype(p)::value>>(grid_for(cols), 256, 0, st, a, descs, n_desc, (unsigned)batch, log_n);
+    });
 }
 
 // N = 2^15 with the outermost layer left to the caller (rns_kernels.hpp, the edge kernels of the key switch): what remains of
@@ -213,11 +182,11 @@ int ntt_inv_inner15(const ModDesc *descs, unsigned n_desc, u64 *a, size_t batch,
 int ntt_mul_multi(const ModDesc *descs, unsigned n_desc, u64 *a, int log_n, size_t batch, hipStream_t st, int pm, NttIo io) {
     if (!io.mul || io.src) return FHE_ERR_INVALID;
     const bool off = fhe::opt(fhe::OPT_NO_FUSED_MUL) != 0;  // lab switch (api_common.hpp)
-    if (log_n >= 13 && log_n <= 15 && !off) {
-        if (pm == 60) return dispatch_mul14<ArithDS<60>>(log_n, descs, n_desc, a, batch, st, io);
-        if (pm == 54) return dispatch_mul14<ArithDS<54>>(log_n, descs, n_desc, a, batch, st, io);
-        return dispatch_mul14<ArithShoup>(log_n, descs, n_desc, a, batch, st, io);
-    }
+    if (log_n >= 13 && log_n <= 15 && !off)
+        return with_mul_policy(pm, [&](auto pol) {
+            using A = typename decltype(pol)::type;
+            return with_int<2, 3, 4>(log_n - 11, [&](auto r0) { return launch_mul14<A, decltype(r0)::value>(descs, n_desc, a, batch, st, io); });
+        });
     int rc = ntt_fwd_multi(descs, n_desc, a, log_n, batch, st, pm);
     return rc != FHE_OK ? rc : ntt_inv_multi(descs, n_desc, a, log_n, batch, st, pm, io);
 }

@@ -10,6 +10,7 @@
 
 #include "api_common.hpp"
 #include "ctx.hpp"
+#include "dispatch.hpp"
 #include "rns_kernels.hpp"
 #include "keygen_kernels.hpp"
 
@@ -355,16 +356,6 @@ int fhe_rns_ctx_create(const uint64_t *qs, int L, const uint64_t *ps, int K, int
 }
 
 namespace {
-// the RNS kernels keep their limb vectors in registers: instantiate for the smallest bound that holds the source base
-#define RNS_BOUND(la, CALL)                                              \
-    do {                                                                 \
-        if ((la) == 8) { CALL(8, true); } /* the BASELINE shape: no limb predicates at all */ \
-        else if ((la) == 1) { CALL(1, true); } /* `rescale()` and K = 1 */ \
-        else if ((la) <= 4) { CALL(4, false); }                          \
-        else if ((la) <= 8) { CALL(8, false); }                          \
-        else if ((la) <= 16) { CALL(16, false); }                        \
-        else { CALL(32, false); }                                        \
-    } while (0)
 // grid of the limb-wise products: x over the coefficients of one polynomial, y over (ciphertext, limb) pairs
 struct PointwiseGrid {
     dim3 g;
@@ -382,22 +373,20 @@ int launch_extend(const fhe_rns_ctx *r, const u64 *in, size_t in_bs, u64 *out, s
                    u64 *copy = nullptr, size_t copy_bs = 0, bool to_qs = false, int c_lo = 0, int c_hi = -1, int r_lo = 0, int r_hi = -1) {
     const dim3 grid(grid_for(n * batch));
     const int la = to_qs ? r->K : r->L, lb = to_qs ? r->L : r->K;
-    int rc = FHE_OK;
     if (c_hi < 0) c_hi = la;
     if (r_hi < 0) r_hi = lb;
     if (r->pm) {
         const fhe::PmSrc &S = to_qs ? r->s_p2q_plain : r->s_q2p;
         const fhe::PmRows R = rows_from(to_qs ? r->r_p2q_plain : r->r_q2p, r_lo);
-#define CALL(M, F) rc = fhe::launch<fhe::rns_extend_pm_kernel<M, F>>(grid, 256, 0, st, in, in_bs, out, out_bs, n, batch, S, R, r_hi - r_lo, r->uni, copy, copy_bs, c_lo, c_hi)
-        RNS_BOUND(la, CALL);
-#undef CALL
-    } else {  // (the Shoup route has no limb subsets: callers check r->pm first)
-        const fhe::BaseConv &C = to_qs ? r->p2q : r->q2p;
-#define CALL(M, F) rc = fhe::launch<fhe::rns_extend_kernel<M, F>>(grid, 256, 0, st, in, in_bs, out, out_bs, n, batch, C, copy, copy_bs)
-        RNS_BOUND(la, CALL);
-#undef CALL
+        return fhe::with_limb_bound(la, [&](auto M, auto FULL) {
+            return fhe::launch<fhe::rns_extend_pm_kernel<M(), FULL()>>(grid, 256, 0, st, in, in_bs, out, out_bs, n, batch, S, R, r_hi - r_lo, r->uni, copy,
+                                                                       copy_bs, c_lo, c_hi);
+        });
     }
-    return rc;
+    const fhe::BaseConv &C = to_qs ? r->p2q : r->q2p;  // (the Shoup route has no limb subsets: callers check r->pm first)
+    return fhe::with_limb_bound(la, [&](auto M, auto FULL) {
+        return fhe::launch<fhe::rns_extend_kernel<M(), FULL()>>(grid, 256, 0, st, in, in_bs, out, out_bs, n, batch, C, copy, copy_bs);
+    });
 }
 // where a whole [batch][L+K][n] block keeps the limbs of a rescale (rns_kernels.hpp RescaleIn)
 fhe::RescaleIn rescale_in_block(const u64 *in, size_t in_bs, int L, int K, size_t n) {
@@ -413,20 +402,17 @@ int launch_rescale(const fhe_rns_ctx *r, bool last, const fhe::RescaleIn &I, u64
     const dim3 grid(grid_for(n * batch));
     const int k = last ? 1 : r->K, L = last ? r->L - 1 : r->L;
     if (q_hi < 0) q_hi = L;
-    int rc = FHE_OK;
     if (r->pm) {
         const fhe::PmSrc &S = last ? r->s_last : r->s_p2q;
         const fhe::PmRows R = rows_from(last ? r->r_last : r->r_resc, q_lo);
-#define CALL(M, F) rc = fhe::launch<fhe::rns_rescale_pm_kernel<M, F>>(grid, 256, 0, st, I, out, out_bs, addend, add_bs, n, batch, q_hi - q_lo, S, R, r->uni)
-        RNS_BOUND(k, CALL);
-#undef CALL
-    } else {
-        const fhe::RescaleConsts &R = last ? r->resc_last : r->resc;
-#define CALL(M, F) rc = fhe::launch<fhe::rns_rescale_kernel<M, F>>(grid, 256, 0, st, I.in_q, I.q_bs, out, out_bs, addend, add_bs, n, batch, R)
-        RNS_BOUND(k, CALL);
-#undef CALL
+        return fhe::with_limb_bound(k, [&](auto M, auto FULL) {
+            return fhe::launch<fhe::rns_rescale_pm_kernel<M(), FULL()>>(grid, 256, 0, st, I, out, out_bs, addend, add_bs, n, batch, q_hi - q_lo, S, R, r->uni);
+        });
     }
-    return rc;
+    const fhe::RescaleConsts &R = last ? r->resc_last : r->resc;
+    return fhe::with_limb_bound(k, [&](auto M, auto FULL) {
+        return fhe::launch<fhe::rns_rescale_kernel<M(), FULL()>>(grid, 256, 0, st, I.in_q, I.q_bs, out, out_bs, addend, add_bs, n, batch, R);
+    });
 }
 // the same two steps with the outermost transform layer of a 2^15 ring in them (rns_kernels.hpp); pseudo-Mersenne bases only
 int launch_extend_edge(const fhe_rns_ctx *r, const u64 *in, size_t in_bs, u64 *out, size_t out_bs, size_t n, size_t batch, hipStream_t st,
@@ -434,23 +420,19 @@ int launch_extend_edge(const fhe_rns_ctx *r, const u64 *in, size_t in_bs, u64 *o
     if (c_hi < 0) c_hi = r->L;
     if (r_hi < 0) r_hi = r->K;
     const fhe::PmRows R = rows_from(r->r_q2p, r_lo), RW = rows_from(r->r_q2p_w, r_lo);
-    int rc = FHE_OK;
-#define CALL(M, F) rc = fhe::launch<fhe::rns_extend_edge_pm_kernel<M, F>>(grid_for(n / 2 * batch), 256, 0, st, in, in_bs, out, out_bs, n, batch, r->s_q2p, R, \
-                                                                         RW, r_hi - r_lo, r->uni, c_lo, c_hi)
-    RNS_BOUND(r->L, CALL);
-#undef CALL
-    return rc;
+    return fhe::with_limb_bound(r->L, [&](auto M, auto FULL) {
+        return fhe::launch<fhe::rns_extend_edge_pm_kernel<M(), FULL()>>(grid_for(n / 2 * batch), 256, 0, st, in, in_bs, out, out_bs, n, batch, r->s_q2p, R, RW,
+                                                                        r_hi - r_lo, r->uni, c_lo, c_hi);
+    });
 }
 int launch_rescale_edge(const fhe_rns_ctx *r, const fhe::RescaleIn &I, u64 *out, size_t out_bs, const u64 *addend, size_t add_bs, size_t n,
                          size_t batch, hipStream_t st, int q_lo = 0, int q_hi = -1) {
     if (q_hi < 0) q_hi = r->L;
     const fhe::PmRows R = rows_from(r->r_resc_edge, q_lo);
-    int rc = FHE_OK;
-#define CALL(M, F) rc = fhe::launch<fhe::rns_rescale_edge_pm_kernel<M, F>>(grid_for(n / 2 * batch), 256, 0, st, I, out, out_bs, addend, add_bs, n, batch, \
-                                                                          q_hi - q_lo, r->s_p2q_sum, r->s_p2q_diff, R, r->uni)
-    RNS_BOUND(r->K, CALL);
-#undef CALL
-    return rc;
+    return fhe::with_limb_bound(r->K, [&](auto M, auto FULL) {
+        return fhe::launch<fhe::rns_rescale_edge_pm_kernel<M(), FULL()>>(grid_for(n / 2 * batch), 256, 0, st, I, out, out_bs, addend, add_bs, n, batch,
+                                                                         q_hi - q_lo, r->s_p2q_sum, r->s_p2q_diff, R, r->uni);
+    });
 }
 // lab switch NO_EDGE: the key switch keeps whole 2^15 transforms (A/B runs and the test that both routes agree bit for bit)
 bool edge_enabled() { return fhe::opt(fhe::OPT_NO_EDGE) == 0; }
@@ -825,8 +807,7 @@ int fhe_rns_rescale(const fhe_rns_ctx *r, const uint64_t *in, uint64_t *out, siz
 int fhe_rns_automorphism(const fhe_rns_ctx *r, int64_t t, const uint64_t *in, uint64_t *out, size_t n, size_t batch, fhe_mem mem, void *stream) {
     if (!r || !is_pow2(n) || (n >> 30) || ((!in || !out) && batch) || in == out) return FHE_ERR_INVALID;
     if (r->device < 0) return FHE_ERR_NO_DEVICE;
-    const int64_t two_n = 2 * (int64_t)n;
-    const unsigned tt = (unsigned)(((t % two_n) + two_n) % two_n);  // t.rem_euclid(2n), avec.rs:38
+    const unsigned tt = rem_euclid_2n(t, n);  // avec.rs:38
     if (!(tt & 1) && n > 1) return FHE_ERR_UNSUPPORTED;  // CKKS only ever uses 5^j and -1; an even t is not a permutation
     if (batch == 0) return FHE_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -846,8 +827,7 @@ int fhe_ckks_rotate(const fhe_rns_ctx *r, const fhe_ckks_key *key, int64_t t, ui
     if (!r || !key || key->rns != r || ((!ct_b || !ct_a) && batch)) return FHE_ERR_INVALID;
     if (r->device < 0) return FHE_ERR_NO_DEVICE;
     const size_t n = size_t(1) << key->log_n, L = r->L;
-    const int64_t two_n = 2 * (int64_t)n;
-    const unsigned tt = (unsigned)(((t % two_n) + two_n) % two_n);
+    const unsigned tt = rem_euclid_2n(t, n);
     if (!(tt & 1) && n > 1) return FHE_ERR_UNSUPPORTED;
     if (batch == 0) return FHE_OK;
     hipStream_t st = (hipStream_t)stream;

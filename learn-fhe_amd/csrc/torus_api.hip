@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "torus_ctx.hpp"
+#include "dispatch.hpp"
 #include "lwe_kernels.hpp"
 #include "keygen_kernels.hpp"
 
@@ -56,23 +57,11 @@ void build_host30(Host30 &H) {
 // the team shape of the torus kernels per ring degree: 4 coefficients per lane from N = 1024 up (the state of a CMUX -- accumulator,
 // difference, digit state, two unreduced sum pairs -- is heavier than FHEW's; measured at cfg5: 17.2-17.3 k gates/s against
 // 16.6-16.9 k with 8 per lane, same session, and the better shape for small batches as well)
-#ifndef FHE_TORUS_LOG_E
-#define FHE_TORUS_LOG_E 2
-#endif
 template <int LN>
-using TorusRing = fhe::WaveRing<LN, (LN <= 9 ? LN - 6 : FHE_TORUS_LOG_E)>;
+using TorusRing = fhe::WaveRing<LN, (LN <= 9 ? LN - 6 : 2)>;
 // the 30-bit path carries half the registers per coefficient: 8 per lane again (22.9 k against 21.8 k gates/s at cfg5)
 template <int LN>
 using TorusRing30 = fhe::WaveRing<LN, (LN <= 9 ? LN - 6 : 3)>;
-
-#define TORUS_DISPATCH(log_n, ...)                                         \
-    switch (log_n) {                                                       \
-        case 8: { constexpr int LN = 8; __VA_ARGS__; break; }              \
-        case 9: { constexpr int LN = 9; __VA_ARGS__; break; }              \
-        case 10: { constexpr int LN = 10; __VA_ARGS__; break; }            \
-        case 11: { constexpr int LN = 11; __VA_ARGS__; break; }            \
-        default: return FHE_ERR_UNSUPPORTED;                               \
-    }
 
 // fft64 mode: a team over the N / 2 complex slots of a polynomial, 4 slots per lane from N = 1024 up (two waves per SIMD)
 constexpr int TF_LOG_CAP = 11;
@@ -80,41 +69,45 @@ template <int LN>
 using TorusRingF = fhe::WaveRing<LN - 1, (LN - 1 <= 8 ? LN - 1 - 6 : 2)>;
 constexpr int TF_MIN_WAVES = 2;
 
+// f(Type<Ring<LN>>{}) for the ring sizes of the torus kernels, N = 256 .. 2048; Ring: TorusRing, TorusRing30 or TorusRingF
+template <template <int> class Ring, class F>
+int with_torus(int log_n, F &&f) {
+    return fhe::with_int<8, 9, 10, 11>(log_n, [&](auto ln) { return f(fhe::Type<Ring<decltype(ln)::value>>{}); });
+}
+
 int launch_cmux(const fhe_torus_ctx *t, const fhe_tggsw_key *key, size_t index, u64 *a, u64 *b, size_t batch, const u64 *rot,
                 size_t rot_stride, hipStream_t st) {
     const size_t n = size_t(1) << key->log_n;
     const size_t per = size_t(2 * key->d) * 2 * n;
     if (key->d_rowsf) {  // fft64 mode
         const double2 *frows = key->d_rowsf + index * (per / 2);
-        TORUS_DISPATCH(key->log_n, {
-            typedef TorusRingF<LN> WR;
-            return fhe::launch<fhe::torusf_cmux_kernel<WR, TF_MIN_WAVES>>((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS, fhe::TorusF<WR>::LDS_BYTES,
-                                                                          st, a, b, (unsigned)batch, frows, key->P, rot, rot_stride, (const double2 *)t->d_twf);
+        return with_torus<TorusRingF>(key->log_n, [&](auto wr) {
+            using WR = typename decltype(wr)::type;
+            return fhe::launch_teams<fhe::torusf_cmux_kernel<WR, TF_MIN_WAVES>, WR>(batch, fhe::TorusF<WR>::LDS_BYTES, st, a, b, (unsigned)batch, frows, key->P,
+                                                                                    rot, rot_stride, (const double2 *)t->d_twf);
         });
     }
     if (key->d_rowsx3) {  // exact, three key pieces through f64 transforms
         const double2 *xrows = key->d_rowsx3 + index * (per / 2) * 3;
-        TORUS_DISPATCH(key->log_n, {
-            typedef TorusRingF<LN> WR;
-            return fhe::launch<fhe::torusx3_cmux_kernel<WR, TF_MIN_WAVES>>((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS,
-                                                                           fhe::TorusX3<WR>::lds_bytes(2 * key->d), st, a, b, (unsigned)batch, xrows, key->P, rot,
-                                                                           rot_stride, (const double2 *)t->d_twf);
+        return with_torus<TorusRingF>(key->log_n, [&](auto wr) {
+            using WR = typename decltype(wr)::type;
+            return fhe::launch_teams<fhe::torusx3_cmux_kernel<WR, TF_MIN_WAVES>, WR>(batch, fhe::TorusX3<WR>::lds_bytes(2 * key->d), st, a, b, (unsigned)batch,
+                                                                                     xrows, key->P, rot, rot_stride, (const double2 *)t->d_twf);
         });
     }
     if (key->d_rows30) {  // three 30-bit primes
         const size_t plane = key->count * per;
-        TORUS_DISPATCH(key->log_n, {
-            typedef TorusRing30<LN> WR;
-            return fhe::launch<fhe::torus30_cmux_kernel<WR>>((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS, WR::TORUS_LDS_BYTES, st, a, b,
-                                                             (unsigned)batch, (const unsigned *)(key->d_rows30 + index * per), plane, key->P, rot, rot_stride,
-                                                             t->T30);
+        return with_torus<TorusRing30>(key->log_n, [&](auto wr) {
+            using WR = typename decltype(wr)::type;
+            return fhe::launch_teams<fhe::torus30_cmux_kernel<WR>, WR>(batch, WR::TORUS_LDS_BYTES, st, a, b, (unsigned)batch,
+                                                                       (const unsigned *)(key->d_rows30 + index * per), plane, key->P, rot, rot_stride, t->T30);
         });
     }
     const u64 *rows0 = key->d_rows[0] + index * per, *rows1 = key->d_rows[1] + index * per;
-    TORUS_DISPATCH(key->log_n, {
-        typedef TorusRing<LN> WR;
-        return fhe::launch<fhe::torus_cmux_kernel<WR>>((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS, WR::TORUS_LDS_BYTES, st, a, b,
-                                                       (unsigned)batch, rows0, rows1, key->P, rot, rot_stride, t->T);
+    return with_torus<TorusRing>(key->log_n, [&](auto wr) {
+        using WR = typename decltype(wr)::type;
+        return fhe::launch_teams<fhe::torus_cmux_kernel<WR>, WR>(batch, WR::TORUS_LDS_BYTES, st, a, b, (unsigned)batch, rows0, rows1, key->P, rot, rot_stride,
+                                                                 t->T);
     });
 }
 
@@ -308,20 +301,19 @@ int fhe_tggsw_prepare(const fhe_torus_ctx *t, int log_b, int d, const uint64_t *
     if (rc == FHE_OK && usex3) {
         if (hipMalloc((void **)&dstx3, 6 * rows * (n / 2) * sizeof(double2)) != hipSuccess) rc = FHE_ERR_HIP;
         if (rc == FHE_OK) {
-            TORUS_DISPATCH(log_n, {
-                typedef TorusRingF<LN> WR;
-                rc = fhe::launch<fhe::torusx3_key_prepare_kernel<WR>>((unsigned)((6 * rows + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS, fhe::TorusF<WR>::LDS_BYTES,
-                                                                      st, (const u64 *)src, (const u64 *)(src + words), rows, (const double2 *)t->d_twf, dstx3);
+            rc = with_torus<TorusRingF>(log_n, [&](auto wr) {
+                using WR = typename decltype(wr)::type;
+                return fhe::launch_teams<fhe::torusx3_key_prepare_kernel<WR>, WR>(6 * rows, fhe::TorusF<WR>::LDS_BYTES, st, (const u64 *)src,
+                                                                                  (const u64 *)(src + words), rows, (const double2 *)t->d_twf, dstx3);
             });
         }
     } else if (rc == FHE_OK && use30) {
         if (hipMalloc((void **)&dst30, 3 * 2 * words * sizeof(unsigned)) != hipSuccess) rc = FHE_ERR_HIP;
         for (int pi = 0; pi < 3 && rc == FHE_OK; ++pi) {
-            TORUS_DISPATCH(log_n, {
-                typedef TorusRing30<LN> WR;
-                rc = fhe::launch<fhe::torus30_key_prepare_kernel<WR>>((unsigned)((2 * rows + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS, WR::LDS_BYTES, st,
-                                                                      (const u64 *)src, (const u64 *)(src + words), rows, t->T30.descs + pi,
-                                                                      dst30 + size_t(pi) * 2 * words);
+            rc = with_torus<TorusRing30>(log_n, [&](auto wr) {
+                using WR = typename decltype(wr)::type;
+                return fhe::launch_teams<fhe::torus30_key_prepare_kernel<WR>, WR>(2 * rows, WR::LDS_BYTES, st, (const u64 *)src, (const u64 *)(src + words),
+                                                                                  rows, t->T30.descs + pi, dst30 + size_t(pi) * 2 * words);
             });
         }
     } else if (rc == FHE_OK) {
@@ -333,8 +325,11 @@ int fhe_tggsw_prepare(const fhe_torus_ctx *t, int log_b, int d, const uint64_t *
             if (rc != FHE_OK) break;
             rc = fhe::ntt_fwd_multi(t->d_descs + pi, 1, tmp, log_n, 2 * rows, st, 60);
             if (rc != FHE_OK) break;
-            TORUS_DISPATCH(log_n, rc = fhe::launch<fhe::key_permute_kernel<TorusRing<LN>>>(grid_for(words), 256, 0, st, (const u64 *)tmp,
-                                                                                          (const u64 *)(tmp + words), dst + size_t(pi) * 2 * words, rows, 60));
+            rc = with_torus<TorusRing>(log_n, [&](auto wr) {
+                using WR = typename decltype(wr)::type;
+                return fhe::launch<fhe::key_permute_kernel<WR>>(grid_for(words), 256, 0, st, (const u64 *)tmp, (const u64 *)(tmp + words),
+                                                                dst + size_t(pi) * 2 * words, rows, 60);
+            });
         }
     }
     if (hipStreamSynchronize(st) != hipSuccess && rc == FHE_OK) rc = FHE_ERR_HIP;
@@ -369,10 +364,10 @@ int fhe_tggsw_prepare_fft64(const fhe_torus_ctx *t, int log_b, int d, const uint
     if (ma.rc | mb.rc) return FHE_ERR_HIP;
     double2 *dst = nullptr;
     HIP_TRY(hipMalloc((void **)&dst, 2 * rows * (n / 2) * sizeof(double2)));
-    TORUS_DISPATCH(log_n, {
-        typedef TorusRingF<LN> WR;
-        rc = fhe::launch<fhe::torusf_key_prepare_kernel<WR>>((unsigned)((2 * rows + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS, fhe::TorusF<WR>::LDS_BYTES, st,
-                                                             (const u64 *)ma.d, (const u64 *)mb.d, rows, (const double2 *)t->d_twf, dst);
+    rc = with_torus<TorusRingF>(log_n, [&](auto wr) {
+        using WR = typename decltype(wr)::type;
+        return fhe::launch_teams<fhe::torusf_key_prepare_kernel<WR>, WR>(2 * rows, fhe::TorusF<WR>::LDS_BYTES, st, (const u64 *)ma.d, (const u64 *)mb.d, rows,
+                                                                         (const double2 *)t->d_twf, dst);
     });
     if (rc != FHE_OK || hipStreamSynchronize(st) != hipSuccess) { (void)hipFree(dst); return FHE_ERR_HIP; }
     fhe_tggsw_key *k = new (std::nothrow) fhe_tggsw_key();
@@ -432,8 +427,7 @@ int fhe_tglwe_rotate(const uint64_t *ct_a, const uint64_t *ct_b, size_t n, int64
     if (!pguard.ok) return FHE_ERR_HIP;
     if (!is_pow2(n) || (n >> 30) || ((!ct_a || !ct_b || !out_a || !out_b) && batch) || (batch && (ct_a == out_a || ct_b == out_b))) return FHE_ERR_INVALID;
     if (batch == 0) return FHE_OK;
-    const int64_t two_n = 2 * (int64_t)n;
-    const unsigned k = (unsigned)(((i % two_n) + two_n) % two_n);  // `X ^ i`: i.rem_euclid(2n) (util/src/ring.rs:380-386)
+    const unsigned k = rem_euclid_2n(i, n);  // `X ^ i` (util/src/ring.rs:380-386)
     hipStream_t st = (hipStream_t)stream;
     const size_t words = n * batch;
     Mirror ma(ct_a, words, mem, true, st), mb(ct_b, words, mem, true, st), moa(out_a, words, mem, false, st), mob(out_b, words, mem, false, st);
@@ -477,20 +471,20 @@ int fhe_tfhe_blind_rotate(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, cons
     // accumulator never leaves the registers of the team that owns the ciphertext
     int rc = FHE_OK;
     if (brk->d_rowsf) {  // fft64 mode
-        TORUS_DISPATCH(brk->log_n, {
-            typedef TorusRingF<LN> WR;
-            rc = fhe::launch<fhe::torusf_blind_rotate_kernel<WR, TF_MIN_WAVES>>((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS,
-                                                                                fhe::TorusF<WR>::LDS_BYTES, st, (const u64 *)mv.d, (const u64 *)ma.d,
-                                                                                (const u64 *)mb.d, (unsigned)n_lwe, (unsigned)batch, (const double2 *)brk->d_rowsf,
-                                                                                brk->P, (const double2 *)t->d_twf, moa.d, mob.d);
+        rc = with_torus<TorusRingF>(brk->log_n, [&](auto wr) {
+            using WR = typename decltype(wr)::type;
+            return fhe::launch_teams<fhe::torusf_blind_rotate_kernel<WR, TF_MIN_WAVES>, WR>(batch, fhe::TorusF<WR>::LDS_BYTES, st, (const u64 *)mv.d,
+                                                                                            (const u64 *)ma.d, (const u64 *)mb.d, (unsigned)n_lwe,
+                                                                                            (unsigned)batch, (const double2 *)brk->d_rowsf, brk->P,
+                                                                                            (const double2 *)t->d_twf, moa.d, mob.d);
         });
     } else if (brk->d_rowsx3) {  // exact, three key pieces through f64 transforms
-        TORUS_DISPATCH(brk->log_n, {
-            typedef TorusRingF<LN> WR;
-            rc = fhe::launch<fhe::torusx3_blind_rotate_kernel<WR, TF_MIN_WAVES>>((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS,
-                                                                                 fhe::TorusX3<WR>::lds_bytes(2 * brk->d), st, (const u64 *)mv.d, (const u64 *)ma.d,
-                                                                                 (const u64 *)mb.d, (unsigned)n_lwe, (unsigned)batch, (const double2 *)brk->d_rowsx3,
-                                                                                 brk->P, (const double2 *)t->d_twf, moa.d, mob.d);
+        rc = with_torus<TorusRingF>(brk->log_n, [&](auto wr) {
+            using WR = typename decltype(wr)::type;
+            return fhe::launch_teams<fhe::torusx3_blind_rotate_kernel<WR, TF_MIN_WAVES>, WR>(batch, fhe::TorusX3<WR>::lds_bytes(2 * brk->d), st,
+                                                                                             (const u64 *)mv.d, (const u64 *)ma.d, (const u64 *)mb.d,
+                                                                                             (unsigned)n_lwe, (unsigned)batch, (const double2 *)brk->d_rowsx3,
+                                                                                             brk->P, (const double2 *)t->d_twf, moa.d, mob.d);
         });
     } else if (brk->d_rows30) {  // three 30-bit primes
         const size_t plane = brk->count * size_t(2 * brk->d) * 2 * n;
@@ -499,27 +493,26 @@ int fhe_tfhe_blind_rotate(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, cons
         // (a digit of base 2^8 ranges over [-128, 128]: one value too many for a byte)
         const bool packed = brk->P.log_b <= 7 && 2 * brk->d <= 8 && brk->log_n >= 8 && fhe::opt(fhe::OPT_NO_PACKED_DIGITS) == 0;
         if (packed) {
-            TORUS_DISPATCH(brk->log_n, {
-                typedef TorusRing30<LN> WR;
-                rc = fhe::launch<fhe::torus30_blind_rotate_pk_kernel<WR>>((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS,
-                                                                          WR::torus_pk_lds_bytes(2 * brk->d), st, (const u64 *)mv.d, (const u64 *)ma.d,
-                                                                          (const u64 *)mb.d, (unsigned)n_lwe, (unsigned)batch, (const unsigned *)brk->d_rows30, plane,
-                                                                          brk->P, t->T30, moa.d, mob.d);
+            rc = with_torus<TorusRing30>(brk->log_n, [&](auto wr) {
+                using WR = typename decltype(wr)::type;
+                return fhe::launch_teams<fhe::torus30_blind_rotate_pk_kernel<WR>, WR>(batch, WR::torus_pk_lds_bytes(2 * brk->d), st, (const u64 *)mv.d,
+                                                                                      (const u64 *)ma.d, (const u64 *)mb.d, (unsigned)n_lwe, (unsigned)batch,
+                                                                                      (const unsigned *)brk->d_rows30, plane, brk->P, t->T30, moa.d, mob.d);
             });
         } else {
-            TORUS_DISPATCH(brk->log_n, {
-                typedef TorusRing30<LN> WR;
-                rc = fhe::launch<fhe::torus30_blind_rotate_kernel<WR>>((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS, WR::TORUS_LDS_BYTES, st,
-                                                                       (const u64 *)mv.d, (const u64 *)ma.d, (const u64 *)mb.d, (unsigned)n_lwe, (unsigned)batch,
-                                                                       (const unsigned *)brk->d_rows30, plane, brk->P, t->T30, moa.d, mob.d);
+            rc = with_torus<TorusRing30>(brk->log_n, [&](auto wr) {
+                using WR = typename decltype(wr)::type;
+                return fhe::launch_teams<fhe::torus30_blind_rotate_kernel<WR>, WR>(batch, WR::TORUS_LDS_BYTES, st, (const u64 *)mv.d, (const u64 *)ma.d,
+                                                                                   (const u64 *)mb.d, (unsigned)n_lwe, (unsigned)batch,
+                                                                                   (const unsigned *)brk->d_rows30, plane, brk->P, t->T30, moa.d, mob.d);
             });
         }
     } else {
-        TORUS_DISPATCH(brk->log_n, {
-            typedef TorusRing<LN> WR;
-            rc = fhe::launch<fhe::torus_blind_rotate_kernel<WR>>((unsigned)((batch + WR::TEAMS - 1) / WR::TEAMS), WR::THREADS, WR::TORUS_LDS_BYTES, st,
-                                                                 (const u64 *)mv.d, (const u64 *)ma.d, (const u64 *)mb.d, (unsigned)n_lwe, (unsigned)batch,
-                                                                 (const u64 *)brk->d_rows[0], (const u64 *)brk->d_rows[1], brk->P, t->T, moa.d, mob.d);
+        rc = with_torus<TorusRing>(brk->log_n, [&](auto wr) {
+            using WR = typename decltype(wr)::type;
+            return fhe::launch_teams<fhe::torus_blind_rotate_kernel<WR>, WR>(batch, WR::TORUS_LDS_BYTES, st, (const u64 *)mv.d, (const u64 *)ma.d,
+                                                                             (const u64 *)mb.d, (unsigned)n_lwe, (unsigned)batch, (const u64 *)brk->d_rows[0],
+                                                                             (const u64 *)brk->d_rows[1], brk->P, t->T, moa.d, mob.d);
         });
     }
     if (rc == FHE_OK) rc = moa.sync_out(st);
@@ -629,10 +622,8 @@ int fhe_tfhe_bootstrap(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, int ks_
 // ---- TFHE key material on the device -----------------------------------------------------
 }  // extern "C"
 namespace {
-inline unsigned long long tdg_blocks(size_t count) { return (count + 3) / 4; }
-inline unsigned long long word_blocks(size_t count) { return (count + 7) / 8; }
 int sample_tdg_dev(double std_dev, const fhe::ChaChaKey &K, unsigned long long first, u64 *out, size_t count, hipStream_t st) {
-    return fhe::launch<fhe::sample_tdg_kernel>(grid_for(tdg_blocks(count)), 256, 0, st, out, count, std_dev, K, first);
+    return fhe::launch<fhe::sample_tdg_kernel>(grid_for(fhe::tdg_blocks(count)), 256, 0, st, out, count, std_dev, K, first);
 }
 // scheme/tfhe/src/tglwe.rs:91-103 (k = 1) for `rows` ciphertexts on device buffers: a uniform, e <- tdg, b = a s + e + pt
 // (pt [pt_rows][n] cycled, or null = encryptions of zero); sk [n], binary
@@ -642,10 +633,10 @@ int tglwe_sk_encrypt_dev(const fhe_torus_ctx *t, const u64 *sk, const u64 *pt, s
     StreamWs we(count * sizeof(u64), st);
     if (we.rc != FHE_OK) return we.rc;
     u64 *e = we.as<u64>();
-    int rc = fhe::launch<fhe::sample_u64_kernel>(grid_for(word_blocks(count)), 256, 0, st, ct_a, count, K, *cursor);
-    *cursor += word_blocks(count);
+    int rc = fhe::launch<fhe::sample_u64_kernel>(grid_for(fhe::word_blocks(count)), 256, 0, st, ct_a, count, K, *cursor);
+    *cursor += fhe::word_blocks(count);
     if (rc == FHE_OK) rc = sample_tdg_dev(std_dev, K, *cursor, e, count, st);
-    *cursor += tdg_blocks(count);
+    *cursor += fhe::tdg_blocks(count);
     if (rc == FHE_OK && hipMemcpyAsync(ct_b, ct_a, count * sizeof(u64), hipMemcpyDeviceToDevice, st) != hipSuccess) rc = FHE_ERR_HIP;
     if (rc == FHE_OK) rc = torus_mul_dev(t, ct_b, sk, 1, log_n, rows, st);  // a binary key: |s_i| <= 1, far inside the exact range
     if (rc == FHE_OK) rc = fhe::launch<fhe::torus_add3_kernel>(grid_for(count), 256, 0, st, ct_b, (const u64 *)e, pt, count, pt ? pt_rows * n : 1);
@@ -700,8 +691,8 @@ int fhe_tlwe_sk_encrypt(const uint64_t *sk, const uint64_t *pt, size_t n, size_t
     StreamWs we(rows * sizeof(u64), st);
     if (we.rc != FHE_OK) return we.rc;
     const fhe::ChaChaKey K = fhe::call_key(rng, stream_id, fhe::RNG_TLWE_ENC);
-    int rc = fhe::launch<fhe::sample_u64_kernel>(grid_for(word_blocks(rows * n)), 256, 0, st, ma.d, rows * n, K, 0ull);
-    if (rc == FHE_OK) rc = sample_tdg_dev(std_dev, K, word_blocks(rows * n), we.as<u64>(), rows, st);
+    int rc = fhe::launch<fhe::sample_u64_kernel>(grid_for(fhe::word_blocks(rows * n)), 256, 0, st, ma.d, rows * n, K, 0ull);
+    if (rc == FHE_OK) rc = sample_tdg_dev(std_dev, K, fhe::word_blocks(rows * n), we.as<u64>(), rows, st);
     if (rc == FHE_OK)
         rc = fhe::launch<fhe::tlwe_encrypt_kernel>(grid_for(rows), 256, 0, st, (const u64 *)ma.d, (const u64 *)msk.d, (const u64 *)we.as<u64>(),
                                                    pt ? (const u64 *)mpt.d : nullptr, mb.d, n, rows, (const u64 *)nullptr, (size_t)1, 0, 0);
@@ -724,8 +715,8 @@ int fhe_tlwe_ksk_gen(int log_b, int d, const uint64_t *sk0, size_t n0, const uin
     StreamWs we(rows * sizeof(u64), st);
     if (we.rc != FHE_OK) return we.rc;
     const fhe::ChaChaKey K = fhe::call_key(rng, stream_id, fhe::RNG_TLWE_KSK);
-    int rc = fhe::launch<fhe::sample_u64_kernel>(grid_for(word_blocks(rows * n0)), 256, 0, st, ma.d, rows * n0, K, 0ull);
-    if (rc == FHE_OK) rc = sample_tdg_dev(std_dev, K, word_blocks(rows * n0), we.as<u64>(), rows, st);
+    int rc = fhe::launch<fhe::sample_u64_kernel>(grid_for(fhe::word_blocks(rows * n0)), 256, 0, st, ma.d, rows * n0, K, 0ull);
+    if (rc == FHE_OK) rc = sample_tdg_dev(std_dev, K, fhe::word_blocks(rows * n0), we.as<u64>(), rows, st);
     if (rc == FHE_OK)
         rc = fhe::launch<fhe::tlwe_encrypt_kernel>(grid_for(rows), 256, 0, st, (const u64 *)ma.d, (const u64 *)m0.d, (const u64 *)we.as<u64>(),
                                                    (const u64 *)nullptr, mb.d, n0, rows, (const u64 *)m1.d, n1, 64 - log_b * d, log_b);

@@ -74,9 +74,6 @@ const u64 *key_at(const fhe_tggswk_key *key, size_t index) {
     return key->d_eval + index * (k1 * key->P.d) * k1 * 2 * (size_t(1) << key->log_n);
 }
 
-inline unsigned long long tdg_blocks(size_t count) { return (count + 3) / 4; }
-inline unsigned long long word_blocks(size_t count) { return (count + 7) / 8; }
-
 // tglwe.rs:91-103 for `rows` ciphertexts on device buffers: every a_j uniform, e <- tdg, b = sum_j a_j s_j + e + pt
 // (pt [pt_rows][n] cycled or null); sk_eval [k][2][n]; ct [rows][k + 1][n]
 int tglwek_encrypt_dev(const fhe_torus_ctx *t, int k, const u64 *sk_eval, const u64 *pt, size_t pt_rows, u64 *ct, int log_n, size_t rows, double std_dev,
@@ -85,8 +82,8 @@ int tglwek_encrypt_dev(const fhe_torus_ctx *t, int k, const u64 *sk_eval, const 
     StreamWs ws((rows * n + DotWs::words(rows, k, 1, n)) * sizeof(u64), st);
     if (ws.rc != FHE_OK) return ws.rc;
     u64 *e = ws.as<u64>();
-    FHE_TRY(fhe::launch<fhe::sample_u64_kernel>(grid_for(word_blocks(words)), 256, 0, st, ct, words, K, 0ull));  // the b slots are overwritten below
-    FHE_TRY(fhe::launch<fhe::sample_tdg_kernel>(grid_for(tdg_blocks(rows * n)), 256, 0, st, e, rows * n, std_dev, K, word_blocks(words)));
+    FHE_TRY(fhe::launch<fhe::sample_u64_kernel>(grid_for(fhe::word_blocks(words)), 256, 0, st, ct, words, K, 0ull));  // the b slots are overwritten below
+    FHE_TRY(fhe::launch<fhe::sample_tdg_kernel>(grid_for(fhe::tdg_blocks(rows * n)), 256, 0, st, e, rows * n, std_dev, K, fhe::word_blocks(words)));
     fhe::TDecomp plain{};  // d = 0: the mask polynomials themselves
     DotSrc S; S.src = ct; S.polys = (unsigned)k; S.src_polys = (unsigned)k + 1;
     DotDst D; D.out = ct; D.out_polys = (unsigned)k + 1; D.out_off = (unsigned)k; D.e = e; D.pt = pt; D.pt_rows = pt ? pt_rows : 1;
@@ -184,8 +181,7 @@ int fhe_tglwek_rotate(const uint64_t *ct, int k, size_t n, int64_t i, uint64_t *
     if (!pguard.ok) return FHE_ERR_HIP;
     if (k < 1 || k > MAX_RANK || !is_pow2(n) || (n >> 30) || ((!ct || !out) && batch) || (batch && ct == out)) return FHE_ERR_INVALID;
     if (batch == 0) return FHE_OK;
-    const int64_t two_n = 2 * (int64_t)n;
-    const unsigned r = (unsigned)(((i % two_n) + two_n) % two_n);
+    const unsigned r = rem_euclid_2n(i, n);
     hipStream_t st = (hipStream_t)stream;
     const size_t polys = batch * (size_t)(k + 1);
     Mirror mi(ct, polys * n, mem, true, st), mo(out, polys * n, mem, false, st);

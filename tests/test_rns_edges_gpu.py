@@ -1,5 +1,5 @@
 """GPU parity tests of the RNS conversions (rns_api.hip, rns_kernels.hpp, pm_dot.hpp) at the edges of the limb counts and of the
-correction u = round(sum_i frac_i vs_i): every register bound MAXA = 1 / 4 / 8 / 16 / 32 of RNS_BOUND up to RNS_MAX_LIMBS = 32 on
+correction u = round(sum_i frac_i vs_i): every register bound MAXA = 1 / 4 / 8 / 16 / 32 of with_limb_bound up to RNS_MAX_LIMBS = 32 on
 both sides, target bases longer than MAXA, bases of pseudo-Mersenne primes of one width, of Shoup primes and of mixed widths, and
 residues built from chosen CRT integers: u = 0, u = la, and exact sums within 2^-900 of k + 1/2, where only the f64 rounding of the
 reference's sequential sum decides u.  Bit-exact against the oracle (oracle/cref.py)."""
