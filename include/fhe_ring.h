@@ -486,6 +486,37 @@ int fhe_ckks_decrypt(const fhe_rns_ctx *rns, const uint64_t *sk, const uint64_t 
 int fhe_ckks_mul_plain(const fhe_rns_ctx *rns, const uint64_t *pt, size_t pt_batch, const uint64_t *ct_b, const uint64_t *ct_a, uint64_t *out_b,
                        uint64_t *out_a, size_t n, size_t batch, fhe_mem mem, void *stream);
 
+/* ---- scheme/ckks/src/bootstrapping.rs:90-108 `Bootstrapping::mul_mat`: a diagonal-sparse plaintext matrix times a ciphertext by
+ * baby-step / giant-step (index sets: util/src/misc/matrix.rs:45-52, 125-150),
+ *     out = sum_i rotate_i( sum_{j in js(i)} mul_constant(diag_rot(i, j), rotate_j(ct)) ),          rotate_0 = identity,
+ * as one entry over a matrix prepared once.  Bit-identical to the composition of fhe_ckks_rotate, fhe_ckks_mul_plain and fhe_rns_add
+ * in the reference's order, with every operand transformed once: the sum over j runs in the evaluation domain on limbs 0 .. L-2 and
+ * is rescaled once per giant step (only the last limb keeps every term on its own).
+ *   rns_hi      the context of the input ciphertext, L >= 2 limbs;
+ *   rns_lo      the caller's context over the prefix qs[0 .. L-1) with the same ps on the same device (FHE_ERR_INVALID otherwise): the
+ *               level the giant steps and the result live on;
+ *   giant, baby the i of the split and the union of all j, each strictly ascending, 0 allowed (no rotation); the rotation amounts
+ *               5^i, 5^j mod 2n (`CkksParam::pow5`) are computed here;
+ *   present     [n_giant][n_baby], non-zero where (i, j) is a term; no term at all is FHE_ERR_INVALID;
+ *   diags       [terms][L][n], row-major over the present (i, j): `Ckks::encode(diag_rot(i, j))`, coefficient domain over rns_hi's qs
+ *               (the encoder and the rotation of the diagonal by -i stay with the caller).  Transformed once and kept on the device;
+ *   baby_keys   [n_baby] rotation keys for j prepared on rns_hi, NULL where j == 0;
+ *   giant_keys  [n_giant] rotation keys for i prepared on rns_lo (the same coefficient-domain key with limb L-1 removed: what the
+ *               reference's key switch uses at the lower level, rns.rs:148-158), NULL where i == 0.
+ * A missing key or one bound to another context is FHE_ERR_INVALID.  The keys are BORROWED: they and both contexts must outlive the
+ * matrix.  `mem` says where `diags` lives. */
+typedef struct fhe_ckks_diag_matrix fhe_ckks_diag_matrix;
+int fhe_ckks_diag_matrix_prepare(const fhe_rns_ctx *rns_hi, const fhe_rns_ctx *rns_lo, size_t n, const uint32_t *giant, int n_giant,
+                                 const uint32_t *baby, int n_baby, const uint8_t *present, const uint64_t *diags,
+                                 const fhe_ckks_key *const *baby_keys, const fhe_ckks_key *const *giant_keys, fhe_mem mem,
+                                 fhe_ckks_diag_matrix **out);
+void fhe_ckks_diag_matrix_destroy(fhe_ckks_diag_matrix *m);
+/* ct_b, ct_a [batch][L][n] over rns_hi, coefficient domain -> out_b, out_a [batch][L-1][n] over rns_lo; host or device memory; runs on
+ * `stream` with a stream-ordered workspace of 8 n batch (2 n_baby L + 2 (n_giant + 1) (L - 1) + 2 terms) bytes (+ the key switch's
+ * own).  batch == 0 returns FHE_OK. */
+int fhe_ckks_mul_mat(const fhe_ckks_diag_matrix *m, const uint64_t *ct_b, const uint64_t *ct_a, uint64_t *out_b, uint64_t *out_a, size_t batch,
+                     fhe_mem mem, void *stream);
+
 /* ---- TFHE key material, k = 1 (rank k: fhe_tglwek_sk_encrypt / fhe_tggswk_encrypt at the end).  Draws are counter based (ChaCha20, as above): reproducible per
  * (generator key, stream_id), checked at decode level like the reference's own tests (its draws are unseeded). */
 /* util/src/misc/distribution.rs:49-54 `tdg(std_dev)`: torus Gaussian noise (Box-Muller deviate, fractional part scaled by 2^64) */

@@ -175,6 +175,10 @@ def lib():
         L.fhe_ckks_pk_encrypt.argtypes = [vp, vp, vp, vp, sz, sz, vp, u64, vp, vp, ci, vp]
         L.fhe_ckks_decrypt.argtypes = [vp, vp, vp, vp, sz, sz, vp, ci, vp]
         L.fhe_ckks_mul_plain.argtypes = [vp, vp, sz, vp, vp, vp, vp, sz, sz, ci, vp]
+        L.fhe_ckks_diag_matrix_prepare.argtypes = [vp, vp, sz, u32p, ci, u32p, ci, C.c_char_p, vp, C.POINTER(vp), C.POINTER(vp), ci, C.POINTER(vp)]
+        L.fhe_ckks_diag_matrix_destroy.argtypes = [vp]
+        L.fhe_ckks_diag_matrix_destroy.restype = None
+        L.fhe_ckks_mul_mat.argtypes = [vp, vp, vp, vp, vp, sz, ci, vp]
         # any TGLWE rank k (torusk_api.hip)
         L.fhe_tggswk_prepare.argtypes = [vp, ci, ci, ci, vp, sz, sz, ci, C.POINTER(vp)]
         L.fhe_tggswk_key_destroy.argtypes = [vp]

@@ -503,6 +503,10 @@ class CkksKey:
         if h and L is not None and getattr(L, "lib", None):  # (module globals are gone at interpreter shutdown)
             L.lib().fhe_ckks_key_destroy(h)
 
+    @property
+    def handle(self):
+        return self._h
+
     def key_switch_(self, ct_b, ct_a):
         """scheme/ckks/src/ckks.rs:284-293, in place on [batch][L][n] b/a."""
         pb, cnt, mem, st = _buf(ct_b)
@@ -524,6 +528,63 @@ class CkksKey:
         batch = cnt // (self.rns.L * self.n)
         ob, oa = _like(ct0_b, (batch, self.rns.L - 1, self.n)), _like(ct0_b, (batch, self.rns.L - 1, self.n))
         L.check(L.lib().fhe_ckks_mul(self.rns.handle, self._h, p0b, p0a, p1b, p1a, _buf(ob)[0], _buf(oa)[0], batch, mem, st), "fhe_ckks_mul")
+        return ob, oa
+
+
+def bsgs_split(diag_indices):
+    """The baby-step / giant-step split `DiagSparseMatrix::bsgs` chooses (util/src/misc/matrix.rs:45-52, 125-150) for the diagonal
+    indices of a matrix -> (k, {i: [j, ...]}).  A diagonal d belongs to the giant step i = d - d % k and the baby step j = d % k; the
+    rotations a split needs are the distinct non-zero values among all i and all j (a value that is both counts once, one key serves
+    it).  The k in 1..=max(d) with the fewest of them is chosen, the smallest such k on a tie.  Indices without a non-zero diagonal
+    (where the reference has no k to choose from) give k = 1."""
+    ds = sorted(set(int(d) for d in diag_indices))
+    assert ds and ds[0] >= 0
+    best = None
+    for k in range(1, max(ds[-1], 1) + 1):
+        rotations = len(({d - d % k for d in ds} | {d % k for d in ds}) - {0})
+        if best is None or rotations < best[0]:
+            best = (rotations, k)
+    k = best[1]
+    split = {}
+    for d in ds:
+        split.setdefault(d - d % k, []).append(d % k)
+    return k, split
+
+
+class CkksDiagMatrix:
+    """scheme/ckks/src/bootstrapping.rs:90-108 `Bootstrapping::mul_mat` for one matrix, prepared once (include/fhe_ring.h
+    fhe_ckks_diag_matrix_prepare).  split: {i: [j, ...]} (bsgs_split); diags: [terms][L][n] = Ckks::encode(diag_rot(i, j)) over
+    rns_hi.qs in the order of sorted i, then sorted j; baby_keys {j: CkksKey on rns_hi}, giant_keys {i: CkksKey on rns_lo} for the
+    non-zero indices.  Keeps the contexts and the keys alive."""
+
+    def __init__(self, rns_hi: RnsContext, rns_lo: RnsContext, n, split, diags, baby_keys, giant_keys):
+        self.rns_hi, self.rns_lo, self.n = rns_hi, rns_lo, n
+        self.giant = sorted(split)
+        self.baby = sorted({j for js in split.values() for j in js})
+        self.terms = sum(len(set(js)) for js in split.values())
+        self._keys = (dict(baby_keys), dict(giant_keys))  # borrowed by the library
+        present = bytes(1 if j in split[i] else 0 for i in self.giant for j in self.baby)
+        handle = lambda keys, idx: keys[idx].handle if idx and keys.get(idx) is not None else None  # noqa: E731
+        bk = (C.c_void_p * len(self.baby))(*[handle(self._keys[0], j) for j in self.baby])
+        gk = (C.c_void_p * len(self.giant))(*[handle(self._keys[1], i) for i in self.giant])
+        pd, cnt, mem, _ = _buf(diags)
+        assert cnt == self.terms * rns_hi.L * n
+        self._h = C.c_void_p()
+        L.check(L.lib().fhe_ckks_diag_matrix_prepare(rns_hi.handle, rns_lo.handle, n, (C.c_uint32 * len(self.giant))(*self.giant), len(self.giant),
+                                                      (C.c_uint32 * len(self.baby))(*self.baby), len(self.baby), present, pd, bk, gk, mem,
+                                                      C.byref(self._h)), "fhe_ckks_diag_matrix_prepare")
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and L is not None and getattr(L, "lib", None):  # (module globals are gone at interpreter shutdown)
+            L.lib().fhe_ckks_diag_matrix_destroy(h)
+
+    def apply(self, ct_b, ct_a):
+        """[batch][L][n] over rns_hi -> (b, a) [batch][L-1][n] over rns_lo."""
+        pb, cnt, mem, st = _buf(ct_b)
+        batch = cnt // (self.rns_hi.L * self.n)
+        ob, oa = _like(ct_b, (batch, self.rns_hi.L - 1, self.n)), _like(ct_b, (batch, self.rns_hi.L - 1, self.n))
+        L.check(L.lib().fhe_ckks_mul_mat(self._h, pb, _buf(ct_a)[0], _buf(ob)[0], _buf(oa)[0], batch, mem, st), "fhe_ckks_mul_mat")
         return ob, oa
 
 
