@@ -394,7 +394,9 @@ int fhe_tfhek_bootstrap(const fhe_torus_ctx *t, const fhe_tggswk_key *brk, int k
  * SAME entry point on the same generator use different stream ids (equal ids reproduce the same mask and the same noise:
  * b1 - b2 = pt1 - pt2).  Pass FHE_STREAM_AUTO to let the generator number the calls itself (fresh id per call, from its own
  * counter, in the upper half of the id space: keep explicit ids below 2^63 when mixing both).  The reference draws from
- * `thread_rng()`; draws are not parity relevant, these entry points are validated at decrypt level and statistically.
+ * `thread_rng()`; draws are not parity relevant.  These entry points are validated at decrypt level, and row by row: with the secret
+ * key known, the exact noise of every coefficient they produce is checked against the sampler's support and law, the gadget term
+ * of every digit, limb and component exactly, and no two rows of a key may share noise (tests/test_keygen_rows_gpu.py).
  *   fhe_rng_create(key32, &rng): key32 = 32 bytes of caller entropy, or NULL = 32 bytes from the operating system (getrandom),
  *                                what the reference's thread_rng() is seeded with.
  *   fhe_rng_create_from_seed:    TESTS AND REPRODUCIBLE RUNS ONLY -- 64 bits of entropy stretched to a key (SplitMix64); keys made
@@ -418,7 +420,8 @@ int fhe_sample_dg(uint64_t q, double std_dev, int n_sigma, const fhe_rng *rng, u
 /* util/src/misc/decompose.rs:35-40 `power_up`: out[p][j] = in[p] * 2^(rounding_bits + j log_b) mod q, [polys][d][n] */
 int fhe_power_up(uint64_t q, int log_b, int d, const uint64_t *in, size_t n, size_t polys, uint64_t *out, fhe_mem mem, void *stream);
 /* scheme/fhew/src/rlwe.rs:146-156 `Rlwe::sk_encrypt` for `batch` plaintexts (pt [batch][n] or NULL = zeros): a uniform,
- * e <- dg(3.2, 6), b = a sk + e + pt.  sk [n]: the secret key as Zq values (`Zq::from_i64` of its coefficients). */
+ * e <- dg(3.2, 6), b = a sk + e + pt.  sk [n]: the secret key as Zq values (`Zq::from_i64` of its coefficients).  n = 1 is taken
+ * (Z_q itself, as in fhe_mul); the key and share producers below need n >= 2. */
 int fhe_rlwe_sk_encrypt(const fhe_ctx *ctx, const uint64_t *sk, const uint64_t *pt, size_t n, size_t batch, const fhe_rng *rng, uint64_t stream_id, uint64_t *ct_a, uint64_t *ct_b, fhe_mem mem, void *stream);
 /* rlwe.rs:237-249 `Rlwe::share_encrypt(param, a, sk, pt)`: b = a sk + e + pt for a GIVEN mask a -- what the multi-party protocol of
  * rlwe.rs:205-324 is made of: `pk_share_gen` (pt NULL, a = the common reference string), `ksk_share_gen` / `ak_share_gen` (one row per

@@ -49,8 +49,15 @@ int rlwe_sk_encrypt_dev(const fhe_ctx *ctx, const u64 *sk_eval, const u64 *pt, s
     *cursor += blocks_uniform(count);
     if (rc == FHE_OK) rc = sample_dg_dev(ctx->q, T, K, *cursor, e, count, st);
     *cursor += blocks_words(count);
+    // n = 1 (Z_q[X] / (X + 1) = Z_q, where no transform exists and sk_eval is sk itself): one product per ciphertext, which the LWE
+    // kernel forms at dimension 1 with the noise and the plaintext added, b[r] = a[r] sk[0] + pt[r] + e[r]
+    if (rc == FHE_OK && n == 1) {
+        if (pt && pt_rows != rows) return FHE_ERR_UNSUPPORTED;
+        return fhe::launch<fhe::lwe_encrypt_kernel>(grid_for(rows), 256, 0, st, (const u64 *)ct_a, sk_eval, (const u64 *)e, pt, ct_b, (size_t)1, rows,
+                                                    fhe::make_barrett(ctx->q), (const u64 *)nullptr, (size_t)1, 0, 0);
+    }
     // b = a * sk: forward transform of a out of place into b, inverse with the (broadcast) evaluation-domain key on its load
-    if (rc == FHE_OK && n > 1) {
+    if (rc == FHE_OK) {
         fhe::NttIo src;
         src.src = ct_a; src.src_mod = (unsigned)rows;
         rc = fhe::ntt_fwd_multi(ctx->d_desc, 1, ct_b, log_n, rows, st, ctx->pm_b, src);
@@ -59,8 +66,6 @@ int rlwe_sk_encrypt_dev(const fhe_ctx *ctx, const u64 *sk_eval, const u64 *pt, s
             mul.mul = sk_eval; mul.mul_div = (unsigned)rows; mul.mul_period = 1;
             rc = fhe::ntt_inv_multi(ctx->d_desc, 1, ct_b, log_n, rows, st, ctx->pm_b, mul);
         }
-    } else if (rc == FHE_OK) {
-        return FHE_ERR_UNSUPPORTED;
     }
     if (rc == FHE_OK) rc = fhe::launch<fhe::add3_kernel>(grid_for(count), 256, 0, st, ct_b, (const u64 *)e, pt, count, pt ? pt_rows * n : 1, (u64)ctx->q);
     return rc;
@@ -189,7 +194,8 @@ int fhe_power_up(uint64_t q, int log_b, int d, const uint64_t *in, size_t n, siz
 int fhe_rlwe_sk_encrypt(const fhe_ctx *ctx, const uint64_t *sk, const uint64_t *pt, size_t n, size_t batch, const fhe_rng *rng, uint64_t stream_id,
                         uint64_t *ct_a, uint64_t *ct_b, fhe_mem mem, void *stream) {
     if (!rng) return FHE_ERR_INVALID;
-    int rc = check_ring(ctx, n);
+    // n = 1 (Z_q[X] / (X + 1) = Z_q, as fhe_mul takes it): no transform exists at that size, a sk is one product per ciphertext
+    int rc = n == 1 ? (!ctx ? FHE_ERR_INVALID : ctx->device < 0 ? FHE_ERR_NO_DEVICE : FHE_OK) : check_ring(ctx, n);
     if (rc != FHE_OK) return rc;
     if (!sk || ((!ct_a || !ct_b) && batch)) return FHE_ERR_INVALID;
     if (batch == 0) return FHE_OK;
@@ -200,11 +206,15 @@ int fhe_rlwe_sk_encrypt(const fhe_ctx *ctx, const uint64_t *sk, const uint64_t *
     if (msk.rc | mpt.rc | ma.rc | mb.rc) return FHE_ERR_HIP;
     StreamWs wsk(n * sizeof(u64), st);
     if (wsk.rc != FHE_OK) return wsk.rc;
-    fhe::NttIo src;
-    src.src = msk.d; src.src_mod = 1;
-    rc = fhe::ntt_fwd_multi(ctx->d_desc, 1, wsk.as<u64>(), ilog2(n), 1, st, ctx->pm_b, src);
+    const u64 *sk_eval = msk.d;  // n = 1: the key is its own evaluation
+    if (n > 1) {
+        fhe::NttIo src;
+        src.src = msk.d; src.src_mod = 1;
+        rc = fhe::ntt_fwd_multi(ctx->d_desc, 1, wsk.as<u64>(), ilog2(n), 1, st, ctx->pm_b, src);
+        sk_eval = wsk.as<u64>();
+    }
     unsigned long long cursor = 0;
-    if (rc == FHE_OK) rc = rlwe_sk_encrypt_dev(ctx, wsk.as<u64>(), pt ? mpt.d : nullptr, batch, ma.d, mb.d, n, batch, fhe::call_key(rng, stream_id, fhe::RNG_RLWE_ENC), &cursor, st);
+    if (rc == FHE_OK) rc = rlwe_sk_encrypt_dev(ctx, sk_eval, pt ? mpt.d : nullptr, batch, ma.d, mb.d, n, batch, fhe::call_key(rng, stream_id, fhe::RNG_RLWE_ENC), &cursor, st);
     if (rc == FHE_OK) rc = ma.sync_out(st);
     if (rc == FHE_OK) rc = mb.sync_out(st);
     return rc;

@@ -6,8 +6,12 @@
 // (i mod 8) of ChaCha20 block (i div 8) (the block function of RFC 8439 in the ORIGINAL layout: 64-bit block counter, 64-bit nonce;
 // known-answer tested on the host, tests/test_abi_cpu.py) under a per-call key derived from an `fhe_rng`'s 256-bit key (the caller's
 // 32 bytes, or getrandom's), the call's stream id and a purpose tag (call_key): reproducible, order independent, and exactly as
-// strong as the key the caller supplied.  Draws are NOT parity-relevant (the reference's are unseeded): these producers are
-// validated at decrypt level and statistically.
+// strong as the key the caller supplied.  Draws are NOT parity-relevant (the reference's are unseeded).  What IS checked, beyond
+// decrypt level (tests/test_keygen_rows_gpu.py): with the secret key known the exact oracle gives a s and the gadget term, so the
+// noise of every coefficient of every row of every producer is recovered as an integer and held against the sampler's support
+// and law, rows against each other (no noise repeated, none zero), masks for range and repeats.  Of the grid-stride loops
+// below, those of the five samplers (uniform, u64, dg, zo, tdg), add3_kernel and ckks_finish_b_kernel are run past their first
+// sweep there; the others (sample_binary, power_up, the LWE / TLWE row kernels, the gadget and sum kernels) never reach the cap.
 #pragma once
 #include <atomic>
 #include <cmath>

@@ -930,25 +930,33 @@ def chacha20_block(key: bytes, nonce: int, counter: int) -> bytes:
     return out.raw
 
 
-def sample_uniform(q, seed, stream_id, like, shape):
-    """util/src/zq.rs:91-93: uniform in [0, q); `like` picks host (numpy) or device (torch) output."""
-    out = _like(like, tuple(shape))
+def _draw_into(out, like, shape):
+    """the buffer of a sampler: a fresh one of `shape` like `like`, or the caller's `out` (at least prod(shape) words; the draw
+    fills its front and touches nothing behind it) -> (out, pointer, count, mem, stream)"""
+    if out is None:
+        out = _like(like, tuple(shape))
     p, cnt, mem, st = _buf(out)
+    count = int(np.prod(tuple(shape), dtype=np.int64)) if shape is not None else cnt
+    assert count <= cnt
+    return out, p, count, mem, st
+
+
+def sample_uniform(q, seed, stream_id, like, shape, out=None):
+    """util/src/zq.rs:91-93: uniform in [0, q); `like` picks host (numpy) or device (torch) output."""
+    out, p, cnt, mem, st = _draw_into(out, like, shape)
     L.check(L.lib().fhe_sample_uniform(q, _rng(seed), stream_id, p, cnt, mem, st), "fhe_sample_uniform")
     return out
 
 
-def sample_torus(seed, stream_id, like, shape):
-    out = _like(like, tuple(shape))
-    p, cnt, mem, st = _buf(out)
+def sample_torus(seed, stream_id, like, shape, out=None):
+    out, p, cnt, mem, st = _draw_into(out, like, shape)
     L.check(L.lib().fhe_sample_torus(_rng(seed), stream_id, p, cnt, mem, st), "fhe_sample_torus")
     return out
 
 
-def sample_dg(q, std_dev, n_sigma, seed, stream_id, like, shape):
+def sample_dg(q, std_dev, n_sigma, seed, stream_id, like, shape, out=None):
     """util/src/misc/distribution.rs:23-46 `dg(std_dev, n)` as Zq values (q = 0: two's-complement integers)."""
-    out = _like(like, tuple(shape))
-    p, cnt, mem, st = _buf(out)
+    out, p, cnt, mem, st = _draw_into(out, like, shape)
     L.check(L.lib().fhe_sample_dg(q, float(std_dev), n_sigma, _rng(seed), stream_id, p, cnt, mem, st), "fhe_sample_dg")
     return out
 
@@ -1093,18 +1101,16 @@ def tglwe_rotate(ct_a, ct_b, n, i):
     return out_a, out_b
 
 
-def sample_tdg(std_dev, seed, stream_id, like, count):
+def sample_tdg(std_dev, seed, stream_id, like, count, out=None):
     """util/src/misc/distribution.rs:49-54"""
-    out = _like(like, (count,))
-    po, _, mem, st = _buf(out)
+    out, po, _, mem, st = _draw_into(out, like, (count,))
     L.check(L.lib().fhe_sample_tdg(std_dev, _rng(seed), stream_id, po, count, mem, st), "fhe_sample_tdg")
     return out
 
 
-def sample_binary(seed, stream_id, like, count):
+def sample_binary(seed, stream_id, like, count, out=None):
     """distribution.rs `binary()`"""
-    out = _like(like, (count,))
-    po, _, mem, st = _buf(out)
+    out, po, _, mem, st = _draw_into(out, like, (count,))
     L.check(L.lib().fhe_sample_binary(_rng(seed), stream_id, po, count, mem, st), "fhe_sample_binary")
     return out
 
@@ -1146,9 +1152,8 @@ def tggsw_encrypt(t, log_b, d, sk, pt, n, std_dev, seed, stream_id):
     return ra, rb
 
 
-def sample_zo(rho, seed, stream_id, like, count):
+def sample_zo(rho, seed, stream_id, like, count, out=None):
     """util/src/misc/distribution.rs:10-21 as two's-complement i64"""
-    out = _like(like, (count,))
-    po, _, mem, st = _buf(out)
+    out, po, _, mem, st = _draw_into(out, like, (count,))
     L.check(L.lib().fhe_sample_zo(rho, _rng(seed), stream_id, po, count, mem, st), "fhe_sample_zo")
     return out

@@ -52,13 +52,8 @@ def test_samplers(fhe, torch_cuda):
     ez = host(fhe.sample_dg(q, 3.2, 6, 11, 0, like, (n,)))
     assert np.array_equal(ez, np.where(e < 0, q - (-e), e).astype(np.uint64))
     # the weights are the reference's: cdf differences with the A&S 7.1.26 erf
-    def erf_as(x):
-        p, a1, a2, a3, a4, a5 = 0.3275911, 0.254829592, -0.284496736, 1.421413741, -1.453152027, 1.061405429
-        tt = 1.0 / (1.0 + p * abs(x))
-        pos = 1.0 - (((((a5 * tt + a4) * tt) + a3) * tt + a2) * tt + a1) * tt * math.exp(-x * x)
-        return pos if x >= 0 else -pos
-    cdf = lambda x: (1.0 + erf_as(x / (3.2 * math.sqrt(2)))) / 2.0  # noqa: E731
-    w = [cdf(i + 0.5) - cdf(i - 0.5) for i in range(-19, 20)]
+    from keygen_checks import dg_weights
+    w = dg_weights(3.2, 6)
     big = host(fhe.sample_dg(0, 3.2, 6, 12, 0, like, (1 << 20,))).view(np.int64)
     for i in (-6, -1, 0, 1, 3, 9):
         exp = w[i + 19] / sum(w) * (1 << 20)
