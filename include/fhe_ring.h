@@ -484,7 +484,7 @@ int fhe_ckks_pk_encrypt(const fhe_rns_ctx *rns, const uint64_t *pk_b, const uint
  * fewer limbs decrypts through an fhe_rns_ctx over that prefix of qs.) */
 int fhe_ckks_decrypt(const fhe_rns_ctx *rns, const uint64_t *sk, const uint64_t *ct_b, const uint64_t *ct_a, size_t n, size_t batch, uint64_t *pt,
                      fhe_mem mem, void *stream);
-/* ckks.rs:250-253 `Ckks::mul_constant` after its `encode` (host-side F256 arithmetic, out of scope): (pt * b, pt * a).rescale().  pt
+/* ckks.rs:250-253 `Ckks::mul_constant` after its `encode` (fhe_ckks_encode below): (pt * b, pt * a).rescale().  pt
  * [pt_batch][L][n] encoded plaintexts, pt_batch = 1 (one constant for the batch) or batch; ct [batch][L][n] -> out [batch][L-1][n]. */
 int fhe_ckks_mul_plain(const fhe_rns_ctx *rns, const uint64_t *pt, size_t pt_batch, const uint64_t *ct_b, const uint64_t *ct_a, uint64_t *out_b,
                        uint64_t *out_a, size_t n, size_t batch, fhe_mem mem, void *stream);
@@ -502,7 +502,8 @@ int fhe_ckks_mul_plain(const fhe_rns_ctx *rns, const uint64_t *pt, size_t pt_bat
  *               5^i, 5^j mod 2n (`CkksParam::pow5`) are computed here;
  *   present     [n_giant][n_baby], non-zero where (i, j) is a term; no term at all is FHE_ERR_INVALID;
  *   diags       [terms][L][n], row-major over the present (i, j): `Ckks::encode(diag_rot(i, j))`, coefficient domain over rns_hi's qs
- *               (the encoder and the rotation of the diagonal by -i stay with the caller).  Transformed once and kept on the device;
+ *               (fhe_ckks_encode makes them; the rotation of the diagonal by -i stays with the caller).  Transformed once and kept on the
+ *               device;
  *   baby_keys   [n_baby] rotation keys for j prepared on rns_hi, NULL where j == 0;
  *   giant_keys  [n_giant] rotation keys for i prepared on rns_lo (the same coefficient-domain key with limb L-1 removed: what the
  *               reference's key switch uses at the lower level, rns.rs:148-158), NULL where i == 0.
@@ -519,6 +520,45 @@ void fhe_ckks_diag_matrix_destroy(fhe_ckks_diag_matrix *m);
  * own).  batch == 0 returns FHE_OK. */
 int fhe_ckks_mul_mat(const fhe_ckks_diag_matrix *m, const uint64_t *ct_b, const uint64_t *ct_a, uint64_t *out_b, uint64_t *out_a, size_t batch,
                      fhe_mem mem, void *stream);
+
+/* ---- CKKS encode / decode: scheme/ckks/src/ckks.rs:186-213 `Ckks::encode` / `Ckks::decode` over scheme/ckks/src/sfft.rs:7-72, in
+ * double-double arithmetic (an unevaluated sum of two f64, about 106 bits) in place of the reference's 256-bit software floats
+ * (util/src/complex/f256.rs).  Complex slots travel as two f64 arrays: `*_hi` [batch][l][2] (re, im: the memory of a complex128
+ * array), l = n / 2, and `*_lo` of the same shape with the low words.  A `*_lo` may be NULL: as an input it means zeros, as an output
+ * only the f64-rounded value is kept.  Device-memory (FHE_MEM_DEVICE) `*_hi` / `*_lo` pointers must be 16-byte aligned (one complex
+ * element per access); host arrays have no such requirement.  Transforms agree with exact arithmetic to about 2^-100 of the largest
+ * slot. */
+typedef struct fhe_ckks_encoder fhe_ckks_encoder; /* one ring degree n on one device: the twiddle table of sfft.rs:57-72 `w()` */
+/* sfft.rs:57-72 `w(l)`: the 4 l powers of cis(pi / (2 l)) as dd pairs, each component within 2^-100 of the true value (computed per
+ * entry from the first octant, never by a running product), and the powers of 5 mod 4 l.  n = 2 .. 2^15 a power of two, anything else
+ * (n = 1, n > 2^15 included) FHE_ERR_INVALID.  device >= 0: tables uploaded to that GPU; device < 0: host-only, serves
+ * fhe_ckks_encoder_twiddles alone (every compute entry returns FHE_ERR_INVALID on it). */
+int fhe_ckks_encoder_create(size_t n, int device, fhe_ckks_encoder **out);
+void fhe_ckks_encoder_destroy(fhe_ckks_encoder *enc);
+/* the first `count` <= 4 l entries of the table: out [count][4] = (re_hi, re_lo, im_hi, im_lo) */
+int fhe_ckks_encoder_twiddles(const fhe_ckks_encoder *enc, double *out, size_t count);
+/* Waits for everything enqueued on `stream`, then FHE_ERR_INVALID if an asynchronous (device-memory) fhe_ckks_encode met a slot that
+ * is not finite or has |z scale| >= 2^126 (`BigInt::from(&F256)` would go on, f256.rs:213-239; here the coefficient is written as 0),
+ * or an fhe_ckks_decode a centred value beyond the f64 range, since the word was last cleared; else FHE_OK.  clear != 0 resets the
+ * word.  Host-memory calls report (and clear) it in their own return value.  An encoder has ONE word: a host-memory call, or a status
+ * query on one stream, also reports and clears what an asynchronous call on ANOTHER stream has set by then, and misses what it sets
+ * later -- callers that mix streams or memory kinds on one encoder and need the flag attributed use one encoder per stream (the
+ * tables are small) or query the status between the calls. */
+int fhe_ckks_encoder_status(const fhe_ckks_encoder *enc, void *stream, int clear);
+/* sfft.rs:21-35 `sifft` / sfft.rs:7-19 `sfft` (crate-private in the reference), in place on `batch` messages */
+int fhe_ckks_sifft(const fhe_ckks_encoder *enc, double *z_hi, double *z_lo, size_t batch, fhe_mem mem, void *stream);
+int fhe_ckks_sfft(const fhe_ckks_encoder *enc, double *z_hi, double *z_lo, size_t batch, fhe_mem mem, void *stream);
+/* ckks.rs:186-198 `Ckks::encode`: z = sifft(m); coefficient i <- BigInt::from(z_i.re * scale), coefficient l + i <- BigInt::from(z_i.im *
+ * scale) (the fraction dropped toward zero, f256.rs:213-239), reduced into every limb of rns's qs (`RnsRq::from_bigint`).  pt
+ * [batch][L][n], coefficient domain: what fhe_ckks_pk_encrypt, fhe_ckks_mul_plain and fhe_ckks_diag_matrix_prepare take.  `scale` is
+ * explicit because the reference's is qs.last() of the FULL chain (ckks.rs:27) whatever level `rns` is on.  enc and rns on different
+ * devices, scale == 0, a NULL m_hi or pt: FHE_ERR_INVALID. */
+int fhe_ckks_encode(const fhe_ckks_encoder *enc, const fhe_rns_ctx *rns, uint64_t scale, const double *m_hi, const double *m_lo, size_t batch,
+                    uint64_t *pt, fhe_mem mem, void *stream);
+/* ckks.rs:200-213 `Ckks::decode`: every coefficient's residues over rns's L limbs -> the centred integer in (-Q/2, Q/2]
+ * (`into_bigint`, exact multi-word arithmetic) -> dd -> / scale -> sfft.  pt [batch][L][n] as fhe_ckks_decrypt gives it. */
+int fhe_ckks_decode(const fhe_ckks_encoder *enc, const fhe_rns_ctx *rns, uint64_t scale, const uint64_t *pt, size_t batch, double *m_hi,
+                    double *m_lo, fhe_mem mem, void *stream);
 
 /* ---- TFHE key material, k = 1 (rank k: fhe_tglwek_sk_encrypt / fhe_tggswk_encrypt at the end).  Draws are counter based (ChaCha20, as above): reproducible per
  * (generator key, stream_id), checked at decode level like the reference's own tests (its draws are unseeded). */

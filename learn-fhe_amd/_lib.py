@@ -179,6 +179,17 @@ def lib():
         L.fhe_ckks_diag_matrix_destroy.argtypes = [vp]
         L.fhe_ckks_diag_matrix_destroy.restype = None
         L.fhe_ckks_mul_mat.argtypes = [vp, vp, vp, vp, vp, sz, ci, vp]
+        # CKKS encode / decode (ckks_encode_api.hip)
+        dblp = C.POINTER(C.c_double)
+        L.fhe_ckks_encoder_create.argtypes = [sz, ci, C.POINTER(vp)]
+        L.fhe_ckks_encoder_destroy.argtypes = [vp]
+        L.fhe_ckks_encoder_destroy.restype = None
+        L.fhe_ckks_encoder_twiddles.argtypes = [vp, dblp, sz]
+        L.fhe_ckks_encoder_status.argtypes = [vp, vp, ci]
+        L.fhe_ckks_sifft.argtypes = [vp, vp, vp, sz, ci, vp]
+        L.fhe_ckks_sfft.argtypes = [vp, vp, vp, sz, ci, vp]
+        L.fhe_ckks_encode.argtypes = [vp, vp, u64, vp, vp, sz, vp, ci, vp]
+        L.fhe_ckks_decode.argtypes = [vp, vp, u64, vp, sz, vp, vp, ci, vp]
         # any TGLWE rank k (torusk_api.hip)
         L.fhe_tggswk_prepare.argtypes = [vp, ci, ci, ci, vp, sz, sz, ci, C.POINTER(vp)]
         L.fhe_tggswk_key_destroy.argtypes = [vp]

@@ -24,6 +24,16 @@ def _buf(x):
     return C.c_void_p(x.ctypes.data), x.size, L.MEM_HOST, C.c_void_p(0)
 
 
+def _cbuf(x):
+    """_buf for complex128 slot arrays -> (pointer, complex element count, mem kind, stream handle)"""
+    if _is_torch(x):
+        import torch
+        assert x.is_cuda and x.is_contiguous() and x.dtype == torch.complex128
+        return C.c_void_p(x.data_ptr()), x.numel(), L.MEM_DEVICE, C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    assert isinstance(x, np.ndarray) and x.dtype == np.complex128 and x.flags["C_CONTIGUOUS"]
+    return C.c_void_p(x.ctypes.data), x.size, L.MEM_HOST, C.c_void_p(0)
+
+
 class NttContext:
     """One prime modulus (the reference's per-q twiddle cache entry, util/src/ring/fft/zq.rs:49-56)."""
 
@@ -586,6 +596,86 @@ class CkksDiagMatrix:
         ob, oa = _like(ct_b, (batch, self.rns_hi.L - 1, self.n)), _like(ct_b, (batch, self.rns_hi.L - 1, self.n))
         L.check(L.lib().fhe_ckks_mul_mat(self._h, pb, _buf(ct_a)[0], _buf(ob)[0], _buf(oa)[0], batch, mem, st), "fhe_ckks_mul_mat")
         return ob, oa
+
+
+class CkksEncoder:
+    """scheme/ckks/src/ckks.rs:186-213 `Ckks::encode` / `Ckks::decode` and scheme/ckks/src/sfft.rs:7-72 `sifft` / `sfft` in double-double
+    arithmetic for one ring degree n (include/fhe_ring.h fhe_ckks_encoder_*).  Slots are complex128 arrays [batch][n / 2] (numpy:
+    host path; torch CUDA tensors: device path, asynchronous) with an optional array of low words of the same shape.  device = -1
+    gives a host-only handle that serves twiddles() alone."""
+
+    def __init__(self, n, device=0):
+        self.n, self.l, self.device = n, n // 2, device
+        self._h = C.c_void_p()
+        L.check(L.lib().fhe_ckks_encoder_create(n, device, C.byref(self._h)), "fhe_ckks_encoder_create(n=%d)" % n)
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and L is not None and getattr(L, "lib", None):  # (module globals are gone at interpreter shutdown)
+            L.lib().fhe_ckks_encoder_destroy(h)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def twiddles(self, count=None):
+        """the first `count` (default all 4 l) powers of cis(pi / 2l) -> [count][4] = (re_hi, re_lo, im_hi, im_lo)"""
+        count = 4 * self.l if count is None else count
+        out = np.zeros((count, 4), dtype=np.float64)
+        L.check(L.lib().fhe_ckks_encoder_twiddles(self._h, out.ctypes.data_as(C.POINTER(C.c_double)), count), "fhe_ckks_encoder_twiddles")
+        return out
+
+    def status(self, like=None, clear=True):
+        """fhe_ckks_encoder_status: waits for the stream `like` lives on and raises FHE_ERR_INVALID if a device-memory encode / decode met
+        an out-of-range value since the word was last cleared."""
+        st = None
+        if like is not None and _is_torch(like):
+            import torch
+            st = C.c_void_p(torch.cuda.current_stream(like.device).cuda_stream)
+        L.check(L.lib().fhe_ckks_encoder_status(self._h, st, int(clear)), "fhe_ckks_encoder_status")
+
+    def _transform(self, name, z_hi, z_lo):
+        p, cnt, mem, st = _cbuf(z_hi)
+        assert cnt % self.l == 0
+        plo = _cbuf(z_lo)[0] if z_lo is not None else None
+        L.check(getattr(L.lib(), name)(self._h, p, plo, cnt // self.l, mem, st), name)
+        return z_hi if z_lo is None else (z_hi, z_lo)
+
+    def sifft(self, z_hi, z_lo=None):
+        """sfft.rs:21-35, in place on [batch][l] complex128 (and the low words)."""
+        return self._transform("fhe_ckks_sifft", z_hi, z_lo)
+
+    def sfft(self, z_hi, z_lo=None):
+        """sfft.rs:7-19, in place."""
+        return self._transform("fhe_ckks_sfft", z_hi, z_lo)
+
+    def encode(self, rns: "RnsContext", scale, m_hi, m_lo=None):
+        """ckks.rs:186-198 -> pt [batch][L][n] over rns.qs (uint64 numpy array or int64 CUDA tensor)."""
+        p, cnt, mem, st = _cbuf(m_hi)
+        batch = cnt // self.l
+        plo = _cbuf(m_lo)[0] if m_lo is not None else None
+        if _is_torch(m_hi):
+            import torch
+            pt = torch.empty((batch, rns.L, self.n), dtype=torch.int64, device=m_hi.device)
+        else:
+            pt = np.empty((batch, rns.L, self.n), dtype=np.uint64)
+        L.check(L.lib().fhe_ckks_encode(self._h, rns.handle, C.c_uint64(scale), p, plo, batch, _buf(pt)[0], mem, st), "fhe_ckks_encode")
+        return pt
+
+    def decode(self, rns: "RnsContext", scale, pt, want_lo=False):
+        """ckks.rs:200-213: pt [batch][L][n] -> slots [batch][l] complex128 (and their low words with want_lo)."""
+        p, cnt, mem, st = _buf(pt)
+        batch = cnt // (rns.L * self.n)
+        if _is_torch(pt):
+            import torch
+            mk = lambda: torch.empty((batch, self.l), dtype=torch.complex128, device=pt.device)  # noqa: E731
+        else:
+            mk = lambda: np.empty((batch, self.l), dtype=np.complex128)  # noqa: E731
+        hi = mk()
+        lo = mk() if want_lo else None
+        plo = _cbuf(lo)[0] if lo is not None else None
+        L.check(L.lib().fhe_ckks_decode(self._h, rns.handle, C.c_uint64(scale), p, batch, _cbuf(hi)[0], plo, mem, st), "fhe_ckks_decode")
+        return (hi, lo) if want_lo else hi
 
 
 class CkksShard:
