@@ -560,6 +560,60 @@ int fhe_ckks_encode(const fhe_ckks_encoder *enc, const fhe_rns_ctx *rns, uint64_
 int fhe_ckks_decode(const fhe_ckks_encoder *enc, const fhe_rns_ctx *rns, uint64_t scale, const uint64_t *pt, size_t batch, double *m_hi,
                     double *m_lo, fhe_mem mem, void *stream);
 
+/* ---- CKKS linear transforms `slot_to_coeff` / `coeff_to_slot`: scheme/ckks/src/bootstrapping.rs:23-31 `BootstrappingParam::new`,
+ * bootstrapping.rs:56-88 `key_gen` / `mul_mats`, over the factor matrices of scheme/ckks/src/sfft.rs:75-99 and the arithmetic of
+ * util/src/misc/matrix.rs:45-52, 71-83, 94-150 `DiagSparseMatrix`.  A PLAN holds the matrices of one direction in double-double on the
+ * encoder's device: `sfft_fmats(l)` (inverse = 0, slot_to_coeff) or `sifft_fmats(l)` (inverse != 0, coeff_to_slot), l = n / 2, filled by a
+ * kernel from the encoder's twiddle table and folded left to right over every chunk of r by one product launch each
+ * (matrix.rs:94-123).  Which diagonals a product has is structural, as in the reference: a diagonal whose values cancel stays.
+ * Diagonal INDICES ARE NORMALISED mod l.  The reference leaves index l (not 0) on an inverse chunk of a single factor (`inv` maps 0 to
+ * l, matrix.rs:77, and `product` of one item never reduces it) and then key-switches for the identity rotation 5^l = 1 mod 2n; here
+ * that diagonal is index 0 and costs no key switch: other noise, the same message.
+ *   r >= 1 the chunk size of bootstrapping.rs:25 (r >= log2 l: one dense matrix); r < 1, a NULL enc or out: FHE_ERR_INVALID;
+ *   n = 2 (l = 1, no factor at all) and a matrix of more than 2^26 elements (2 GiB): FHE_ERR_UNSUPPORTED.
+ * On a host-only encoder (device < 0) the plan answers the structure queries alone.  The encoder is BORROWED and must outlive the plan. */
+typedef struct fhe_ckks_linear_plan fhe_ckks_linear_plan;
+int fhe_ckks_linear_plan_create(const fhe_ckks_encoder *enc, int r, int inverse, fhe_ckks_linear_plan **out);
+void fhe_ckks_linear_plan_destroy(fhe_ckks_linear_plan *plan);
+/* depth = the number of matrices ceil(log2 l / r); n_rot = the size of `key_gen`'s rotation set for this direction (either may be NULL) */
+int fhe_ckks_linear_plan_info(const fhe_ckks_linear_plan *plan, int *depth, int *n_rot);
+/* bootstrapping.rs:61-64: the first `count` <= n_rot of the ascending union of the non-zero giant and baby steps of all matrices */
+int fhe_ckks_linear_plan_rotations(const fhe_ckks_linear_plan *plan, uint32_t *out, int count);
+/* matrix k (0 .. depth-1, the reference's list order): the number of diagonals, the k `DiagSparseMatrix::bsgs` chooses
+ * (matrix.rs:45-52: fewest distinct non-zero rotations, the smallest k on a tie; 1 where 0 is the only index) and the sizes of its split;
+ * then diag [n_diag] ascending, giant [n_giant] and baby [n_baby] ascending, present [n_giant][n_baby] (any may be NULL) */
+int fhe_ckks_linear_plan_matrix_info(const fhe_ckks_linear_plan *plan, int k, int *n_diag, uint32_t *bsgs_k, int *n_giant, int *n_baby);
+int fhe_ckks_linear_plan_matrix_split(const fhe_ckks_linear_plan *plan, int k, uint32_t *diag, uint32_t *giant, uint32_t *baby, uint8_t *present);
+/* the values of matrix k to HOST memory: out [n_diag][l][4] = (re_hi, re_lo, im_hi, im_lo), diagonal d at position c = dense[c][(c + d) mod l]
+ * (matrix.rs:87-91); FHE_ERR_INVALID on a host-only plan */
+int fhe_ckks_linear_plan_diags(const fhe_ckks_linear_plan *plan, int k, double *out);
+/* ckks.rs:174-184 `Ckks::rtk_gen(param, sk, j)`: j is taken mod l = n / 2 (j = 0 mod l: FHE_ERR_INVALID, the identity has no key),
+ * sk(X^(5^j)) is formed on the device from the i64 key (avec.rs:34-50) and handed to fhe_ckks_ksk_gen: ksk_b, ksk_a [L+K][n]. */
+int fhe_ckks_rtk_gen(const fhe_rns_ctx *rns, const uint64_t *sk, size_t n, int64_t j, const fhe_rng *rng, uint64_t stream_id, uint64_t *ksk_b,
+                     uint64_t *ksk_a, fhe_mem mem, void *stream);
+/* bootstrapping.rs:81-88 `mul_mats` prepared once: the matrices of `plan` applied last to first, step s (matrix depth-1-s) taking a
+ * ciphertext from levels[s] to levels[s + 1].
+ *   levels   [n_levels >= depth + 1] the caller's contexts over qs[0 .. L), qs[0 .. L-1), ..: the same ps, all on the device of the plan's
+ *            encoder (the rule of fhe_ckks_diag_matrix_prepare for rns_hi / rns_lo); L >= depth + 1;
+ *   scale    of `Ckks::encode` (ckks.rs:27: qs.last() of the full chain);
+ *   rot, ksk_b, ksk_a   n_rot rotation indices (taken mod l) and for each ONE coefficient-domain key [L+K][n] over levels[0]
+ *            (fhe_ckks_rtk_gen); as in the reference one key per index serves every level: the copy a step uses is the same rows with the
+ *            dropped q-limbs removed.  Baby steps of step s are prepared on levels[s], giant steps on levels[s + 1], each (level, index)
+ *            once.  `mem` says where the keys live.  Every index of fhe_ckks_linear_plan_rotations must be there.
+ * Every `diag_rot(i, j)[c] = diag_{i+j}[(c - i) mod l]` (bootstrapping.rs:101) is encoded on the device with the rotation folded into the
+ * encode kernels' loads: the prepared plaintexts have the bits fhe_ckks_encode gives for the rotated diagonal.  A missing index,
+ * mismatched contexts, too few levels, a host-only plan or a NULL argument: FHE_ERR_INVALID, nothing stays allocated.  The contexts are
+ * BORROWED; the plan and the caller's keys are not needed after the call. */
+typedef struct fhe_ckks_linear_transform fhe_ckks_linear_transform;
+int fhe_ckks_linear_transform_prepare(const fhe_ckks_linear_plan *plan, const fhe_rns_ctx *const *levels, int n_levels, uint64_t scale,
+                                      const uint32_t *rot, const uint64_t *const *ksk_b, const uint64_t *const *ksk_a, int n_rot, fhe_mem mem,
+                                      fhe_ckks_linear_transform **out);
+void fhe_ckks_linear_transform_destroy(fhe_ckks_linear_transform *t);
+/* ct_b, ct_a [batch][L][n] over levels[0] -> out_b, out_a [batch][L - depth][n] over levels[depth], host or device memory, on `stream`:
+ * bit-identical to chaining fhe_ckks_mul_mat by hand.  batch == 0 returns FHE_OK. */
+int fhe_ckks_linear_transform_apply(const fhe_ckks_linear_transform *t, const uint64_t *ct_b, const uint64_t *ct_a, uint64_t *out_b,
+                                    uint64_t *out_a, size_t batch, fhe_mem mem, void *stream);
+
 /* ---- TFHE key material, k = 1 (rank k: fhe_tglwek_sk_encrypt / fhe_tggswk_encrypt at the end).  Draws are counter based (ChaCha20, as above): reproducible per
  * (generator key, stream_id), checked at decode level like the reference's own tests (its draws are unseeded). */
 /* util/src/misc/distribution.rs:49-54 `tdg(std_dev)`: torus Gaussian noise (Box-Muller deviate, fractional part scaled by 2^64) */

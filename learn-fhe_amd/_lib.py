@@ -190,6 +190,20 @@ def lib():
         L.fhe_ckks_sfft.argtypes = [vp, vp, vp, sz, ci, vp]
         L.fhe_ckks_encode.argtypes = [vp, vp, u64, vp, vp, sz, vp, ci, vp]
         L.fhe_ckks_decode.argtypes = [vp, vp, u64, vp, sz, vp, vp, ci, vp]
+        # CKKS linear transforms (ckks_linear_api.hip)
+        L.fhe_ckks_linear_plan_create.argtypes = [vp, ci, ci, C.POINTER(vp)]
+        L.fhe_ckks_linear_plan_destroy.argtypes = [vp]
+        L.fhe_ckks_linear_plan_destroy.restype = None
+        L.fhe_ckks_linear_plan_info.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]
+        L.fhe_ckks_linear_plan_rotations.argtypes = [vp, u32p, ci]
+        L.fhe_ckks_linear_plan_matrix_info.argtypes = [vp, ci, C.POINTER(ci), u32p, C.POINTER(ci), C.POINTER(ci)]
+        L.fhe_ckks_linear_plan_matrix_split.argtypes = [vp, ci, u32p, u32p, u32p, C.c_char_p]
+        L.fhe_ckks_linear_plan_diags.argtypes = [vp, ci, dblp]
+        L.fhe_ckks_rtk_gen.argtypes = [vp, vp, sz, C.c_int64, vp, u64, vp, vp, ci, vp]
+        L.fhe_ckks_linear_transform_prepare.argtypes = [vp, C.POINTER(vp), ci, u64, u32p, C.POINTER(vp), C.POINTER(vp), ci, ci, C.POINTER(vp)]
+        L.fhe_ckks_linear_transform_destroy.argtypes = [vp]
+        L.fhe_ckks_linear_transform_destroy.restype = None
+        L.fhe_ckks_linear_transform_apply.argtypes = [vp, vp, vp, vp, vp, sz, ci, vp]
         # any TGLWE rank k (torusk_api.hip)
         L.fhe_tggswk_prepare.argtypes = [vp, ci, ci, ci, vp, sz, sz, ci, C.POINTER(vp)]
         L.fhe_tggswk_key_destroy.argtypes = [vp]

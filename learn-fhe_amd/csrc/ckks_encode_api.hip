@@ -10,20 +10,10 @@
 
 #include "api_common.hpp"
 #include "ckks_encode_kernels.hpp"
+#include "ckks_encoder.hpp"
 #include "dispatch.hpp"
 #include "modmath.hpp"
 #include "rns_ctx.hpp"
-
-struct fhe_ckks_encoder {
-    size_t n = 0;
-    unsigned l = 0;
-    int log_l = 0, device = -1;
-    std::vector<fhe::cdd> tw;     // [4 l]
-    std::vector<unsigned> pow5;   // [max(l / 2, 1)]
-    double4 *d_tw = nullptr;
-    unsigned *d_pow5 = nullptr;
-    int *d_status = nullptr;      // sticky device-side status word: fhe_ckks_encoder_status
-};
 
 namespace {
 using fhe::EncTables;
@@ -93,6 +83,14 @@ int transform(const fhe_ckks_encoder *e, double *z_hi, double *z_lo, size_t batc
     return rc != FHE_OK ? rc : ml.sync_out(st);
 }
 }  // namespace
+
+int fhe::ckks_encode_diag_rot(const fhe_ckks_encoder *e, const fhe_rns_ctx *rns, uint64_t scale, fhe::DiagRotIn src, size_t msgs, u64 *pt, hipStream_t st) {
+    if (pair_ok(e, rns, scale) != FHE_OK || !pt) return FHE_ERR_INVALID;
+    if (msgs == 0) return FHE_OK;
+    if (too_many(e, msgs, rns->L < 4 ? 4 : (size_t)rns->L)) return FHE_ERR_UNSUPPORTED;
+    const fhe::EncodeTail dst{pt, e->l, (unsigned)rns->L, rns->d_barrett, rns->resc.red_mu, fhe::ddm::from_u64(scale), e->d_status};
+    return run_sifft(e, src, dst, msgs, st);
+}
 
 extern "C" {
 

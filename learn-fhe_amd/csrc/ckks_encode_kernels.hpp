@@ -80,6 +80,18 @@ struct WsOut {
     __device__ __forceinline__ void store(size_t msg, unsigned i, cdd v) const { w[msg * l + i] = pack(v); }
 };
 
+// The source of the encode kernels for `diag_rot(i, j)` (bootstrapping.rs:101, ckks_linear_api.hip): message t is diagonal terms[t].x (slot) read at
+// (c - terms[t].y) mod l, so the rotation costs nothing and no rotated copy exists.
+struct DiagRotIn {
+    const double4 *diags;  // [n_diag][l]
+    const uint2 *terms;    // [msgs] (slot of diagonal i + j, i mod l)
+    unsigned l;
+    __device__ __forceinline__ cdd load(size_t msg, unsigned c) const {
+        const uint2 t = terms[msg];
+        return unpack(diags[(size_t)t.x * l + ((c - t.y) & (l - 1))]);
+    }
+};
+
 // ckks.rs:191-195: coefficient i <- BigInt::from(z_i.re * scale), coefficient l + i <- BigInt::from(z_i.im * scale), each reduced into
 // every limb (`RnsRq::from_bigint`); a negative v gives q - (|v| mod q).
 struct EncodeTail {

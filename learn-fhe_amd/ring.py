@@ -678,6 +678,91 @@ class CkksEncoder:
         return (hi, lo) if want_lo else hi
 
 
+class CkksLinearPlan:
+    """scheme/ckks/src/bootstrapping.rs:23-31 `BootstrappingParam::new` for one direction (include/fhe_ring.h
+    fhe_ckks_linear_plan_*): the chunked products of `sfft_fmats(l)` (inverse=False, slot_to_coeff) or `sifft_fmats(l)` (inverse=True,
+    coeff_to_slot), made on the encoder's device.  A plan on a host-only encoder answers the structure queries alone.  Diagonal
+    indices are normalised mod l."""
+
+    def __init__(self, enc: CkksEncoder, r, inverse=False):
+        self.enc, self.r, self.inverse = enc, r, bool(inverse)
+        self._h = C.c_void_p()
+        L.check(L.lib().fhe_ckks_linear_plan_create(enc.handle, r, int(self.inverse), C.byref(self._h)), "fhe_ckks_linear_plan_create")
+        depth, n_rot = C.c_int(), C.c_int()
+        L.check(L.lib().fhe_ckks_linear_plan_info(self._h, C.byref(depth), C.byref(n_rot)), "fhe_ckks_linear_plan_info")
+        self.depth = depth.value
+        rot = (C.c_uint32 * max(n_rot.value, 1))()
+        L.check(L.lib().fhe_ckks_linear_plan_rotations(self._h, rot, n_rot.value), "fhe_ckks_linear_plan_rotations")
+        self.rotations = [int(x) for x in rot[:n_rot.value]]
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and L is not None and getattr(L, "lib", None):  # (module globals are gone at interpreter shutdown)
+            L.lib().fhe_ckks_linear_plan_destroy(h)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def matrix(self, k):
+        """-> (diagonal indices, bsgs k, {i: [j, ...]}) of matrix k: the shape bsgs_split gives"""
+        nd, bk, ng, nb = C.c_int(), C.c_uint32(), C.c_int(), C.c_int()
+        L.check(L.lib().fhe_ckks_linear_plan_matrix_info(self._h, k, C.byref(nd), C.byref(bk), C.byref(ng), C.byref(nb)), "fhe_ckks_linear_plan_matrix_info")
+        diag, giant, baby = (C.c_uint32 * nd.value)(), (C.c_uint32 * ng.value)(), (C.c_uint32 * nb.value)()
+        present = C.create_string_buffer(ng.value * nb.value)
+        L.check(L.lib().fhe_ckks_linear_plan_matrix_split(self._h, k, diag, giant, baby, present), "fhe_ckks_linear_plan_matrix_split")
+        split = {int(giant[i]): [int(baby[j]) for j in range(nb.value) if present.raw[i * nb.value + j]] for i in range(ng.value)}
+        return [int(d) for d in diag], int(bk.value), split
+
+    def diags(self, k):
+        """the values of matrix k -> float64 [n_diag][l][4] = (re_hi, re_lo, im_hi, im_lo) on the host"""
+        out = np.zeros((len(self.matrix(k)[0]), self.enc.l, 4), dtype=np.float64)
+        L.check(L.lib().fhe_ckks_linear_plan_diags(self._h, k, out.ctypes.data_as(C.POINTER(C.c_double))), "fhe_ckks_linear_plan_diags")
+        return out
+
+
+def rtk_gen(rns: RnsContext, sk, n, j, seed, stream_id):
+    """scheme/ckks/src/ckks.rs:174-184 `Ckks::rtk_gen` -> (ksk_b, ksk_a) [L+K][n] for the rotation by j (taken mod n / 2)."""
+    ps, _, mem, st = _buf(sk)
+    kb, ka = _like(sk, (rns.L + rns.K, n)), _like(sk, (rns.L + rns.K, n))
+    L.check(L.lib().fhe_ckks_rtk_gen(rns.handle, ps, n, j, _rng(seed), stream_id, _buf(kb)[0], _buf(ka)[0], mem, st), "fhe_ckks_rtk_gen")
+    return kb, ka
+
+
+class CkksLinearTransform:
+    """scheme/ckks/src/bootstrapping.rs:81-88 `mul_mats` prepared once (include/fhe_ring.h fhe_ckks_linear_transform_*).  levels:
+    RnsContexts over qs[:L], qs[:L-1], .. (at least plan.depth + 1); keys {rotation index: (ksk_b, ksk_a)} over levels[0] as rtk_gen
+    gives them.  Keeps the contexts alive."""
+
+    def __init__(self, plan: CkksLinearPlan, levels, scale, keys):
+        self.plan, self.levels, self.n = plan, list(levels), plan.enc.n
+        idx = sorted(keys)
+        mem = {_buf(k)[2] for i in idx for k in keys[i]}
+        assert len(mem) <= 1
+        lv = (C.c_void_p * len(self.levels))(*[c.handle for c in self.levels])
+        kb = (C.c_void_p * max(len(idx), 1))(*[_buf(keys[i][0])[0] for i in idx])
+        ka = (C.c_void_p * max(len(idx), 1))(*[_buf(keys[i][1])[0] for i in idx])
+        self._h = C.c_void_p()
+        L.check(L.lib().fhe_ckks_linear_transform_prepare(plan.handle, lv, len(self.levels), C.c_uint64(scale), (C.c_uint32 * max(len(idx), 1))(*idx), kb, ka,
+                                                           len(idx), mem.pop() if mem else L.MEM_DEVICE, C.byref(self._h)),
+                "fhe_ckks_linear_transform_prepare")
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and L is not None and getattr(L, "lib", None):  # (module globals are gone at interpreter shutdown)
+            L.lib().fhe_ckks_linear_transform_destroy(h)
+
+    def apply(self, ct_b, ct_a):
+        """[batch][L][n] over levels[0] -> (b, a) [batch][L - depth][n] over levels[depth]."""
+        pb, cnt, mem, st = _buf(ct_b)
+        lv = self.levels[0].L
+        batch = cnt // (lv * self.n)
+        ob, oa = _like(ct_b, (batch, lv - self.plan.depth, self.n)), _like(ct_b, (batch, lv - self.plan.depth, self.n))
+        L.check(L.lib().fhe_ckks_linear_transform_apply(self._h, pb, _buf(ct_a)[0], _buf(ob)[0], _buf(oa)[0], batch, mem, st),
+                "fhe_ckks_linear_transform_apply")
+        return ob, oa
+
+
 class CkksShard:
     """One device's part of a limb-sharded key switch (include/fhe_ring.h fhe_ckks_shard_*): owns the
     q-limbs [q_lo, q_hi) and the p-limbs [p_lo, p_hi) of `key.rns`."""
