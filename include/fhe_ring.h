@@ -642,6 +642,38 @@ int fhe_tglwek_sk_encrypt(const fhe_torus_ctx *t, int k, const uint64_t *sk, con
 int fhe_tggswk_encrypt(const fhe_torus_ctx *t, int k, int log_b, int d, const uint64_t *sk, const uint64_t *pt, size_t n, size_t count,
                        double std_dev, const fhe_rng *rng, uint64_t stream_id, uint64_t *rows, fhe_mem mem, void *stream);
 
+/* ---- FHEW gate circuits: scheme/fhew/src/fhew/boolean.rs:134-176 and fhew/uint8.rs:50-163 (`FhewU8::wrapping_add` .. `div_rem`) build
+ * arithmetic out of `Fhew::{and, nand, or, nor, xor, xnor, majority}` (fhew.rs:59-67) and `Fhew::not` (fhew.rs:27-29), one gate
+ * bootstrap after the other.  Here such a composition is a NETLIST, prepared once and run in one call: the gates of one level, across
+ * the whole batch, form one batch of gate bootstraps, and nothing on the host sits between two levels. */
+typedef struct fhe_fhew_circuit fhe_fhew_circuit;
+enum { FHE_GATE_AND = 0, FHE_GATE_NAND = 1, FHE_GATE_OR = 2, FHE_GATE_NOR = 3, FHE_GATE_XOR = 4, FHE_GATE_XNOR = 5, FHE_GATE_MAJORITY = 6 };
+typedef struct { uint8_t op; uint8_t pad[3]; uint32_t in[3]; } fhe_fhew_gate;   /* op: FHE_GATE_AND, NAND, OR, NOR, XOR, XNOR, MAJORITY */
+#define FHE_WIRE_NOT 0x80000000u   /* on a wire reference: take `Fhew::not` of it (fhew.rs:27-29), a free linear step */
+/* Wire w < n_inputs is input w, wire n_inputs + g the output of gate g; a gate reads wires below its own only (topological order);
+ * the two-input ops ignore in[2]; outputs[] may repeat a wire, name an input and carry FHE_WIRE_NOT.  The netlist is validated
+ * (unknown op, forward or out-of-range reference, n_inputs == 0, n_outputs == 0, more than 2^24 wires: FHE_ERR_INVALID), gates no
+ * output depends on are dropped (the reference computes a few: the last carries of uint8.rs:65-76 and 119-131), and every live gate
+ * gets the level 1 + max(level of its inputs), inputs at level 0.  Host only: needs no device. */
+int  fhe_fhew_circuit_create(const fhe_fhew_gate *gates, size_t n_gates, size_t n_inputs,
+                             const uint32_t *outputs, size_t n_outputs, fhe_fhew_circuit **out);
+void fhe_fhew_circuit_destroy(fhe_fhew_circuit *c);
+/* levels, gates that are kept, gates of the widest level (each pointer may be NULL) */
+int  fhe_fhew_circuit_info(const fhe_fhew_circuit *c, size_t *n_levels, size_t *n_live_gates, size_t *max_width);
+int  fhe_fhew_circuit_levels(const fhe_fhew_circuit *c, uint32_t *level_of_gate /* [n_gates], 0 = dead */);
+/* The netlist on `batch` ciphertexts per wire, exactly the composition of fhew.rs:27-29 and 59-67 it describes: bit-identical to running
+ * the gates one by one through fhe_lwe_lincomb and fhe_fhew_bootstrap with addend = round(Q / 8).  Keys as for fhe_fhew_bootstrap.
+ * Per level ONE pass over (gates of the level) x batch ciphertexts: a front kernel (gather, signed sums, inversions, mod_switch to
+ * q_ks, per-ciphertext look-up rows), key switch, mod_switch_odd, blind rotation (the split route where fhe_blind_rotate_split says
+ * so), sample extract straight into the wire table.  The outputs must not overlap the inputs.  Device-memory calls are asynchronous
+ * and report the blind rotations' data-dependent conditions through fhe_bootstrap_key_status; host-memory calls mirror inputs and
+ * outputs once and report them in the return value.  Ring degree below 4: FHE_ERR_UNSUPPORTED (the look-up rows have runs of n / 4). */
+int fhe_fhew_circuit_run(const fhe_fhew_circuit *c, const fhe_bootstrap_key *bk, uint64_t q_ks, int ks_log_b, int ks_d,
+                         const uint64_t *lwe_ksk_a, const uint64_t *lwe_ksk_b,
+                         const uint64_t *in_a  /* [n_inputs][batch][N] */,  const uint64_t *in_b  /* [n_inputs][batch] */,
+                         uint64_t *out_a       /* [n_outputs][batch][N] */, uint64_t *out_b       /* [n_outputs][batch] */,
+                         size_t batch, fhe_mem mem, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

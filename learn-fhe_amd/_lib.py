@@ -115,6 +115,12 @@ def lib():
         L.fhe_lwe_key_switch.argtypes = [C.c_uint64, ci, ci, vp, vp, vp, vp, sz, sz, vp, vp, sz, ci, vp]
         L.fhe_rlwe_sample_extract.argtypes = [C.c_uint64, vp, vp, sz, sz, C.c_uint64, vp, vp, sz, ci, vp]
         L.fhe_fhew_bootstrap.argtypes = [vp, C.c_uint64, ci, ci, vp, vp, vp, sz, C.c_uint64, vp, vp, vp, vp, sz, ci, vp]
+        L.fhe_fhew_circuit_create.argtypes = [vp, sz, sz, u32p, sz, C.POINTER(vp)]
+        L.fhe_fhew_circuit_destroy.argtypes = [vp]
+        L.fhe_fhew_circuit_destroy.restype = None
+        L.fhe_fhew_circuit_info.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
+        L.fhe_fhew_circuit_levels.argtypes = [vp, u32p]
+        L.fhe_fhew_circuit_run.argtypes = [vp, vp, C.c_uint64, ci, ci, vp, vp, vp, vp, vp, vp, sz, ci, vp]
         L.fhe_torus_ctx_create.argtypes = [ci, C.POINTER(vp)]
         L.fhe_torus_ctx_destroy.argtypes = [vp]
         L.fhe_torus_ctx_destroy.restype = None
