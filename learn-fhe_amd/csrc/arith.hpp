@@ -365,7 +365,67 @@ struct ArithPM {
 struct DsK {
     u64 q, q2, q4;
     unsigned c, c2, pw;  // c, 2c, 2^(B-31)
+    u64 qk;              // DsLazy<B>::K q: the offset of the lazy forward butterfly's difference (a scalar register pair)
 };
+
+// Bounds of the LAZY forward butterfly (ArithDS<B>::ct_lazy: the product is never folded, only the additive operand is), exact in
+// 128-bit integers for EVERY modulus q = 2^B - c with 1 <= c <= CMAX and every 64-bit multiplicand:
+//     x_f = fold(x) or x;   R' = x_f + R(y, w);   X' = R';   Y' = 2 x_f + K q - R' = x_f + K q - R(y, w)
+//   * R(y, w) <= RMAX (twiddle words and the words of y at their maxima), so K = ceil(RMAX / QMIN) makes K q >= R for every admitted q;
+//   * a value that enters a layer below `in` leaves it below in + max(RMAX, K QMAX); it is folded first exactly where that would
+//     reach 2^64, and comes out of the fold below 2^B + (in >> B) CMAX.
+// SCHED is that recurrence run from canonical inputs over MAX_LAYERS layers: which layers fold their X inputs (the Y input, a
+// multiplicand, never needs it) and the bound of what enters each layer.  The static_asserts below are the proof that no
+// intermediate reaches 2^64; tests/ds_lazy_host_test.cpp checks that the code follows it.  At B = 60 the X inputs are folded before
+// every second layer from layer 2 on (x < q + 15c -> 8q -> 15q < 2^64 = 16q + 16c); at B <= 55 never within 16 layers.
+template <int B>
+struct DsLazy {
+    typedef unsigned __int128 u128;
+    static constexpr int BITS = B, MAX_LAYERS = 16;
+    static constexpr u128 CAP = u128(1) << 64;
+    static constexpr u128 CMAX = u128(1) << (B - 33);  // the pseudo-Mersenne eligibility bound itself (ring_api.hip, ctx_build_host)
+    static constexpr u128 QMIN = (u128(1) << B) - CMAX, QMAX = (u128(1) << B) - 1;
+    static constexpr u128 WORD = (u128(1) << 32) - 1;                                   // y0, y1
+    static constexpr u128 LO = (u128(1) << (B - 31)) - 1, HI = (u128(1) << 31) - 1;      // a0, b0 | a1, b1
+    static constexpr u128 S1MAX = 2 * HI * WORD, S0MAX = 2 * LO * WORD;
+    static constexpr u128 RMAX = S0MAX + WORD * (LO + 1) + WORD * 2 * CMAX;             // S0 + lo32(S1) 2^(B-31) + hi32(S1) 2c
+    static constexpr u64 K = (u64)((RMAX + QMIN - 1) / QMIN);
+    static constexpr u128 GROW = RMAX > K * QMAX ? RMAX : K * QMAX;
+    static constexpr u128 IN0 = QMAX - 1;  // kernel inputs are canonical: user data, the opening pass of a larger ring, the RNS edge kernels
+    static constexpr u128 fold_max(u128 in) { return ((u128(1) << B) - 1) + (in >> B) * CMAX; }
+    struct Sched {
+        bool fold[MAX_LAYERS];
+        u128 in[MAX_LAYERS + 1];  // in[L]: what enters layer L; in[n]: the outputs of an n-layer transform
+        bool ok;
+    };
+    static constexpr Sched make() {
+        Sched s{};
+        s.ok = true;
+        s.in[0] = IN0;
+        for (int l = 0; l < MAX_LAYERS; ++l) {
+            s.fold[l] = s.in[l] + GROW >= CAP;
+            const u128 xf = s.fold[l] ? fold_max(s.in[l]) : s.in[l];
+            s.in[l + 1] = xf + GROW;
+            if (s.in[l + 1] >= CAP) s.ok = false;
+        }
+        return s;
+    }
+    static constexpr Sched SCHED = make();
+    static constexpr bool fold_before(int layer) { return SCHED.fold[layer]; }
+    static constexpr u128 in_max(int layer) { return SCHED.in[layer]; }
+    // the outputs of an n-layer transform take ONE fold and ONE conditional subtraction to become canonical (canon_fwd)
+    static constexpr bool canon_ok(int n) { return fold_max(SCHED.in[n]) < 2 * QMIN; }
+    static_assert(B >= 34 && B <= 60, "pseudo-Mersenne widths");
+    static_assert(S1MAX < CAP, "S1 = a1 y0 + b1 y1 carries");
+    static_assert(2 * CMAX <= WORD && K * QMAX < CAP, "2c is a 32-bit multiplier, K q a 64-bit constant");
+    static_assert(K * QMIN >= RMAX, "K q must cover the largest raw product for every admitted q");
+    static_assert(SCHED.ok, "a layer's outputs reach 2^64 even with folded inputs");
+    static_assert(canon_ok(12) && canon_ok(13) && canon_ok(14) && canon_ok(15) && canon_ok(16), "canon_fwd needs more than one subtraction");
+};
+// the schedule as derived by hand for 60-bit moduli (K = 7, a fold before layers 2, 4, .., 14), and none at the narrower widths
+static_assert(DsLazy<60>::K == 7 && !DsLazy<60>::fold_before(0) && !DsLazy<60>::fold_before(1) && DsLazy<60>::fold_before(2) &&
+              !DsLazy<60>::fold_before(3) && DsLazy<60>::fold_before(4) && !DsLazy<60>::fold_before(13) && DsLazy<60>::fold_before(14), "60 bits");
+static_assert(DsLazy<55>::K == 7 && !DsLazy<55>::fold_before(15) && DsLazy<54>::K == 7 && !DsLazy<54>::fold_before(15), "54 / 55 bits");
 
 template <int B>
 struct ArithDS {
@@ -400,6 +460,8 @@ struct ArithDS {
         K k;
         k.m.q = D.q; k.m.q2 = 2 * D.q; k.m.q4 = 4 * D.q;
         k.m.c = D.pm_c; k.m.c2 = 2 * D.pm_c; k.m.pw = D.ds_pow;
+        k.m.qk = Lazy::K * D.q;
+        asm("" : "+s"(k.m.qk));  // a value the compiler cannot see into: as K * q it rebuilds the product in every butterfly (three instructions)
         k.tw = as_const(D.twd); k.twi = as_const(D.twdi);
         k.ninv = pb ? D.ds_one : D.ds_ninv[log_n_total];
         k.ninv_w = D.ds_ninv_w[log_n_total];
@@ -407,18 +469,19 @@ struct ArithDS {
         k.tw3i = as_const(D.twd3i); k.tw3_stride = D.twd3_stride;
         return k;
     }
-    // w y mod q, unreduced: < 2^(B+3) for any y
-    static __device__ __forceinline__ u64 mul_raw(u64 y, const uint4 &w, const DsK &m) {
+    typedef DsLazy<B> Lazy;
+    // add + w y mod q, unreduced: w y part < 2^(B+3) for any y (exactly: <= Lazy::RMAX); `add` rides on the first multiply-add of S0
+    static __host__ __device__ __forceinline__ u64 mul_raw(u64 y, const uint4 &w, const DsK &m, u64 add = 0) {
         const unsigned y0 = (unsigned)y, y1 = (unsigned)(y >> 32);
         const u64 s1 = (u64)w.y * y0 + (u64)w.w * y1;
-        const u64 s0 = (u64)w.x * y0 + (u64)w.z * y1;
+        const u64 s0 = ((u64)w.x * y0 + add) + (u64)w.z * y1;
         const u64 v = (u64)(unsigned)s1 * m.pw + s0;
         return (u64)(unsigned)(s1 >> 32) * m.c2 + v;
     }
     // x mod~ q: < 2^B + (x >> B) c
     // (written on the two words: as `(x & MASK) + (x >> B) * c` hipcc builds the masked value in a fresh register pair and pays a
     // v_mov per fold -- 224 of them in a 2^14 transform)
-    static __device__ __forceinline__ u64 fold1(u64 x, const DsK &m) {
+    static __host__ __device__ __forceinline__ u64 fold1(u64 x, const DsK &m) {
         const unsigned hi = (unsigned)(x >> 32), h = hi >> (B - 32);
         const u64 base = ((u64)(hi & (unsigned)(MASK >> 32)) << 32) | (unsigned)x;
         return (u64)h * m.c + base;
@@ -435,6 +498,17 @@ struct ArithDS {
         const u64 x = X;
         X = x + t;
         Y = x + k.m.q2 - t;
+    }
+    // Lazy forward butterfly (the wave-local transforms, ntt14w.hpp): the product is left raw and X rides on its first multiply-add,
+    //     R' = x_f + w y (raw),   X' = R',   Y' = 2 x_f + K q - R'   (= x_f + K q - w y: >= 0 and < 2^64, the u64 subtraction wraps),
+    // six multiply-adds, one v_lshl_add_u64 and one 64-bit subtract; FOLDX (three more instructions) only at the layers where
+    // DsLazy<B> says the X input has to be folded.  Outputs are bounded by Lazy::in_max(layer + 1), never canonical-sized.
+    template <bool FOLDX>
+    static __host__ __device__ __forceinline__ void ct_lazy(u64 &X, u64 &Y, const TwReg &w, const DsK &m) {
+        const u64 x = FOLDX ? fold1(X, m) : X;
+        const u64 r = mul_raw(Y, w, m, x);
+        X = r;
+        Y = ((x << 1) + m.qk) - r;
     }
     static constexpr int CT_LAYERS = 64;                      // no fold tied to a network's own layer count ...
     static constexpr bool PASS_FOLD = false;                  // ... nor to pass boundaries:
@@ -564,6 +638,32 @@ __device__ __forceinline__ void ct_apply(typename A::Elem (&x)[E], const typenam
                 }
             }
     }
+}
+
+// ... with the lazy butterflies of a policy that has them (A::Lazy, A::ct_lazy): which layers fold their X inputs is the policy's
+// compile-time schedule over the layers of the WHOLE transform (U::L0 + U::l), whatever the pass boundaries are
+template <class A, class U, int NTW, int E>
+__device__ __forceinline__ void ct_apply_lazy(typename A::Elem (&x)[E], const typename A::TwRaw (&raw)[NTW], const typename A::K &k) {
+    constexpr bool FOLDX = A::Lazy::fold_before(U::L0 + U::l);
+    // A scheduling boundary after every LAZY_GROUP butterflies: a lazy butterfly is two independent chains of multiply-adds with
+    // nothing folded in between, and hipcc left to itself keeps so many of them in flight that the 2^14 forward kernel needs more
+    // than its 128 registers (20 bytes of scratch per lane, reloaded behind every twiddle fetch in flight).  Groups of four: 127
+    // registers, no scratch, the same instruction count.
+    constexpr int LAZY_GROUP = 4;
+    static_for<0, (U::SHARED ? (1 << U::l) : U::NREP)>([&](auto oc) {
+        constexpr int outer = decltype(oc)::value;
+        static_for<0, (U::SHARED ? U::NREP : (1 << U::l))>([&](auto ic) {
+            constexpr int inner = decltype(ic)::value;
+            constexpr int b = U::SHARED ? outer : inner, rr = U::SHARED ? inner : outer;
+            const typename A::TwReg w = A::prep(raw[U::SHARED ? b : ((rr << U::l) | b)]);
+#pragma unroll
+            for (int j = 0; j < U::half; ++j) {
+                const int o = (U::REP0 + rr) * U::STRIDE + b * 2 * U::half + j;
+                A::template ct_lazy<FOLDX>(x[o], x[o + U::half], w, k.m);
+                if ((j + 1) % LAZY_GROUP == 0 || j + 1 == U::half) __builtin_amdgcn_sched_barrier(0);
+            }
+        });
+    });
 }
 
 // inverse: the unit of layer l is step R-1-l of its network; PH = step & 1 pairs layers for the lazy policies, sums are

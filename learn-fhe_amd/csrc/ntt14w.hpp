@@ -75,6 +75,31 @@ __device__ __host__ constexpr bool w14_pairs() {
     return R0 <= 3 && !w14_old_deal<A>::value;
 }
 
+// Forward butterflies: a policy with lazy products (A::Lazy, A::ct_lazy: ArithDS) leaves every twiddle product raw and folds only
+// the additive operand, at the layers its compile-time schedule names (arith.hpp, DsLazy).  The schedule starts from CANONICAL
+// inputs, which is what every producer of these kernels' inputs guarantees: callers' polynomials, ntt_big_fwd_pass (canon4) and the
+// RNS edge kernel (csub) for PFX sub-transforms; the forward half of the fused ring product is the same body (w14_lazy_fwd).  Its outputs are
+// bounded by Lazy::in_max(layers): canon_fwd (one fold, one conditional subtraction) makes them canonical before they leave.
+// Lab switch: a policy that declares W14_EAGER_CT keeps the folded butterflies (A::ct) for its own instantiations.
+template <class A, class = void> struct w14_has_lazy { static constexpr bool value = false; };
+template <class A> struct w14_has_lazy<A, std::void_t<typename A::Lazy>> { static constexpr bool value = true; };
+template <class A, class = void> struct w14_eager_ct { static constexpr bool value = false; };
+template <class A> struct w14_eager_ct<A, decltype((void)A::W14_EAGER_CT)> { static constexpr bool value = true; };
+template <class A>
+__device__ __host__ constexpr bool w14_lazy() {
+    return w14_has_lazy<A>::value && !w14_eager_ct<A>::value;
+}
+template <class A, bool KEEP>
+__device__ __host__ constexpr bool w14_lazy_fwd() {
+    if constexpr (w14_lazy<A>()) return !KEEP || A::Lazy::BITS == 60;
+    else return false;
+}
+template <bool LAZY, class A, class U, int NTW, int E>
+__device__ __forceinline__ void w14_ct(typename A::Elem (&x)[E], const typename A::TwRaw (&raw)[NTW], const typename A::K &k) {
+    if constexpr (LAZY) ct_apply_lazy<A, U>(x, raw, k);
+    else ct_apply<A, U>(x, raw, k);
+}
+
 #ifdef NTT14_STAMPS
 __device__ unsigned long long g_stamps[4096][16];
 #define STAMP_DECL unsigned long long stamps_[12]
@@ -386,6 +411,10 @@ template <class A, int R0, bool KEEP = false>
 __device__ __forceinline__ void fwd_one(u64 (&x)[32], u64 *__restrict__ g, const typename A::K &k, u64 *lds, u64 *wl,
                                         const int t, const int lane, const int w STAMP_ENTRY_PARAM) {
     typedef typename A::TwRaw Tw;
+    // lazy butterflies (w14_lazy_fwd).  The fused ring product's forward half, KEEP, takes them at 60 bits only: at 54 bits they push its
+    // kernel from no scratch to 16-24 bytes per lane beside the multipliers and the inverse half's addresses, at 60 bits from 20 bytes to none
+    constexpr bool LAZY = w14_lazy_fwd<A, KEEP>();
+    if constexpr (LAZY) static_assert(A::Lazy::canon_ok(11 + R0), "lazy outputs of this many layers do not fit canon_fwd");
     STAMP_DECL;
     STAMP_REAL(10);
     STAMP(0);
@@ -397,18 +426,18 @@ __device__ __forceinline__ void fwd_one(u64 (&x)[32], u64 *__restrict__ g, const
         if constexpr (R0 == 4) tw_load<A, false, P0<R0, (R0 == 4 ? 3 : 0)>>(a3, 0, k);
         STAMP(1);
         FHE_SCHED_FENCE();
-        ct_apply<A, P0<R0, 0>>(x, a0, k);
+        w14_ct<LAZY, A, P0<R0, 0>>(x, a0, k);
         if constexpr (R0 >= 2) {
             FHE_SCHED_FENCE();
-            ct_apply<A, P0<R0, (R0 >= 2 ? 1 : 0)>>(x, a1, k);
+            w14_ct<LAZY, A, P0<R0, (R0 >= 2 ? 1 : 0)>>(x, a1, k);
         }
         if constexpr (R0 >= 3) {
             FHE_SCHED_FENCE();
-            ct_apply<A, P0<R0, (R0 >= 3 ? 2 : 0)>>(x, a2, k);
+            w14_ct<LAZY, A, P0<R0, (R0 >= 3 ? 2 : 0)>>(x, a2, k);
         }
         if constexpr (R0 == 4) {
             FHE_SCHED_FENCE();
-            ct_apply<A, P0<R0, (R0 == 4 ? 3 : 0)>>(x, a3, k);
+            w14_ct<LAZY, A, P0<R0, (R0 == 4 ? 3 : 0)>>(x, a3, k);
         }
     }
     FHE_SCHED_FENCE();
@@ -422,15 +451,15 @@ __device__ __forceinline__ void fwd_one(u64 (&x)[32], u64 *__restrict__ g, const
         for (int r = 0; r < 32; ++r) x[r] = A::fold(x[r], k);
     }
     FHE_SCHED_FENCE();
-    ct_apply<A, P1<R0, 0>>(x, b0, k);
+    w14_ct<LAZY, A, P1<R0, 0>>(x, b0, k);
     FHE_SCHED_FENCE();
-    ct_apply<A, P1<R0, 1>>(x, b1, k);
+    w14_ct<LAZY, A, P1<R0, 1>>(x, b1, k);
     FHE_SCHED_FENCE();
-    ct_apply<A, P1<R0, 2>>(x, b2, k);
+    w14_ct<LAZY, A, P1<R0, 2>>(x, b2, k);
     FHE_SCHED_FENCE();
-    ct_apply<A, P1<R0, 3>>(x, b3, k);
+    w14_ct<LAZY, A, P1<R0, 3>>(x, b3, k);
     FHE_SCHED_FENCE();
-    const int t2 = (w << 4) | (lane >> 2), t3 = (w << 8) | lane;
+    const int t2 = (w << 4) | (lane >> 2), t3e = (w << 8) | lane;
     Tw c0[1], c1[2], c2[4], c3[8];  // pass 2: per lane; the first seven ride through X12
     tw_load<A, false, P2<R0, 0>>(c0, t2, k); tw_load<A, false, P2<R0, 1>>(c1, t2, k); tw_load<A, false, P2<R0, 2>>(c2, t2, k);
     STAMP(4);
@@ -441,19 +470,28 @@ __device__ __forceinline__ void fwd_one(u64 (&x)[32], u64 *__restrict__ g, const
         for (int r = 0; r < 32; ++r) x[r] = A::fold(x[r], k);
     }
     FHE_SCHED_FENCE();
-    ct_apply<A, P2<R0, 0>>(x, c0, k);
+    w14_ct<LAZY, A, P2<R0, 0>>(x, c0, k);
     FHE_SCHED_FENCE();
-    ct_apply<A, P2<R0, 1>>(x, c1, k);
+    w14_ct<LAZY, A, P2<R0, 1>>(x, c1, k);
     FHE_SCHED_FENCE();
     tw_load<A, false, P2<R0, 3>>(c3, t2, k);
-    ct_apply<A, P2<R0, 2>>(x, c2, k);
+    w14_ct<LAZY, A, P2<R0, 2>>(x, c2, k);
     FHE_SCHED_FENCE();
-    ct_apply<A, P2<R0, 3>>(x, c3, k);
+    w14_ct<LAZY, A, P2<R0, 3>>(x, c3, k);
     FHE_SCHED_FENCE();
+    // Pass 3 takes its lane number as a FRESH value where the lazy butterflies run: with fewer instructions between them more
+    // butterflies are in flight, and hipcc, which computes pass 3's twiddle, exchange and store addresses at the top of the kernel,
+    // then spills five of them through passes 1 and 2 (20 bytes of scratch).  Two instructions here instead.
+    int lane3 = lane, t3 = t3e;
+    if constexpr (LAZY) {
+        lane3 = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        asm volatile("" : "+v"(lane3));
+        t3 = (w << 8) | lane3;
+    }
     Tw7<A> d[2];  // pass 3: one replica ahead
     tw7_load<A, false, R0, 0>(d[0], t3, k);
     STAMP(6);
-    xchg_23(x, lane, wl);
+    xchg_23(x, lane3, wl);
     STAMP(7);
     if constexpr (A::PASS_FOLD) {
 #pragma unroll
@@ -463,17 +501,17 @@ __device__ __forceinline__ void fwd_one(u64 (&x)[32], u64 *__restrict__ g, const
     static_for<0, 4>([&](auto abc) {
         constexpr int ab = decltype(abc)::value;
         FHE_SCHED_FENCE();
-        ct_apply<A, P3<R0, 0, ab>>(x, d[ab & 1].l0, k);
-        ct_apply<A, P3<R0, 1, ab>>(x, d[ab & 1].l1, k);
+        w14_ct<LAZY, A, P3<R0, 0, ab>>(x, d[ab & 1].l0, k);
+        w14_ct<LAZY, A, P3<R0, 1, ab>>(x, d[ab & 1].l1, k);
         FHE_SCHED_FENCE();
         if constexpr (ab < 3) tw7_load<A, false, R0, (ab < 3 ? ab + 1 : 3)>(d[(ab + 1) & 1], t3, k);
-        ct_apply<A, P3<R0, 2, ab>>(x, d[ab & 1].l2, k);
+        w14_ct<LAZY, A, P3<R0, 2, ab>>(x, d[ab & 1].l2, k);
         FHE_SCHED_FENCE();
         if constexpr (KEEP) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) x[ab * 8 + j] = A::canon_fwd(x[ab * 8 + j], k);
         } else {
-            store_p3<A, ab>(x, dst_wave, lane, wl, k);
+            store_p3<A, ab>(x, dst_wave, lane3, wl, k);
         }
     });
     STAMP(8);

@@ -32,6 +32,12 @@ int check_transform(const fhe_ctx *ctx, const void *a, size_t n, size_t batch) {
 // are what is instantiated:
 template <class F>
 int with_wave_policy(int pm, F &&f) { return fhe::with_policy<fhe::ArithDS, 60, 54, 55>(pm, f); }  // the wave-local transforms (ntt14w.hpp)
+// The lazy forward butterflies of those kernels are proved for c <= DsLazy<B>::CMAX (arith.hpp).  That bound is the eligibility bound of
+// ctx_build_host itself: a modulus that reaches ArithDS at one of the listed widths is inside the proof, anything else takes Shoup
+// arithmetic as before, so no modulus needs a second set of butterflies.  A width added to the list without this holding does not compile.
+template <int... Bs>
+constexpr bool lazy_covers_eligible() { return (... && (fhe::DsLazy<Bs>::CMAX >= ((unsigned __int128)1 << (Bs - 33)))); }
+static_assert(lazy_covers_eligible<60, 54, 55>(), "a pseudo-Mersenne eligible modulus outside the lazy butterflies' proof");
 template <class F>
 int with_gen_policy(int pm, F &&f) { return fhe::with_policy<fhe::ArithPM, 60, 54, 55>(pm, f); }  // the generic kernels from N = 2^10 up
 // the fused ring product has no 55-bit instantiation: 55-bit moduli take its Shoup kernel

@@ -33,6 +33,7 @@ struct DSSkipV : ArithDS<60> {  // as DSSkip, but every word of a computed twidd
     }
 };
 struct DSNone : ArithDS<60> {  // ablation: HBM traffic + exchanges only
+    static constexpr bool W14_EAGER_CT = true;  // its own `ct` below, not the lazy butterflies
     static __device__ __forceinline__ void ct(u64 &X, u64 &Y, const TwReg &, const K &) { X ^= 1; Y ^= 1; }
     template <int PH> static __device__ __forceinline__ void gs(u64 &X, u64 &Y, const TwReg &, const K &) { X ^= 1; Y ^= 1; }
     template <bool INV> static __device__ __forceinline__ TwRaw fetch(const K &, int idx) { return uint4{(unsigned)idx, 1u, 2u, 3u}; }
