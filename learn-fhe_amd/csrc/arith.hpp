@@ -427,6 +427,243 @@ static_assert(DsLazy<60>::K == 7 && !DsLazy<60>::fold_before(0) && !DsLazy<60>::
               !DsLazy<60>::fold_before(3) && DsLazy<60>::fold_before(4) && !DsLazy<60>::fold_before(13) && DsLazy<60>::fold_before(14), "60 bits");
 static_assert(DsLazy<55>::K == 7 && !DsLazy<55>::fold_before(15) && DsLazy<54>::K == 7 && !DsLazy<54>::fold_before(15), "54 / 55 bits");
 
+// Bounds of the LAZY inverse butterfly (ArithDS<B>::gs_lazy), the inverse's counterpart of DsLazy, over the same moduli and in the
+// same 128-bit arithmetic:
+//     x = fold(X) or X;  y = fold(Y) or Y;  s = x + y (folded or not);  d = x + m q - y;  X' = s;  Y' = R(d, w), left raw.
+//   * the difference needs m QMIN >= bound(y) (the offset covers the subtrahend for every admitted q: m = cover(bound(y))) and
+//     bound(x) + m QMAX < 2^64; the product takes ANY 64-bit d and comes back <= RMAX, so the difference branch never folds;
+//   * a sum is folded exactly where it could not enter another butterfly as it stands (keep_ok: two such values must still pair up);
+//     since keep_ok is monotone, every pair of values that passed it pairs up, whatever the exchanges did to their order.
+// SCHED<R0, PAIRS, IN> walks the real order of the wave-local inverse (ntt14w.hpp: inv_one) with ONE bound per register index:
+// pass 3 in its diagonal form (gs_diag_lazy: F8, then the seven multipliers), X32, pass 2, X21, pass 1, X10, pass 0 and the last layer.
+// An exchange turns register bits into lane bits: a register then holds, across the lanes, every value that was written in the same
+// round, so its bound is the maximum over them (x32 / x21 / x10 below mirror the index expressions of xchg_32 / xchg_21 / xchg_10).
+// IN names what enters: canonical values (callers' evaluations) or ArithDS::mulvar outputs (the multiplying load and the fused ring
+// product, whose forward half leaves canonical replicas that are then multiplied): below MULVAR_MAX, not canonical.
+// The offsets m q in use are a handful of constants (Sched::ms); kernels pass them as opaque scalar pairs, like DsK::qk.
+template <int B>
+struct DsGsLazy {
+    typedef DsLazy<B> L;
+    typedef unsigned __int128 u128;
+    static constexpr int BITS = B, IN_CANON = 0, IN_MUL = 1, MAX_OFFS = 12, STEPS = 12;  // layers 3 .. 14 of the inverse at most (R0 = 4)
+    static constexpr u128 CAP = L::CAP, QMIN = L::QMIN, QMAX = L::QMAX, RMAX = L::RMAX, CMAX = L::CMAX;
+    static constexpr u128 fold_max(u128 in) { return L::fold_max(in); }
+    // pm_mul on two canonical operands: v < 2^(B+2), u < 2^31 2^(B-32) + 2^32, one fold of v + u 2c at bit B
+    static constexpr u128 MULVAR_MAX = fold_max((u128(1) << (B + 2)) + ((u128(1) << (B - 1)) + (u128(1) << 32)) * 2 * CMAX);
+    static constexpr u128 in_max(int in_kind) { return in_kind == IN_MUL ? MULVAR_MAX : QMAX - 1; }
+    // the offset multiple for a subtrahend below `by`: the smallest m with m QMIN >= by up to 8, above that the next of 16, 64, 256, ..
+    // (the narrow widths have room to spare, and every distinct offset is a scalar register pair in the kernels)
+    static constexpr unsigned cover(u128 by) {
+        const u128 m = (by + QMIN - 1) / QMIN;
+        if (m <= 8) return (unsigned)m;
+        unsigned r = 16;
+        while (r < m && r < (1u << 30)) r *= 4;
+        return r;
+    }
+    static constexpr bool pair_ok(u128 bx, u128 by) { return bx + by < CAP && bx + cover(by) * QMAX < CAP; }
+    static constexpr bool keep_ok(u128 b) { return pair_ok(b, b); }
+
+    struct Step {
+        bool used, fx, fy, fs, ok;
+        unsigned m;
+        u128 bx, by;  // the bounds of X and Y as they arrive
+    };
+    // one butterfly on the bounds (X, Y); last = the final layer: both outputs leave canonical (one fold or product, one subtraction)
+    static constexpr Step bfly(u128 &X, u128 &Y, bool last) {
+        Step s{};
+        s.used = true; s.bx = X; s.by = Y;
+        u128 x = X, y = Y;
+        if (!pair_ok(x, y)) {  // not met by the schedules below (keep_ok is monotone); kept so that the recurrence is closed
+            if (y >= x) { s.fy = true; y = fold_max(Y); }
+            else { s.fx = true; x = fold_max(X); }
+        }
+        if (!pair_ok(x, y)) { s.fx = s.fy = true; x = fold_max(X); y = fold_max(Y); }
+        s.ok = pair_ok(x, y);
+        s.m = cover(y);
+        const u128 sum = x + y;
+        if (last) {
+            s.ok = s.ok && fold_max(sum) < 2 * QMIN && fold_max(RMAX) < 2 * QMIN;
+            X = Y = QMAX - 1;
+        } else {
+            s.fs = !keep_ok(sum);
+            X = s.fs ? fold_max(sum) : sum;
+            Y = RMAX;
+        }
+        return s;
+    }
+
+    // pass 3, one block of 8 values that all arrive below `in` (names as in gs_diag_lazy).  Three folds can be needed: of the
+    // product t1 (it is ADDED to the unfolded t0, and both u1 and e1 are added to a raw product later), of the sum u3 of two raw
+    // products (it is subtracted) and of v0, the one output that no product reduces.  Of the eight combinations the cheapest valid one.
+    struct Diag {
+        bool ft1, fu3, fv0, ok;
+        unsigned mv, ms, mt1, mr, mu2, mu3;  // offsets: layer A | s1, s3 | t1 | raw products | u2 | u3
+        u128 in, out[8], arg_max;             // arg_max: the largest sum or offset difference formed
+        int folds;
+    };
+    static constexpr Diag diag_try(u128 in, bool ft1, bool fu3, bool fv0) {
+        Diag d{};
+        d.in = in; d.ft1 = ft1; d.fu3 = fu3; d.fv0 = fv0; d.folds = int(ft1) + int(fu3) + int(fv0);
+        d.mv = cover(in); d.mr = cover(RMAX);
+        const u128 sb = 2 * in, t0b = in + d.mv * QMAX;             // layer A: s = v + v', t = v + mv q - v'
+        d.ms = cover(sb);
+        const u128 t1b = ft1 ? fold_max(RMAX) : RMAX;
+        d.mt1 = cover(t1b);
+        const u128 u0b = 2 * sb, e0b = sb + d.ms * QMAX;            // layer B
+        const u128 u1b = t0b + t1b, e1b = t0b + d.mt1 * QMAX;
+        const u128 u2b = 2 * sb, e2a = sb + d.ms * QMAX;
+        const u128 u3r = 2 * RMAX, u3b = fu3 ? fold_max(u3r) : u3r, e3a = RMAX + d.mr * QMAX;
+        d.mu2 = cover(u2b); d.mu3 = cover(u3b);
+        const u128 v0r = u0b + u2b;                                 // layer C
+        const u128 args[12] = {sb, t0b, u0b, e0b, u1b, e1b, e2a, u3r, e3a, v0r, u1b + u3b, e0b + RMAX};
+        const u128 args2[5] = {e1b + RMAX, u0b + d.mu2 * QMAX, u1b + d.mu3 * QMAX, e0b + d.mr * QMAX, e1b + d.mr * QMAX};
+        d.ok = true;
+        for (u128 a : args) { if (a > d.arg_max) d.arg_max = a; }
+        for (u128 a : args2) { if (a > d.arg_max) d.arg_max = a; }
+        if (d.arg_max >= CAP) d.ok = false;
+        d.out[0] = fv0 ? fold_max(v0r) : v0r;
+        if (!keep_ok(d.out[0]) || !keep_ok(RMAX)) d.ok = false;
+        for (int p = 1; p < 8; ++p) d.out[p] = RMAX;
+        return d;
+    }
+    static constexpr Diag diag(u128 in) {
+        Diag best{};
+        for (int n = 0; n <= 3; ++n)
+            for (int c = 0; c < 8; ++c) {
+                const Diag d = diag_try(in, c & 1, c & 2, c & 4);
+                if (d.folds == n && d.ok && !best.ok) best = d;
+            }
+        return best;
+    }
+
+    // the wave-private and cross-wave exchanges on the bounds: round h of each moves the registers named by the same expressions as the code
+    static constexpr void x32(u128 (&b)[32]) {
+        u128 nb[32] = {};
+        for (int h = 0; h < 2; ++h) {
+            u128 mx = 0;
+            for (int R = 0; R < 16; ++R) { const u128 v = b[((R >> 2) << 3) | (h << 2) | (R & 3)]; if (v > mx) mx = v; }
+            for (int c = 0; c < 16; ++c) nb[(h << 4) | c] = mx;
+        }
+        for (int r = 0; r < 32; ++r) b[r] = nb[r];
+    }
+    static constexpr void x21(u128 (&b)[32]) {
+        u128 nb[32] = {};
+        for (int h = 0; h < 2; ++h) {
+            u128 mx = 0;
+            for (int r4 = 0; r4 < 16; ++r4) { const u128 v = b[((r4 & 1) << 4) | (h << 3) | (r4 >> 1)]; if (v > mx) mx = v; }
+            for (int n4 = 0; n4 < 16; ++n4) nb[(h << 4) | n4] = mx;
+        }
+        for (int r = 0; r < 32; ++r) b[r] = nb[r];
+    }
+    static constexpr bool x10(u128 (&b)[32], int R0, bool pairs) {
+        const int PB = 5 - R0, NLOW = 1 << (PB - 1);
+        u128 nb[32] = {};
+        for (int h = 0; h < 2; ++h) {
+            u128 mx = 0;
+            for (int m = 0; m < 16; ++m) { const u128 v = b[((m & 1) << 4) | (h << 3) | (m >> 1)]; if (v > mx) mx = v; }
+            if (pairs) {
+                for (int lo = 0; lo < NLOW / 2; ++lo)
+                    for (int n = 0; n < (1 << R0); ++n) {
+                        const int r = ((((h * (NLOW / 2)) | lo) << 1) << R0) | n;
+                        nb[r] = mx; nb[r + (1 << R0)] = mx;
+                    }
+            } else {
+                for (int lo = 0; lo < NLOW; ++lo)
+                    for (int n = 0; n < (1 << R0); ++n) nb[((((h << (PB - 1)) | lo)) << R0) | n] = mx;
+            }
+        }
+        bool all = true;
+        for (int r = 0; r < 32; ++r) { if (nb[r] == 0) all = false; b[r] = nb[r]; }
+        return all;  // every register of pass 0 has been given a bound
+    }
+
+    struct Sched {
+        Diag diag;
+        Step lay[STEPS][32];   // lay[g - 3][o]: the butterfly of layer g (counted as inv_one counts them) whose X is register o
+        u128 after[STEPS][32]; // the register bounds behind that layer
+        unsigned ms[MAX_OFFS]; // the distinct offsets m q in use, ascending
+        int nm, layers, folds, bflies;
+        bool ok;
+        constexpr int mi(unsigned m) const {
+            for (int i = 0; i < nm; ++i) if (ms[i] == m) return i;
+            return -1;
+        }
+    };
+    static constexpr void add_m(Sched &s, unsigned m) {
+        if (s.mi(m) >= 0) return;
+        if (s.nm == MAX_OFFS) { s.ok = false; return; }
+        int i = s.nm++;
+        for (; i > 0 && s.ms[i - 1] > m; --i) s.ms[i] = s.ms[i - 1];
+        s.ms[i] = m;
+    }
+    // one layer of a radix-2^R network on NREP replicas STRIDE registers apart (Unit, below); l counts down within a pass
+    static constexpr void layer(Sched &s, u128 (&b)[32], int g, int R, int l, int nrep, int stride, bool last) {
+        const int half = 1 << (R - 1 - l);
+        for (int rr = 0; rr < nrep; ++rr)
+            for (int bb = 0; bb < (1 << l); ++bb)
+                for (int j = 0; j < half; ++j) {
+                    const int o = rr * stride + bb * 2 * half + j;
+                    const Step st = bfly(b[o], b[o + half], last);
+                    s.lay[g - 3][o] = st;
+                    s.ok = s.ok && st.ok;
+                    s.folds += int(st.fx) + int(st.fy) + int(st.fs) + (last ? 2 : 0);
+                    s.bflies += 1;
+                    add_m(s, st.m);
+                }
+        for (int r = 0; r < 32; ++r) s.after[g - 3][r] = b[r];
+    }
+    static constexpr Sched make(int R0, bool pairs, int in_kind) {
+        Sched s{};
+        s.diag = diag(in_max(in_kind));
+        s.ok = s.diag.ok && keep_ok(in_max(in_kind));
+        add_m(s, s.diag.mv); add_m(s, s.diag.ms); add_m(s, s.diag.mt1); add_m(s, s.diag.mr); add_m(s, s.diag.mu2); add_m(s, s.diag.mu3);
+        s.folds = 4 * s.diag.folds; s.bflies = 4 * 12;
+        u128 b[32] = {};
+        for (int r = 0; r < 32; ++r) b[r] = s.diag.out[r & 7];  // pass-3 register (ab, n3): position n3 of its block
+        x32(b);
+        int g = 3;
+        for (int l = 3; l >= 0; --l) layer(s, b, g++, 4, l, 2, 16, false);  // pass 2
+        x21(b);
+        for (int l = 3; l >= 0; --l) layer(s, b, g++, 4, l, 2, 16, false);  // pass 1
+        if (!x10(b, R0, pairs)) s.ok = false;
+        for (int l = R0 - 1; l >= 1; --l) layer(s, b, g++, R0, l, 32 >> R0, 1 << R0, false);  // pass 0
+        layer(s, b, g++, R0, 0, 32 >> R0, 1 << R0, true);
+        s.layers = g;
+        return s;
+    }
+    template <int R0, bool PAIRS, int IN>
+    static constexpr Sched SCHED = make(R0, PAIRS, IN);
+    // ... as compile-time template arguments of the kernels
+    template <int R0, bool PAIRS, int IN> static constexpr bool fx(int g, int o) { return SCHED<R0, PAIRS, IN>.lay[g - 3][o].fx; }
+    template <int R0, bool PAIRS, int IN> static constexpr bool fy(int g, int o) { return SCHED<R0, PAIRS, IN>.lay[g - 3][o].fy; }
+    template <int R0, bool PAIRS, int IN> static constexpr bool fs(int g, int o) { return SCHED<R0, PAIRS, IN>.lay[g - 3][o].fs; }
+    template <int R0, bool PAIRS, int IN> static constexpr int mi(int g, int o) {
+        return SCHED<R0, PAIRS, IN>.mi(SCHED<R0, PAIRS, IN>.lay[g - 3][o].m);
+    }
+    template <int R0, bool PAIRS, int IN> static constexpr bool valid() {
+        constexpr Sched s = SCHED<R0, PAIRS, IN>;
+        return s.ok && s.layers == 11 + R0 && s.bflies == 16 * (11 + R0);
+    }
+    // folds per butterfly in hundredths (the last layer's two canonicalisations count as folds, as in the folded inverse)
+    template <int R0, bool PAIRS, int IN> static constexpr int folds_x100() { return SCHED<R0, PAIRS, IN>.folds * 100 / SCHED<R0, PAIRS, IN>.bflies; }
+
+    static_assert(keep_ok(RMAX), "a raw product must be able to enter a butterfly as it stands");
+    static_assert(fold_max(CAP - 1) < 2 * QMIN, "a folded value is below 2q: one conditional subtraction makes it canonical");
+    static_assert(cover(RMAX) == L::K, "the offset of a raw subtrahend is DsLazy's K");
+    // no intermediate reaches 2^64, every offset covers its subtrahend and the last layer leaves canonical values (Step::ok, Diag::ok),
+    // for every ring size, both dealings of the pass-0 side and both kinds of input
+    static_assert(valid<1, true, 0>() && valid<2, true, 0>() && valid<3, true, 0>() && valid<4, false, 0>(), "whole rings, canonical inputs");
+    static_assert(valid<1, true, 1>() && valid<2, true, 1>() && valid<3, true, 1>() && valid<4, false, 1>(), "multiplied inputs");
+    static_assert(valid<1, false, 0>() && valid<2, false, 0>() && valid<3, false, 0>() && valid<3, false, 1>(), "the 8-byte dealing");
+};
+// 60 bits: the states are q, 2q, 4q and raw (<= RMAX < 7q + ..): 4q + 4q and raw + raw fold, the diagonal pass folds three values per
+// block where the folded inverse folds thirteen, about 0.7 folds per butterfly in all against 1.3
+static_assert(DsGsLazy<60>::SCHED<3, true, 0>.diag.folds == 3 && DsGsLazy<60>::folds_x100<3, true, 0>() <= 75, "60 bits");
+static_assert(DsGsLazy<60>::folds_x100<3, true, 1>() <= 75 && DsGsLazy<60>::folds_x100<4, false, 0>() <= 75, "60 bits");
+// 54 / 55 bits, the same recurrence: hardly anything but the last layer's canonicalisations (32 of them are 0.14 per butterfly)
+static_assert(DsGsLazy<55>::SCHED<3, true, 0>.diag.folds == 0 && DsGsLazy<55>::folds_x100<3, true, 0>() <= 30, "55 bits");
+static_assert(DsGsLazy<54>::SCHED<3, true, 0>.diag.folds == 0 && DsGsLazy<54>::folds_x100<3, true, 0>() <= 30, "54 bits");
+
 template <int B>
 struct ArithDS {
     typedef u64 Elem;
@@ -543,6 +780,66 @@ struct ArithDS {
     static __device__ __forceinline__ u64 fold(u64 x, const K &k) { return fold1(x, k.m); }
     static __device__ __forceinline__ u64 canon_fwd(u64 x, const K &k) { return csub(fold1(x, k.m), k.m.q); }
     static __device__ __forceinline__ u64 finish_inv(u64 x, const K &k) { return csub(mul(x, k.ninv, k.m), k.m.q); }
+    // Lazy inverse butterfly (the wave-local transforms, ntt14w.hpp): the product of the difference branch is left raw, the difference
+    // takes the offset `off` = m q that DsGsLazy<B> computed for the bound of Y, and nothing is folded unless the schedule says so
+    // (FX / FY: an input first; FS: the sum on its way out).  Two 64-bit additions, one subtraction and six multiply-adds.
+    typedef DsGsLazy<B> GsLazy;
+    template <bool FX, bool FY, bool FS>
+    static __host__ __device__ __forceinline__ void gs_lazy(u64 &X, u64 &Y, const TwReg &w, const DsK &m, u64 off) {
+        const u64 x = FX ? fold1(X, m) : X, y = FY ? fold1(Y, m) : Y;
+        const u64 s = x + y;
+        Y = mul_raw((x + off) - y, w, m);
+        X = FS ? fold1(s, m) : s;
+    }
+    // x < 2q -> canonical (csub of dev_arith.hpp, written out: these are checked on the host as well)
+    static __host__ __device__ __forceinline__ u64 canon2(u64 x, const DsK &m) { return x >= m.q ? x - m.q : x; }
+    // ... the last layer: what gs_last_scaled / gs_last_plain do (one product or fold and one conditional subtraction per output),
+    // on inputs that arrive with the schedule's bounds instead of a layer count
+    template <bool FX, bool FY>
+    static __host__ __device__ __forceinline__ void gs_last_scaled_lazy(u64 &X, u64 &Y, const uint4 &ninv, const uint4 &ninv_w, const DsK &m, u64 off) {
+        const u64 x = FX ? fold1(X, m) : X, y = FY ? fold1(Y, m) : Y;
+        const u64 s = x + y, d = (x + off) - y;
+        X = canon2(fold1(mul_raw(s, ninv, m), m), m);
+        Y = canon2(fold1(mul_raw(d, ninv_w, m), m), m);
+    }
+    template <bool FX, bool FY>
+    static __host__ __device__ __forceinline__ void gs_last_plain_lazy(u64 &X, u64 &Y, const TwReg &w, const DsK &m, u64 off) {
+        const u64 x = FX ? fold1(X, m) : X, y = FY ? fold1(Y, m) : Y;
+        const u64 s = x + y, d = (x + off) - y;
+        X = canon2(fold1(s, m), m);
+        Y = canon2(fold1(mul_raw(d, w, m), m), m);
+    }
+    // Pass 3 of the inverse in its diagonal form (ntt14w.hpp: p3_diag_apply) on one block v[0..7], lazily: F8 with the twiddles
+    // ci, cj, cij, then the seven multipliers e[]; every product raw, differences by offsets, and the three folds of GsLazy::Diag
+    // where it asks for them.  off[] = the schedule's offsets (Sched::ms) times q; used(p, product) is called once multiplier p has been used.
+    template <int R0, bool PAIRS, int IN, int NM, class F>
+    static __host__ __device__ __forceinline__ void gs_diag_lazy(u64 *v, const uint4 (&e)[7], const uint4 &ci, const uint4 &cj, const uint4 &cij,
+                                                                 const DsK &m, const u64 (&off)[NM], F &&used) {
+        constexpr typename GsLazy::Sched S = GsLazy::template SCHED<R0, PAIRS, IN>;
+        constexpr typename GsLazy::Diag D = S.diag;
+        static_assert(S.nm <= NM, "offset table too small");
+        const u64 ov = off[S.mi(D.mv)], os = off[S.mi(D.ms)], ot1 = off[S.mi(D.mt1)], orr = off[S.mi(D.mr)], ou2 = off[S.mi(D.mu2)],
+                  ou3 = off[S.mi(D.mu3)];
+        // layer A: pairs (2j, 2j + 1)
+        const u64 s0 = v[0] + v[1], t0 = (v[0] + ov) - v[1];
+        const u64 s1 = v[2] + v[3], t1r = mul_raw((v[2] + ov) - v[3], ci, m), t1 = D.ft1 ? fold1(t1r, m) : t1r;
+        const u64 s2 = v[4] + v[5], t2 = mul_raw((v[4] + ov) - v[5], cj, m);
+        const u64 s3 = v[6] + v[7], t3 = mul_raw((v[6] + ov) - v[7], cij, m);
+        // layer B: pairs (4j + k, 4j + 2 + k)
+        const u64 u0 = s0 + s1, e0 = (s0 + os) - s1;
+        const u64 u1 = t0 + t1, e1 = (t0 + ot1) - t1;
+        const u64 u2 = s2 + s3, e2 = mul_raw((s2 + os) - s3, ci, m);
+        const u64 u3r = t2 + t3, u3 = D.fu3 ? fold1(u3r, m) : u3r, e3 = mul_raw((t2 + orr) - t3, ci, m);
+        // layer C: pairs (k, 4 + k); then the diagonal (no scheduling boundaries in here: every placement tried cost registers)
+        v[0] = D.fv0 ? fold1(u0 + u2, m) : u0 + u2;
+        v[1] = mul_raw(u1 + u3, e[0], m); used(0, v[1]);
+        v[2] = mul_raw(e0 + e2, e[1], m); used(1, v[2]);
+        v[3] = mul_raw(e1 + e3, e[2], m); used(2, v[3]);
+        v[4] = mul_raw((u0 + ou2) - u2, e[3], m); used(3, v[4]);
+        v[5] = mul_raw((u1 + ou3) - u3, e[4], m); used(4, v[5]);
+        v[6] = mul_raw((e0 + orr) - e2, e[5], m); used(5, v[6]);
+        v[7] = mul_raw((e1 + orr) - e3, e[6], m); used(6, v[7]);
+    }
     // Multiply-accumulate against VARIABLE key values (the fused gadget products): a key value has no precomputed w 2^32 mod q,
     // so this is ArithPM's unreduced (v, u) accumulation on its 8-byte packed operands -- the transforms around it run on the
     // two-operand product.  Forward outputs here are < (2 log2 N + 1) q, inside the bound ArithPM::mac states.
@@ -687,6 +984,38 @@ __device__ __forceinline__ void gs_apply(typename A::Elem (&x)[E], const typenam
                 A::template gs<PH>(x[o], x[o + U::half], w, k);
                 if constexpr (FOLD) x[o] = A::gs_fold(x[o], k);
             }
+        });
+    });
+}
+
+// ... with the lazy butterflies of a policy that has them (A::GsLazy, A::gs_lazy): layer GSTEP of the whole inverse, every butterfly
+// with the folds and the offset that the policy's compile-time schedule SEL (R0, PAIRS, IN) holds for its registers.  Scheduling
+// boundaries as in ct_apply_lazy, for the same reason.
+template <int R0_, bool PAIRS_, int IN_>
+struct GsSel {
+    static constexpr int R0 = R0_, IN = IN_;
+    static constexpr bool PAIRS = PAIRS_;
+};
+template <class A, class U, class SEL, int GSTEP, int NTW, int E, int NM>
+__device__ __forceinline__ void gs_apply_lazy(typename A::Elem (&x)[E], const typename A::TwRaw (&raw)[NTW], const typename A::K &k,
+                                              const u64 (&off)[NM]) {
+    typedef typename A::GsLazy G;
+    constexpr int LAZY_GROUP = 4;
+    static_for<0, (U::SHARED ? (1 << U::l) : U::NREP)>([&](auto oc) {
+        constexpr int outer = decltype(oc)::value;
+        static_for<0, (U::SHARED ? U::NREP : (1 << U::l))>([&](auto ic) {
+            constexpr int inner = decltype(ic)::value;
+            constexpr int b = U::SHARED ? outer : inner, rr = U::SHARED ? inner : outer;
+            const typename A::TwReg w = A::prep(raw[U::SHARED ? b : ((rr << U::l) | b)]);
+            static_for<0, U::half>([&](auto jc) {
+                constexpr int j = decltype(jc)::value, o = (U::REP0 + rr) * U::STRIDE + b * 2 * U::half + j;
+                constexpr bool FX = G::template fx<SEL::R0, SEL::PAIRS, SEL::IN>(GSTEP, o), FY = G::template fy<SEL::R0, SEL::PAIRS, SEL::IN>(GSTEP, o),
+                               FS = G::template fs<SEL::R0, SEL::PAIRS, SEL::IN>(GSTEP, o);
+                constexpr int MI = G::template mi<SEL::R0, SEL::PAIRS, SEL::IN>(GSTEP, o);
+                static_assert(MI >= 0 && MI < NM, "no offset for this butterfly");
+                A::template gs_lazy<FX, FY, FS>(x[o], x[o + U::half], w, k.m, off[MI]);
+                if constexpr ((j + 1) % LAZY_GROUP == 0 || j + 1 == U::half) __builtin_amdgcn_sched_barrier(0);
+            });
         });
     });
 }

@@ -100,6 +100,55 @@ __device__ __forceinline__ void w14_ct(typename A::Elem (&x)[E], const typename 
     else ct_apply<A, U>(x, raw, k);
 }
 
+// Inverse butterflies: a policy with a lazy inverse (A::GsLazy, A::gs_lazy: ArithDS) leaves every product raw, takes its differences by
+// offsets m q and folds a sum only where the compile-time schedule of arith.hpp (DsGsLazy) finds that it could not enter the next
+// butterfly as it stands.  The schedule is walked per ring size (R0), dealing (PAIRS) and kind of input (IN: canonical evaluations, or
+// the products of the multiplying load / of the fused ring product); the last layer leaves canonical values as before.
+// Lab switch: a policy that declares W14_FOLDED_GS keeps the folded inverse (A::gs, every product folded) for its own instantiations.
+template <class A, class = void> struct w14_has_gs_lazy { static constexpr bool value = false; };
+template <class A> struct w14_has_gs_lazy<A, std::void_t<typename A::GsLazy>> { static constexpr bool value = true; };
+template <class A, class = void> struct w14_folded_gs { static constexpr bool value = false; };
+template <class A> struct w14_folded_gs<A, decltype((void)A::W14_FOLDED_GS)> { static constexpr bool value = true; };
+template <class A>
+__device__ __host__ constexpr bool w14_lazy_inv() {
+    return w14_has_gs_lazy<A>::value && !w14_folded_gs<A>::value;
+}
+// ... and where: every instantiation whose listing has no scratch with the lazy butterflies (profiles/kernel_inventory.txt).  The
+// others keep the folded inverse, as the fused product's forward half does at 54 bits: whole rings of 2^14 with a multiplying load
+// or at 54 / 55 bits (2 - 8 registers spilled), whole rings of 2^15 (one workgroup of 16 waves: 2 - 3), and the fused ring product
+// at 2^14 and 2^15 and at 54 / 55 bits (4 - 9 beside the multipliers).
+template <class A, bool PFX, int R0, int IN, bool FUSED>
+__device__ __host__ constexpr bool w14_lazy_inv_at() {
+    if constexpr (!w14_lazy_inv<A>()) return false;
+    else if (PFX) return true;
+    else if (FUSED) return R0 == 2 && A::GsLazy::BITS == 60;
+    else if (R0 <= 2) return true;
+    else return R0 == 3 && IN == 0 && A::GsLazy::BITS == 60;
+}
+constexpr int W14_OFFS = 12;  // DsGsLazy::MAX_OFFS
+// the schedule's offsets m q as values the compiler cannot see into (as m * q it rebuilds the product in every butterfly); asked for
+// again at the head of every pass, so that none of them occupies scalar registers across a pass that does not use it
+template <class A, class SEL>
+__device__ __forceinline__ void w14_gs_offs(u64 (&off)[W14_OFFS], const typename A::K &k) {
+    typedef typename A::GsLazy G;
+    static_assert(G::MAX_OFFS == W14_OFFS, "offset table size");
+    static_for<0, W14_OFFS>([&](auto ic) {
+        constexpr int i = decltype(ic)::value;
+        constexpr typename G::Sched S = G::template SCHED<SEL::R0, SEL::PAIRS, SEL::IN>;
+        if constexpr (i < S.nm) {
+            off[i] = u64(S.ms[i]) * k.m.q;
+            asm("" : "+s"(off[i]));
+        } else {
+            off[i] = 0;
+        }
+    });
+}
+template <bool LZ, class A, class U, class SEL, int GSTEP, int NTW, int E>
+__device__ __forceinline__ void w14_gs(typename A::Elem (&x)[E], const typename A::TwRaw (&raw)[NTW], const typename A::K &k, const u64 (&off)[W14_OFFS]) {
+    if constexpr (LZ) gs_apply_lazy<A, U, SEL, GSTEP>(x, raw, k, off);
+    else gs_apply<A, U, GSTEP>(x, raw, k);
+}
+
 #ifdef NTT14_STAMPS
 __device__ unsigned long long g_stamps[4096][16];
 #define STAMP_DECL unsigned long long stamps_[12]
@@ -589,6 +638,24 @@ __device__ __forceinline__ void p3_diag_apply(u64 (&x)[32], uint4 (&e)[7], const
     v[7] = A::mul(e1 + m.q2 - e3, e[6], m); refill(6);
 }
 
+// ... with the lazy arithmetic (ArithDS::gs_diag_lazy: three folds per block instead of thirteen at 60 bits, none at 54 / 55)
+template <class A, class SEL, int R0, int AB, int NEXT>
+__device__ __forceinline__ void p3_diag_apply_lazy(u64 (&x)[32], uint4 (&e)[7], const uint4 &ci, const uint4 &cj, const uint4 &cij, int t3,
+                                                   const typename A::K &k, const u64 (&off)[W14_OFFS]) {
+    const int blk = NEXT >= 0 ? p3_blk<A, R0, (NEXT >= 0 ? NEXT : 0)>(t3, k) : 0;
+    // The refill of a slot takes its index through the product that used the slot last: table loads are ordered against nothing else, and
+    // hipcc otherwise requests the multipliers of all four replicas at the head of the kernel (84 registers beside the 64 of x:
+    // 260 bytes of scratch per lane).
+    A::template gs_diag_lazy<SEL::R0, SEL::PAIRS, SEL::IN>(x + 8 * AB, e, ci, cj, cij, k.m, off, [&](int p, u64 done) {
+        if constexpr (NEXT >= 0) {
+            int b = blk;
+            asm("" : "+v"(b) : "v"((unsigned)done));
+            const FHE_CONST uint4 *q = k.tw3i + size_t(p) * k.tw3_stride + b;
+            e[p] = uint4{q->x, q->y, q->z, q->w};
+        }
+    });
+}
+
 // One inverse transform; x[] arrives loaded in the pass-3 layout, d[] with the pass-3 twiddles of replicas 0 and 1 (fetched BEFORE
 // the coefficients: vmcnt retires in order, and the twiddles are L2 hits).
 template <class A, bool PFX, int R0>
@@ -738,6 +805,198 @@ __device__ __forceinline__ void inv_one(u64 (&x)[32], Tw7<A> (&d)[2], u64 *__res
     STAMP_FLUSH();
 }
 
+// ... with the lazy butterflies (w14_lazy_inv_at): the same passes, exchanges, twiddle order and last layer; IN: 0 = canonical
+// inputs, 1 = mulvar outputs.  Kept beside inv_one, not inside it, so that every other instantiation compiles exactly as before.
+template <class A, bool PFX, int R0, int IN>
+__device__ __forceinline__ void inv_one_lazy(u64 (&x)[32], Tw7<A> (&d)[2], u64 *__restrict__ g, const typename A::K &k, u64 *lds, u64 *wl,
+                                        const int t, const int lane, const int w STAMP_ENTRY_PARAM) {
+    typedef typename A::TwRaw Tw;
+    const int t3 = (w << 8) | lane;
+    // lazy butterflies (w14_lazy_inv) by the schedule of this ring size, dealing and input; IN: 0 = canonical, 1 = mulvar outputs
+    constexpr bool LZ = true;
+    typedef GsSel<R0, w14_pairs<A, R0>(), IN> SEL;
+    u64 off[W14_OFFS] = {};
+    if constexpr (LZ) {
+        static_assert(w14_p3_diag<A>(), "the lazy inverse is written for the diagonal form of pass 3");
+        static_assert(A::GsLazy::template valid<R0, w14_pairs<A, R0>(), IN>(), "no valid lazy schedule");
+        w14_gs_offs<A, SEL>(off, k);
+    }
+    STAMP_DECL;
+    STAMP_REAL(10);
+    STAMP(0);
+    // pass 3: layers 13, 12, 11.  Eight-byte twiddles are fetched two replicas ahead (d[] arrives holding replicas 0 and 1); sixteen-
+    // byte ones (ArithDS) refill each layer's slot for the NEXT replica as soon as the layer has used it -- 28 registers instead
+    // of 56 beside the 64 of x.  The two schemes measure the same (tools/ntt_lab2.hip: 0.331 / 0.333 ms); the refill is kept for the
+    // registers it leaves free.
+    constexpr bool REFILL = w14_p3_refill<A>();
+    Tw c3[8], c2[4], c1[2], c0[1];
+    if constexpr (w14_p3_diag<A>()) {
+        uint4(&e)[7] = reinterpret_cast<uint4(&)[7]>(d[0]);   // Tw7 of a 16-byte policy = seven uint4
+        const uint4 ci = A::template fetch<true>(k, 1), cj = A::template fetch<true>(k, 2), cij = A::template fetch<true>(k, 3);
+        if constexpr (LZ) {
+            FHE_SCHED_FENCE();
+            p3_diag_apply_lazy<A, SEL, R0, 0, 1>(x, e, ci, cj, cij, t3, k, off);
+            FHE_SCHED_FENCE();
+            p3_diag_apply_lazy<A, SEL, R0, 1, 2>(x, e, ci, cj, cij, t3, k, off);
+            FHE_SCHED_FENCE();
+            p3_diag_apply_lazy<A, SEL, R0, 2, 3>(x, e, ci, cj, cij, t3, k, off);
+            FHE_SCHED_FENCE();
+            p3_diag_apply_lazy<A, SEL, R0, 3, -1>(x, e, ci, cj, cij, t3, k, off);
+        } else {
+        FHE_SCHED_FENCE();
+        p3_diag_apply<A, R0, 0, 1>(x, e, ci, cj, cij, t3, k);
+        FHE_SCHED_FENCE();
+        p3_diag_apply<A, R0, 1, 2>(x, e, ci, cj, cij, t3, k);
+        FHE_SCHED_FENCE();
+        p3_diag_apply<A, R0, 2, 3>(x, e, ci, cj, cij, t3, k);
+        FHE_SCHED_FENCE();
+        p3_diag_apply<A, R0, 3, -1>(x, e, ci, cj, cij, t3, k);
+        }
+    } else
+    static_for<0, 4>([&](auto abc) {
+        constexpr int ab = decltype(abc)::value, nx = ab < 3 ? ab + 1 : 3;
+        Tw7<A> &e = d[REFILL ? 0 : ab & 1];
+        FHE_SCHED_FENCE();
+        gs_apply<A, P3<R0, 2, ab>, 0>(x, e.l2, k);
+        if constexpr (REFILL && ab < 3) tw_load<A, true, P3<R0, 2, nx>>(e.l2, t3, k);
+        FHE_SCHED_FENCE();
+        gs_apply<A, P3<R0, 1, ab>, 1>(x, e.l1, k);
+        if constexpr (REFILL && ab < 3) tw_load<A, true, P3<R0, 1, nx>>(e.l1, t3, k);
+        gs_apply<A, P3<R0, 0, ab>, 2>(x, e.l0, k);
+        if constexpr (REFILL && ab < 3) tw_load<A, true, P3<R0, 0, nx>>(e.l0, t3, k);
+        FHE_SCHED_FENCE();
+        if constexpr (!REFILL && ab < 2) tw7_load<A, true, R0, (ab < 2 ? ab + 2 : 3)>(d[ab & 1], t3, k);
+    });
+    FHE_SCHED_FENCE();
+    STAMP(1);
+    // pass 2's first twiddle set is requested BEHIND the exchange when it is 32 registers wide: held across the exchange it pushes
+    // the allocator over 128 registers, and a spilled twiddle comes back through scratch memory behind every load in flight
+    // (vmcnt retires in order): 0.307 -> 0.294 ms per 4096 transforms
+    const int t2 = (w << 4) | (lane >> 2);
+    constexpr bool C3_LATE = sizeof(Tw) > 8;
+    if constexpr (!C3_LATE) tw_load<A, true, P2<R0, 3>>(c3, t2, k);
+    xchg_32(x, lane, wl);
+    STAMP(2);
+    FHE_SCHED_FENCE();
+    if constexpr (C3_LATE) tw_load<A, true, P2<R0, 3>>(c3, t2, k);
+    // the lazy inverse asks for pass 2's second set behind the first layer: with raw products in flight, x, c3 and c2 together (112
+    // registers) leave the allocator three short, and it spills three addresses at the top of the kernel
+    constexpr bool C2_LATE = LZ;
+    if constexpr (!C2_LATE) tw_load<A, true, P2<R0, 2>>(c2, t2, k);
+    if constexpr (LZ) w14_gs_offs<A, SEL>(off, k);
+    w14_gs<LZ, A, P2<R0, 3>, SEL, 3>(x, c3, k, off);
+    FHE_SCHED_FENCE();
+    if constexpr (C2_LATE) tw_load<A, true, P2<R0, 2>>(c2, t2, k);
+    tw_load<A, true, P2<R0, 1>>(c1, t2, k); tw_load<A, true, P2<R0, 0>>(c0, t2, k);
+    w14_gs<LZ, A, P2<R0, 2>, SEL, 4>(x, c2, k, off);
+    FHE_SCHED_FENCE();
+    w14_gs<LZ, A, P2<R0, 1>, SEL, 5>(x, c1, k, off);
+    FHE_SCHED_FENCE();
+    w14_gs<LZ, A, P2<R0, 0>, SEL, 6>(x, c0, k, off);
+    FHE_SCHED_FENCE();
+    STAMP(3);
+    Tw b3[8], b2[4], b1[2], b0[1];  // wave-uniform
+    tw_load<A, true, P1<R0, 3>>(b3, w, k); tw_load<A, true, P1<R0, 2>>(b2, w, k); tw_load<A, true, P1<R0, 1>>(b1, w, k); tw_load<A, true, P1<R0, 0>>(b0, w, k);
+    xchg_21(x, lane, wl);
+    STAMP(4);
+    FHE_SCHED_FENCE();
+    if constexpr (LZ) w14_gs_offs<A, SEL>(off, k);
+    w14_gs<LZ, A, P1<R0, 3>, SEL, 7>(x, b3, k, off);
+    FHE_SCHED_FENCE();
+    w14_gs<LZ, A, P1<R0, 2>, SEL, 8>(x, b2, k, off);
+    FHE_SCHED_FENCE();
+    w14_gs<LZ, A, P1<R0, 1>, SEL, 9>(x, b1, k, off);
+    FHE_SCHED_FENCE();
+    w14_gs<LZ, A, P1<R0, 0>, SEL, 10>(x, b0, k, off);
+    FHE_SCHED_FENCE();
+    STAMP(5);
+    Tw a3[8], a2[4], a1[2], a0[1];
+    if constexpr (R0 == 4) tw_load<A, true, P0<R0, (R0 == 4 ? 3 : 0)>>(a3, 0, k);
+    if constexpr (R0 >= 3) tw_load<A, true, P0<R0, (R0 >= 3 ? 2 : 0)>>(a2, 0, k);
+    if constexpr (R0 >= 2) tw_load<A, true, P0<R0, (R0 >= 2 ? 1 : 0)>>(a1, 0, k);
+    if constexpr (PFX) tw_load<A, true, P0<R0, 0>>(a0, 0, k);
+    xchg_10<R0, w14_pairs<A, R0>()>(x, t, w, lds);
+    STAMP(6);
+    if constexpr (LZ) w14_gs_offs<A, SEL>(off, k);
+    if constexpr (R0 == 4) {
+        FHE_SCHED_FENCE();
+        w14_gs<LZ, A, P0<R0, (R0 == 4 ? 3 : 0)>, SEL, 11>(x, a3, k, off);
+    }
+    if constexpr (R0 >= 3) {
+        FHE_SCHED_FENCE();
+        w14_gs<LZ, A, P0<R0, (R0 >= 3 ? 2 : 0)>, SEL, 8 + R0>(x, a2, k, off);
+    }
+    if constexpr (R0 >= 2) {
+        FHE_SCHED_FENCE();
+        w14_gs<LZ, A, P0<R0, (R0 >= 2 ? 1 : 0)>, SEL, 9 + R0>(x, a1, k, off);
+    }
+    // the last layer leaves canonical values: a whole ring folds n^-1 into it (the difference branch multiplies by twi[1] n^-1),
+    // a sub-transform of a larger ring is not scaled here at all
+    STAMP(7);
+    typename A::TwReg wlast{};
+    if constexpr (PFX) wlast = A::prep(a0[0]);
+    constexpr int LAST_PH = A::GS_SPAN > 0 ? (10 + R0) % (A::GS_SPAN > 0 ? A::GS_SPAN : 1) : 1;  // layers since the sums were last folded
+    constexpr int HALF = 1 << (R0 - 1), REPS = 32 >> R0, CH = HALF < 4 ? HALF : 4;
+    if constexpr (LZ) w14_gs_offs<A, SEL>(off, k);
+    auto last = [&](auto oc) {  // the butterfly of registers (o, o + HALF)
+        constexpr int o = decltype(oc)::value;
+        if constexpr (LZ) {
+            typedef typename A::GsLazy G;
+            constexpr bool FX = G::template fx<R0, SEL::PAIRS, IN>(10 + R0, o), FY = G::template fy<R0, SEL::PAIRS, IN>(10 + R0, o);
+            constexpr int MI = G::template mi<R0, SEL::PAIRS, IN>(10 + R0, o);
+            static_assert(MI >= 0 && MI < W14_OFFS, "no offset for this butterfly");
+            if constexpr (PFX) A::template gs_last_plain_lazy<FX, FY>(x[o], x[o + HALF], wlast, k.m, off[MI]);
+            else A::template gs_last_scaled_lazy<FX, FY>(x[o], x[o + HALF], k.ninv, k.ninv_w, k.m, off[MI]);
+        } else {
+            if constexpr (PFX) A::template gs_last_plain<LAST_PH>(x[o], x[o + HALF], wlast, k);
+            else A::template gs_last_scaled<LAST_PH>(x[o], x[o + HALF], k);
+        }
+    };
+    if constexpr (w14_pairs<A, R0>()) {
+        // the replicas (hi, i0 = 0) and (hi, 1) of a butterfly finish together and leave as two 16-byte stores; (up to) four
+        // butterflies at a time, stored as they finish
+        constexpr int CHP = CH < 2 ? 1 : CH / 2;
+        static_for<0, (REPS / 2) * (HALF / CHP)>([&](auto cc) {
+            constexpr int hi = decltype(cc)::value / (HALF / CHP), j0 = (decltype(cc)::value % (HALF / CHP)) * CHP;
+            FHE_SCHED_FENCE();
+            static_for<j0, j0 + CHP>([&](auto jc) {
+                constexpr int j = decltype(jc)::value, o = ((2 * hi) << R0) + j, o1 = o + (1 << R0);
+                last(std::integral_constant<int, o>{});
+                last(std::integral_constant<int, o1>{});
+                u64 *p = g + ((hi << (7 + R0)) | (t << 1));
+                *reinterpret_cast<ulonglong2 *>(p + (j << 11)) = make_ulonglong2(x[o], x[o1]);
+                *reinterpret_cast<ulonglong2 *>(p + ((j + HALF) << 11)) = make_ulonglong2(x[o + HALF], x[o1 + HALF]);
+            });
+        });
+    } else {
+        static_for<0, REPS * (HALF / CH)>([&](auto cc) {  // (up to) four butterflies at a time, stored as they finish
+            constexpr int pass = decltype(cc)::value / (HALF / CH), j0 = (decltype(cc)::value % (HALF / CH)) * CH;
+            FHE_SCHED_FENCE();
+            static_for<j0, j0 + CH>([&](auto jc) {
+                constexpr int j = decltype(jc)::value, o = (pass << R0) + j;
+                last(std::integral_constant<int, o>{});
+                g[(j << 11) | (pass << (6 + R0)) | t] = x[o];
+                g[((j + HALF) << 11) | (pass << (6 + R0)) | t] = x[o + HALF];
+            });
+        });
+    }
+    STAMP(8);
+#ifdef NTT14_STAMPS
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+    STAMP(9);
+    STAMP_REAL(11);
+    STAMP_FLUSH();
+}
+
+// the inverse of this instantiation: lazy where w14_lazy_inv_at says so
+template <class A, bool PFX, int R0, int IN, bool FUSED>
+__device__ __forceinline__ void inv_any(u64 (&x)[32], Tw7<A> (&d)[2], u64 *__restrict__ g, const typename A::K &k, u64 *lds, u64 *wl,
+                                        const int t, const int lane, const int w STAMP_ENTRY_PARAM) {
+    if constexpr (w14_lazy_inv_at<A, PFX, R0, IN, FUSED>()) inv_one_lazy<A, PFX, R0, IN>(x, d, g, k, lds, wl, t, lane, w STAMP_ENTRY_ARG);
+    else inv_one<A, PFX, R0>(x, d, g, k, lds, wl, t, lane, w STAMP_ENTRY_ARG);
+}
+
 // Which sub-polynomial a workgroup takes.  A launch over several moduli (the RNS limbs of CKKS: polynomial p uses descs[p % n_desc])
 // comes as a 2-D grid, y = the modulus, x = that modulus's sub-polynomials across the batch: workgroups are dispatched x first, so
 // the ~512 that are resident together share a few twiddle tables (768 KiB each at 60 bits) instead of all n_desc of them -- 16
@@ -818,7 +1077,7 @@ __global__ __launch_bounds__(w14::threads<R0>(), 4) void ntt14w_inv_kernel(u64 *
     } else {
         w14::load_p3<0>(x, src); w14::load_p3<1>(x, src); w14::load_p3<2>(x, src); w14::load_p3<3>(x, src);
     }
-    w14::inv_one<A, PFX, R0>(x, d, g, k, lds, lds + w * w14::WSLOTS, t, lane, w STAMP_ENTRY_ARG);
+    w14::inv_any<A, PFX, R0, MUL ? 1 : 0, false>(x, d, g, k, lds, lds + w * w14::WSLOTS, t, lane, w STAMP_ENTRY_ARG);
 }
 
 // util/src/ring/fft/zq.rs:14-19 with the left operand never leaving the chip: forward transform of polynomial s, pointwise product
@@ -867,7 +1126,7 @@ __global__ __launch_bounds__(w14::threads<R0>(), 4) void ntt14w_mul_kernel(u64 *
     if constexpr (w14::w14_p3_diag<A>()) w14::p3_diag_load<A, R0, 0>(reinterpret_cast<uint4(&)[7]>(d[0]), (wi << 8) | lane_i, k);
     else w14::tw7_load<A, true, R0, 0>(d[0], (wi << 8) | lane_i, k);
     if constexpr (!w14::w14_p3_diag<A>() && !w14::w14_p3_refill<A>()) w14::tw7_load<A, true, R0, 1>(d[1], (wi << 8) | lane_i, k);
-    w14::inv_one<A, false, R0>(x, d, g, k, lds, lds + wi * w14::WSLOTS, ti, lane_i, wi STAMP_ENTRY_ARG);
+    w14::inv_any<A, false, R0, 1, true>(x, d, g, k, lds, lds + wi * w14::WSLOTS, ti, lane_i, wi STAMP_ENTRY_ARG);
 }
 
 }  // namespace fhe

@@ -17,6 +17,9 @@ constexpr size_t N14_LDS_BYTES = w14::LDS_BYTES;
 struct DSOld : ArithDS<60> {  // the pass-0 side as it was dealt before the coefficient pairs: thread = i[8:0], 8-byte HBM and LDS accesses (same results)
     static constexpr bool W14_OLD_DEAL = true;
 };
+struct DSFoldedInv : ArithDS<60> {  // the inverse as it was before the lazy butterflies: every product folded, sums every third layer (same results)
+    static constexpr bool W14_FOLDED_GS = true;
+};
 struct DSNoTw : ArithDS<60> {  // ablation: butterflies with a computed twiddle, no twiddle loads (wrong results, same work)
     template <bool INV> static __device__ __forceinline__ TwRaw fetch(const K &k, int idx) { return uint4{k.ninv.x + (unsigned)idx, k.ninv.y, k.ninv.z ^ (unsigned)idx, k.ninv.w}; }
 };
@@ -34,6 +37,7 @@ struct DSSkipV : ArithDS<60> {  // as DSSkip, but every word of a computed twidd
 };
 struct DSNone : ArithDS<60> {  // ablation: HBM traffic + exchanges only
     static constexpr bool W14_EAGER_CT = true;  // its own `ct` below, not the lazy butterflies
+    static constexpr bool W14_FOLDED_GS = true;  // ... and its own `gs`
     static __device__ __forceinline__ void ct(u64 &X, u64 &Y, const TwReg &, const K &) { X ^= 1; Y ^= 1; }
     template <int PH> static __device__ __forceinline__ void gs(u64 &X, u64 &Y, const TwReg &, const K &) { X ^= 1; Y ^= 1; }
     template <bool INV> static __device__ __forceinline__ TwRaw fetch(const K &, int idx) { return uint4{(unsigned)idx, 1u, 2u, 3u}; }
@@ -141,6 +145,7 @@ int main(int argc, char **argv) {
     V vs[] = {
         {"wave-local, PM60", ntt14w_fwd_kernel<ArithPM<60>, false>, ntt14w_inv_kernel<ArithPM<60>, false>, 0, 0, 1},
         {"wave-local, DS60", ntt14w_fwd_kernel<ArithDS<60>, false>, ntt14w_inv_kernel<ArithDS<60>, false>, 0, 0, 1},
+        {"DS60, folded inverse (old)", ntt14w_fwd_kernel<DSFoldedInv, false>, ntt14w_inv_kernel<DSFoldedInv, false>, 0, 0, 1},
         {"DS60, 8-byte pass-0 side (old)", ntt14w_fwd_kernel<DSOld, false>, ntt14w_inv_kernel<DSOld, false>, 0, 0, 1},
         {"wave-local, Shoup", ntt14w_fwd_kernel<ArithShoup, false>, ntt14w_inv_kernel<ArithShoup, false>, 0, 0, 1},
         {"wave-local DS60, no twiddle loads", ntt14w_fwd_kernel<DSNoTw, false>, ntt14w_inv_kernel<DSNoTw, false>, 0, 0, 1},
@@ -200,7 +205,7 @@ int main(int argc, char **argv) {
         printf("%-32s fwd %.4f ms %5.0f GB/s (%.3f of 8 TB/s) | inv %.4f ms %5.0f GB/s (%.3f)\n", v.name, v.sf / reps, bytes / (v.sf / reps * 1e-3) / 1e9,
                bytes / (v.sf / reps * 1e-3) / 8e12, v.si / reps, bytes / (v.si / reps * 1e-3) / 1e9, bytes / (v.si / reps * 1e-3) / 8e12);
 #ifdef NTT14_STAMPS
-    for (int vi : {0, 1, 2})  // PM60, DS60 (coefficient pairs), DS60 with the 8-byte pass-0 side
+    for (int vi : {0, 1, 3})  // PM60, DS60 (coefficient pairs), DS60 with the 8-byte pass-0 side
     for (int dir : {0, 1}) {   // where does a workgroup spend its life?
         auto &v = vs[vi];
         for (int r = 0; r < 40; ++r) hipLaunchKernelGGL(dir ? v.i : v.f, dim3(GRID(v)), dim3(N14_THREADS), N14_LDS_BYTES, 0, d, (const ModDesc *)d_desc, 1u, (unsigned)batch, 0, NttIo());
