@@ -52,18 +52,6 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_wave_barrier();
     asm volatile("" ::: "memory");
 }
-// An exchange is a short burst of LDS instructions: latency critical, while the other waves of the SIMD are usually inside a
-// butterfly pass (throughput bound).  W14_XCHG_PRIO: exchanging waves take issue priority (lab switch; see DESIGN.md for the A/B).
-#ifndef W14_XCHG_PRIO
-#define W14_XCHG_PRIO 0
-#endif
-#if W14_XCHG_PRIO
-#define W14_PRIO_UP() __builtin_amdgcn_s_setprio(3)
-#define W14_PRIO_DOWN() __builtin_amdgcn_s_setprio(0)
-#else
-#define W14_PRIO_UP()
-#define W14_PRIO_DOWN()
-#endif
 
 // The pass-0 side deals a thread coefficient PAIRS (i, i + 1): 16-byte HBM and LDS accesses (R0 <= 3; see the table above).
 // Lab switch: a policy that declares W14_OLD_DEAL gets the earlier dealing (thread = i[5 + R0:0], 8-byte accesses) for its own
@@ -189,18 +177,11 @@ __device__ unsigned long long g_stamps[4096][16];
 // bits, pass = the 5 - R0 passive bits, i[10] first.  PAIRS: the last passive bit is i0 (R0 = 3: (i10, i0)), thread t = i[6 + R0:1];
 // otherwise they are the bits below bit 11 (R0 = 3: (i10, i9), R0 = 4: i10) and thread t = the remaining low bits.
 // Slot of a coefficient in the half image (bit 10 removed): (n << 10) | i[9:0]; lanes keep i[5:0]: conflict free unpadded.
-#ifdef W14_LAB_NO_BARRIER  // developer lab only: what do the workgroup barriers of the cross-wave exchange cost? (results wrong)
-#define W14_SYNC() wave_sync()
-#else
-#define W14_SYNC() __syncthreads()
-#endif
-
 template <int R0, bool PAIRS>
 __device__ __forceinline__ void xchg_01(u64 (&x)[32], int t, int w, u64 *lds) {
     constexpr int PB = 5 - R0, NLOW = 1 << (PB - 1);  // register bits below bit 10 (i9 for R0 = 3, none for R0 = 4)
     u64 *wp = lds + (PAIRS ? 2 * t : t), *rp = lds + (w << 10) + (t & 63);  // constant offsets from here on: immediates of the ds instructions
     u64 y[32];
-    W14_PRIO_UP();
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         if constexpr (PAIRS) {  // pass = (i10 = h, lo, i0): the pair (i0 = 0, 1) leaves as one ds_write_b128 at slot (n << 10) | (lo << (7 + R0)) | 2 t
@@ -217,15 +198,14 @@ __device__ __forceinline__ void xchg_01(u64 (&x)[32], int t, int w, u64 *lds) {
 #pragma unroll
                 for (int n = 0; n < (1 << R0); ++n) wp[(n << 10) | (lo << (10 - (PB - 1)))] = x[((((h << (PB - 1)) | lo)) << R0) | n];
         }
-        W14_SYNC();
+        __syncthreads();
 #pragma unroll
         for (int m = 0; m < 16; ++m) {  // m = (i9 i8 i7 i6)
             const int n4 = (h << 3) | (m >> 1), s = m & 1;
             y[(s << 4) | n4] = rp[m << 6];
         }
-        W14_SYNC();
+        __syncthreads();
     }
-    W14_PRIO_DOWN();
 #pragma unroll
     for (int r = 0; r < 32; ++r) x[r] = y[r];
 }
@@ -235,8 +215,7 @@ __device__ __forceinline__ void xchg_10(u64 (&x)[32], int t, int w, u64 *lds) {
     constexpr int PB = 5 - R0, NLOW = 1 << (PB - 1);
     u64 *rp = lds + (PAIRS ? 2 * t : t), *wp = lds + (w << 10) + (t & 63);
     u64 y[32];
-    W14_PRIO_UP();
-    W14_SYNC();  // every wave has left its private region
+    __syncthreads();  // every wave has left its private region
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
 #pragma unroll
@@ -244,7 +223,7 @@ __device__ __forceinline__ void xchg_10(u64 (&x)[32], int t, int w, u64 *lds) {
             const int n4 = (h << 3) | (m >> 1), s = m & 1;
             wp[m << 6] = x[(s << 4) | n4];
         }
-        W14_SYNC();
+        __syncthreads();
         if constexpr (PAIRS) {  // one ds_read_b128 per pair, the slots of xchg_01
 #pragma unroll
             for (int lo = 0; lo < NLOW / 2; ++lo)
@@ -260,9 +239,8 @@ __device__ __forceinline__ void xchg_10(u64 (&x)[32], int t, int w, u64 *lds) {
 #pragma unroll
                 for (int n = 0; n < (1 << R0); ++n) y[((((h << (PB - 1)) | lo)) << R0) | n] = rp[(n << 10) | (lo << (10 - (PB - 1)))];
         }
-        if (h == 0) W14_SYNC();
+        if (h == 0) __syncthreads();
     }
-    W14_PRIO_DOWN();
 #pragma unroll
     for (int r = 0; r < 32; ++r) x[r] = y[r];
 }
@@ -272,7 +250,6 @@ __device__ __forceinline__ void xchg_12(u64 (&x)[32], int lane, u64 *wl) {
     u64 *wp = wl + lane;
     const u64 *rp = wl + 68 * (lane >> 2) + (lane & 3);  // as pass-2 lane (i[10:7], i[1:0]); + 4 (i[5:2])
     u64 y[32];
-    W14_PRIO_UP();
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
 #pragma unroll
@@ -283,7 +260,6 @@ __device__ __forceinline__ void xchg_12(u64 (&x)[32], int lane, u64 *wl) {
             y[((r4 & 1) << 4) | (h << 3) | (r4 >> 1)] = rp[4 * r4];
         wave_sync();
     }
-    W14_PRIO_DOWN();
 #pragma unroll
     for (int r = 0; r < 32; ++r) x[r] = y[r];
 }
@@ -292,7 +268,6 @@ __device__ __forceinline__ void xchg_21(u64 (&x)[32], int lane, u64 *wl) {
     u64 *wp = wl + 68 * (lane >> 2) + (lane & 3);
     const u64 *rp = wl + lane;
     u64 y[32];
-    W14_PRIO_UP();
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
 #pragma unroll
@@ -302,7 +277,6 @@ __device__ __forceinline__ void xchg_21(u64 (&x)[32], int lane, u64 *wl) {
         for (int n4 = 0; n4 < 16; ++n4) y[(h << 4) | n4] = rp[68 * n4];
         wave_sync();
     }
-    W14_PRIO_DOWN();
 #pragma unroll
     for (int r = 0; r < 32; ++r) x[r] = y[r];
 }
@@ -316,7 +290,6 @@ __device__ __forceinline__ void xchg_23(u64 (&x)[32], int lane, u64 *wl) {
     // as pass-3 lane i[8:3]: 34 i8 + 2 i[6:3] + i7;  + 68 (i10 i9 i1 i0)
     const u64 *rp = wl + 34 * (lane >> 5) + 2 * (lane & 15) + ((lane >> 4) & 1);
     u64 y[32];
-    W14_PRIO_UP();
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
 #pragma unroll
@@ -327,7 +300,6 @@ __device__ __forceinline__ void xchg_23(u64 (&x)[32], int lane, u64 *wl) {
             y[((R >> 2) << 3) | (h << 2) | (R & 3)] = rp[68 * R];
         wave_sync();
     }
-    W14_PRIO_DOWN();
 #pragma unroll
     for (int r = 0; r < 32; ++r) x[r] = y[r];
 }
@@ -338,7 +310,6 @@ __device__ __forceinline__ void xchg_32(u64 (&x)[32], int lane, u64 *wl) {
     const u64 *rp = wl + 17 * lane;                        // as pass-2 lane; + i[6:3]
     u64 *wp = wl + 68 * (lane >> 4) + (lane & 15);         // as pass-3 lane i[8:3]: 17 ((i8 i7) << 2) + i[6:3]; + 17 ((i10 i9) << 4 | (i1 i0))
     u64 y[32];
-    W14_PRIO_UP();
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
 #pragma unroll
@@ -348,7 +319,6 @@ __device__ __forceinline__ void xchg_32(u64 (&x)[32], int lane, u64 *wl) {
         for (int c = 0; c < 16; ++c) y[(h << 4) | c] = rp[c];
         wave_sync();
     }
-    W14_PRIO_DOWN();
 #pragma unroll
     for (int r = 0; r < 32; ++r) x[r] = y[r];
 }
@@ -360,12 +330,9 @@ template <int R0, int l> using P2 = Unit<R0 + 4, 4, l, 0, 2, 16, true>;
 template <int R0, int l, int AB> using P3 = Unit<R0 + 8, 3, l, AB, 1, 8, false, 6>;  // block prefix (w << 8) | (AB << 6) | lane
 
 // pass 3 of the inverse: refill each layer's twiddle slot one replica ahead (true) or fetch whole replicas two ahead (false)
-#ifndef W14_P3_REFILL
-#define W14_P3_REFILL -1
-#endif
 template <class A>
 __device__ __host__ constexpr bool w14_p3_refill() {
-    return W14_P3_REFILL < 0 ? std::is_same<typename A::TwRaw, uint4>::value : W14_P3_REFILL != 0;
+    return std::is_same<typename A::TwRaw, uint4>::value;
 }
 
 // one replica's pass-3 twiddles (layers 11, 12, 13)
@@ -388,9 +355,6 @@ __device__ __forceinline__ void load_p0(u64 (&x)[32], const u64 *__restrict__ g,
 #pragma unroll
     for (int r = 0; r < 32; ++r) {
         const int n = r & ((1 << R0) - 1), pass = r >> R0;
-#ifdef W14_ABLATE_NO_GLOBAL  // developer lab only: no HBM traffic
-        x[r] = (u64)(t + r) * 0x9E3779B97F4A7C15ull >> 5;
-#else
         if constexpr (PAIRS) {
             if (pass & 1) continue;
             const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(g + ((n << 11) | ((pass >> 1) << (7 + R0)) | (t << 1)));
@@ -398,7 +362,6 @@ __device__ __forceinline__ void load_p0(u64 (&x)[32], const u64 *__restrict__ g,
         } else {
             x[r] = g[(n << 11) | (pass << (6 + R0)) | t];
         }
-#endif
     }
 }
 // HBM side of pass 3 (inverse loads): register (ab, n3) <-> coefficient (w << 11) | (ab << 9) | (lane << 3) | n3
@@ -447,9 +410,6 @@ __device__ __forceinline__ void store_p3(u64 (&x)[32], u64 *__restrict__ dst_wav
     for (int kk = 0; kk < 4; ++kk) {
         ulonglong2 v;
         v.x = x[AB * 8 + 2 * kk]; v.y = x[AB * 8 + 2 * kk + 1];
-#ifdef W14_ABLATE_NO_GLOBAL
-        if (v.x == 0xdeadbeefcafef00dull)
-#endif
         *reinterpret_cast<ulonglong2 *>(dst_wave + (AB << 9) + 128 * kk + 2 * lane) = v;
     }
 }
@@ -583,11 +543,7 @@ __device__ __forceinline__ void fwd_one(u64 (&x)[32], u64 *__restrict__ g, const
 // are bit-identical.  Bounds (inputs canonical): every sum stays below 8.2 q < 2^64; products come back below q + 9c.
 template <class A>
 __device__ __host__ constexpr bool w14_p3_diag() {
-#ifdef W14_NO_DIAG
-    return false;
-#else
     return std::is_same<typename A::TwRaw, uint4>::value;
-#endif
 }
 
 template <class A, int R0, int AB>
@@ -656,166 +612,30 @@ __device__ __forceinline__ void p3_diag_apply_lazy(u64 (&x)[32], uint4 (&e)[7], 
     });
 }
 
+// one diagonal block by the arithmetic of this instantiation (as w14_gs for the plain layers)
+template <bool LZ, class A, class SEL, int R0, int AB, int NEXT>
+__device__ __forceinline__ void w14_p3(u64 (&x)[32], uint4 (&e)[7], const uint4 &ci, const uint4 &cj, const uint4 &cij, int t3,
+                                       const typename A::K &k, const u64 (&off)[W14_OFFS]) {
+    if constexpr (LZ) p3_diag_apply_lazy<A, SEL, R0, AB, NEXT>(x, e, ci, cj, cij, t3, k, off);
+    else p3_diag_apply<A, R0, AB, NEXT>(x, e, ci, cj, cij, t3, k);
+}
+
 // One inverse transform; x[] arrives loaded in the pass-3 layout, d[] with the pass-3 twiddles of replicas 0 and 1 (fetched BEFORE
-// the coefficients: vmcnt retires in order, and the twiddles are L2 hits).
-template <class A, bool PFX, int R0>
+// the coefficients: vmcnt retires in order, and the twiddles are L2 hits).  LZ (the caller's w14_lazy_inv_at): the lazy butterflies by
+// the schedule of this ring size, dealing and input (IN: 0 = canonical evaluations, 1 = mulvar outputs); otherwise every product is
+// folded (A::gs).  Passes, exchanges, twiddle order and stores are the same for both; each `if constexpr (LZ)` below says why the two
+// differ there (profiles/inverse_merge_identity.txt: every instantiation compiles to the instructions it had from two separate bodies).
+template <class A, bool PFX, int R0, int IN, bool LZ>
 __device__ __forceinline__ void inv_one(u64 (&x)[32], Tw7<A> (&d)[2], u64 *__restrict__ g, const typename A::K &k, u64 *lds, u64 *wl,
                                         const int t, const int lane, const int w STAMP_ENTRY_PARAM) {
     typedef typename A::TwRaw Tw;
-    const int t2 = (w << 4) | (lane >> 2), t3 = (w << 8) | lane;
-    STAMP_DECL;
-    STAMP_REAL(10);
-    STAMP(0);
-    // pass 3: layers 13, 12, 11.  Eight-byte twiddles are fetched two replicas ahead (d[] arrives holding replicas 0 and 1); sixteen-
-    // byte ones (ArithDS) refill each layer's slot for the NEXT replica as soon as the layer has used it -- 28 registers instead
-    // of 56 beside the 64 of x.  The two schemes measure the same (tools/ntt_lab2.hip: 0.331 / 0.333 ms); the refill is kept for the
-    // registers it leaves free.
-    constexpr bool REFILL = w14_p3_refill<A>();
-    Tw c3[8], c2[4], c1[2], c0[1];
-    if constexpr (w14_p3_diag<A>()) {
-        uint4(&e)[7] = reinterpret_cast<uint4(&)[7]>(d[0]);   // Tw7 of a 16-byte policy = seven uint4
-        const uint4 ci = A::template fetch<true>(k, 1), cj = A::template fetch<true>(k, 2), cij = A::template fetch<true>(k, 3);
-        FHE_SCHED_FENCE();
-        p3_diag_apply<A, R0, 0, 1>(x, e, ci, cj, cij, t3, k);
-        FHE_SCHED_FENCE();
-        p3_diag_apply<A, R0, 1, 2>(x, e, ci, cj, cij, t3, k);
-        FHE_SCHED_FENCE();
-        p3_diag_apply<A, R0, 2, 3>(x, e, ci, cj, cij, t3, k);
-        FHE_SCHED_FENCE();
-        p3_diag_apply<A, R0, 3, -1>(x, e, ci, cj, cij, t3, k);
-    } else
-    static_for<0, 4>([&](auto abc) {
-        constexpr int ab = decltype(abc)::value, nx = ab < 3 ? ab + 1 : 3;
-        Tw7<A> &e = d[REFILL ? 0 : ab & 1];
-        FHE_SCHED_FENCE();
-        gs_apply<A, P3<R0, 2, ab>, 0>(x, e.l2, k);
-        if constexpr (REFILL && ab < 3) tw_load<A, true, P3<R0, 2, nx>>(e.l2, t3, k);
-        FHE_SCHED_FENCE();
-        gs_apply<A, P3<R0, 1, ab>, 1>(x, e.l1, k);
-        if constexpr (REFILL && ab < 3) tw_load<A, true, P3<R0, 1, nx>>(e.l1, t3, k);
-        gs_apply<A, P3<R0, 0, ab>, 2>(x, e.l0, k);
-        if constexpr (REFILL && ab < 3) tw_load<A, true, P3<R0, 0, nx>>(e.l0, t3, k);
-        FHE_SCHED_FENCE();
-        if constexpr (!REFILL && ab < 2) tw7_load<A, true, R0, (ab < 2 ? ab + 2 : 3)>(d[ab & 1], t3, k);
-    });
-    FHE_SCHED_FENCE();
-    STAMP(1);
-    // pass 2's first twiddle set is requested BEHIND the exchange when it is 32 registers wide: held across the exchange it pushes
-    // the allocator over 128 registers, and a spilled twiddle comes back through scratch memory behind every load in flight
-    // (vmcnt retires in order): 0.307 -> 0.294 ms per 4096 transforms
-    constexpr bool C3_LATE = sizeof(Tw) > 8;
-    if constexpr (!C3_LATE) tw_load<A, true, P2<R0, 3>>(c3, t2, k);
-    xchg_32(x, lane, wl);
-    STAMP(2);
-    FHE_SCHED_FENCE();
-    if constexpr (C3_LATE) tw_load<A, true, P2<R0, 3>>(c3, t2, k);
-    tw_load<A, true, P2<R0, 2>>(c2, t2, k);
-    gs_apply<A, P2<R0, 3>, 3>(x, c3, k);
-    FHE_SCHED_FENCE();
-    tw_load<A, true, P2<R0, 1>>(c1, t2, k); tw_load<A, true, P2<R0, 0>>(c0, t2, k);
-    gs_apply<A, P2<R0, 2>, 4>(x, c2, k);
-    FHE_SCHED_FENCE();
-    gs_apply<A, P2<R0, 1>, 5>(x, c1, k);
-    FHE_SCHED_FENCE();
-    gs_apply<A, P2<R0, 0>, 6>(x, c0, k);
-    FHE_SCHED_FENCE();
-    STAMP(3);
-    Tw b3[8], b2[4], b1[2], b0[1];  // wave-uniform
-    tw_load<A, true, P1<R0, 3>>(b3, w, k); tw_load<A, true, P1<R0, 2>>(b2, w, k); tw_load<A, true, P1<R0, 1>>(b1, w, k); tw_load<A, true, P1<R0, 0>>(b0, w, k);
-    xchg_21(x, lane, wl);
-    STAMP(4);
-    FHE_SCHED_FENCE();
-    gs_apply<A, P1<R0, 3>, 7>(x, b3, k);
-    FHE_SCHED_FENCE();
-    gs_apply<A, P1<R0, 2>, 8>(x, b2, k);
-    FHE_SCHED_FENCE();
-    gs_apply<A, P1<R0, 1>, 9>(x, b1, k);
-    FHE_SCHED_FENCE();
-    gs_apply<A, P1<R0, 0>, 10>(x, b0, k);
-    FHE_SCHED_FENCE();
-    STAMP(5);
-    Tw a3[8], a2[4], a1[2], a0[1];
-    if constexpr (R0 == 4) tw_load<A, true, P0<R0, (R0 == 4 ? 3 : 0)>>(a3, 0, k);
-    if constexpr (R0 >= 3) tw_load<A, true, P0<R0, (R0 >= 3 ? 2 : 0)>>(a2, 0, k);
-    if constexpr (R0 >= 2) tw_load<A, true, P0<R0, (R0 >= 2 ? 1 : 0)>>(a1, 0, k);
-    if constexpr (PFX) tw_load<A, true, P0<R0, 0>>(a0, 0, k);
-    xchg_10<R0, w14_pairs<A, R0>()>(x, t, w, lds);
-    STAMP(6);
-    if constexpr (R0 == 4) {
-        FHE_SCHED_FENCE();
-        gs_apply<A, P0<R0, (R0 == 4 ? 3 : 0)>, 11>(x, a3, k);
-    }
-    if constexpr (R0 >= 3) {
-        FHE_SCHED_FENCE();
-        gs_apply<A, P0<R0, (R0 >= 3 ? 2 : 0)>, 8 + R0>(x, a2, k);
-    }
-    if constexpr (R0 >= 2) {
-        FHE_SCHED_FENCE();
-        gs_apply<A, P0<R0, (R0 >= 2 ? 1 : 0)>, 9 + R0>(x, a1, k);
-    }
-    // the last layer leaves canonical values: a whole ring folds n^-1 into it (the difference branch multiplies by twi[1] n^-1),
-    // a sub-transform of a larger ring is not scaled here at all
-    STAMP(7);
-    typename A::TwReg wlast{};
-    if constexpr (PFX) wlast = A::prep(a0[0]);
-    constexpr int LAST_PH = A::GS_SPAN > 0 ? (10 + R0) % (A::GS_SPAN > 0 ? A::GS_SPAN : 1) : 1;  // layers since the sums were last folded
-    constexpr int HALF = 1 << (R0 - 1), REPS = 32 >> R0, CH = HALF < 4 ? HALF : 4;
-    if constexpr (w14_pairs<A, R0>()) {
-        // the replicas (hi, i0 = 0) and (hi, 1) of a butterfly finish together and leave as two 16-byte stores; (up to) four
-        // butterflies at a time, stored as they finish
-        constexpr int CHP = CH < 2 ? 1 : CH / 2;
-        static_for<0, (REPS / 2) * (HALF / CHP)>([&](auto cc) {
-            constexpr int hi = decltype(cc)::value / (HALF / CHP), j0 = (decltype(cc)::value % (HALF / CHP)) * CHP;
-            FHE_SCHED_FENCE();
-#pragma unroll
-            for (int j = j0; j < j0 + CHP; ++j) {
-                const int o = ((2 * hi) << R0) + j, o1 = o + (1 << R0);
-                if constexpr (PFX) {
-                    A::template gs_last_plain<LAST_PH>(x[o], x[o + HALF], wlast, k);
-                    A::template gs_last_plain<LAST_PH>(x[o1], x[o1 + HALF], wlast, k);
-                } else {
-                    A::template gs_last_scaled<LAST_PH>(x[o], x[o + HALF], k);
-                    A::template gs_last_scaled<LAST_PH>(x[o1], x[o1 + HALF], k);
-                }
-                u64 *p = g + ((hi << (7 + R0)) | (t << 1));
-                *reinterpret_cast<ulonglong2 *>(p + (j << 11)) = make_ulonglong2(x[o], x[o1]);
-                *reinterpret_cast<ulonglong2 *>(p + ((j + HALF) << 11)) = make_ulonglong2(x[o + HALF], x[o1 + HALF]);
-            }
-        });
-    } else {
-        static_for<0, REPS * (HALF / CH)>([&](auto cc) {  // (up to) four butterflies at a time, stored as they finish
-            constexpr int pass = decltype(cc)::value / (HALF / CH), j0 = (decltype(cc)::value % (HALF / CH)) * CH;
-            FHE_SCHED_FENCE();
-#pragma unroll
-            for (int j = j0; j < j0 + CH; ++j) {
-                const int o = (pass << R0) + j;
-                if constexpr (PFX) A::template gs_last_plain<LAST_PH>(x[o], x[o + HALF], wlast, k);
-                else A::template gs_last_scaled<LAST_PH>(x[o], x[o + HALF], k);
-                g[(j << 11) | (pass << (6 + R0)) | t] = x[o];
-                g[((j + HALF) << 11) | (pass << (6 + R0)) | t] = x[o + HALF];
-            }
-        });
-    }
-    STAMP(8);
-#ifdef NTT14_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-    STAMP(9);
-    STAMP_REAL(11);
-    STAMP_FLUSH();
-}
-
-// ... with the lazy butterflies (w14_lazy_inv_at): the same passes, exchanges, twiddle order and last layer; IN: 0 = canonical
-// inputs, 1 = mulvar outputs.  Kept beside inv_one, not inside it, so that every other instantiation compiles exactly as before.
-template <class A, bool PFX, int R0, int IN>
-__device__ __forceinline__ void inv_one_lazy(u64 (&x)[32], Tw7<A> (&d)[2], u64 *__restrict__ g, const typename A::K &k, u64 *lds, u64 *wl,
-                                        const int t, const int lane, const int w STAMP_ENTRY_PARAM) {
-    typedef typename A::TwRaw Tw;
+    // pass 2's twiddle prefix is computed here by the folded inverse and where pass 2 begins by the lazy one: hipcc's schedule follows the
+    // place, and either place for both changes the instruction streams of 35 to 38 instantiations (registers and scratch among them)
+    int t2 = 0;
+    if constexpr (!LZ) t2 = (w << 4) | (lane >> 2);
     const int t3 = (w << 8) | lane;
-    // lazy butterflies (w14_lazy_inv) by the schedule of this ring size, dealing and input; IN: 0 = canonical, 1 = mulvar outputs
-    constexpr bool LZ = true;
     typedef GsSel<R0, w14_pairs<A, R0>(), IN> SEL;
-    u64 off[W14_OFFS] = {};
+    u64 off[W14_OFFS] = {};  // the schedule's offsets m q (lazy only)
     if constexpr (LZ) {
         static_assert(w14_p3_diag<A>(), "the lazy inverse is written for the diagonal form of pass 3");
         static_assert(A::GsLazy::template valid<R0, w14_pairs<A, R0>(), IN>(), "no valid lazy schedule");
@@ -833,25 +653,14 @@ __device__ __forceinline__ void inv_one_lazy(u64 (&x)[32], Tw7<A> (&d)[2], u64 *
     if constexpr (w14_p3_diag<A>()) {
         uint4(&e)[7] = reinterpret_cast<uint4(&)[7]>(d[0]);   // Tw7 of a 16-byte policy = seven uint4
         const uint4 ci = A::template fetch<true>(k, 1), cj = A::template fetch<true>(k, 2), cij = A::template fetch<true>(k, 3);
-        if constexpr (LZ) {
-            FHE_SCHED_FENCE();
-            p3_diag_apply_lazy<A, SEL, R0, 0, 1>(x, e, ci, cj, cij, t3, k, off);
-            FHE_SCHED_FENCE();
-            p3_diag_apply_lazy<A, SEL, R0, 1, 2>(x, e, ci, cj, cij, t3, k, off);
-            FHE_SCHED_FENCE();
-            p3_diag_apply_lazy<A, SEL, R0, 2, 3>(x, e, ci, cj, cij, t3, k, off);
-            FHE_SCHED_FENCE();
-            p3_diag_apply_lazy<A, SEL, R0, 3, -1>(x, e, ci, cj, cij, t3, k, off);
-        } else {
         FHE_SCHED_FENCE();
-        p3_diag_apply<A, R0, 0, 1>(x, e, ci, cj, cij, t3, k);
+        w14_p3<LZ, A, SEL, R0, 0, 1>(x, e, ci, cj, cij, t3, k, off);
         FHE_SCHED_FENCE();
-        p3_diag_apply<A, R0, 1, 2>(x, e, ci, cj, cij, t3, k);
+        w14_p3<LZ, A, SEL, R0, 1, 2>(x, e, ci, cj, cij, t3, k, off);
         FHE_SCHED_FENCE();
-        p3_diag_apply<A, R0, 2, 3>(x, e, ci, cj, cij, t3, k);
+        w14_p3<LZ, A, SEL, R0, 2, 3>(x, e, ci, cj, cij, t3, k, off);
         FHE_SCHED_FENCE();
-        p3_diag_apply<A, R0, 3, -1>(x, e, ci, cj, cij, t3, k);
-        }
+        w14_p3<LZ, A, SEL, R0, 3, -1>(x, e, ci, cj, cij, t3, k, off);
     } else
     static_for<0, 4>([&](auto abc) {
         constexpr int ab = decltype(abc)::value, nx = ab < 3 ? ab + 1 : 3;
@@ -872,7 +681,7 @@ __device__ __forceinline__ void inv_one_lazy(u64 (&x)[32], Tw7<A> (&d)[2], u64 *
     // pass 2's first twiddle set is requested BEHIND the exchange when it is 32 registers wide: held across the exchange it pushes
     // the allocator over 128 registers, and a spilled twiddle comes back through scratch memory behind every load in flight
     // (vmcnt retires in order): 0.307 -> 0.294 ms per 4096 transforms
-    const int t2 = (w << 4) | (lane >> 2);
+    if constexpr (LZ) t2 = (w << 4) | (lane >> 2);
     constexpr bool C3_LATE = sizeof(Tw) > 8;
     if constexpr (!C3_LATE) tw_load<A, true, P2<R0, 3>>(c3, t2, k);
     xchg_32(x, lane, wl);
@@ -937,47 +746,77 @@ __device__ __forceinline__ void inv_one_lazy(u64 (&x)[32], Tw7<A> (&d)[2], u64 *
     if constexpr (PFX) wlast = A::prep(a0[0]);
     constexpr int LAST_PH = A::GS_SPAN > 0 ? (10 + R0) % (A::GS_SPAN > 0 ? A::GS_SPAN : 1) : 1;  // layers since the sums were last folded
     constexpr int HALF = 1 << (R0 - 1), REPS = 32 >> R0, CH = HALF < 4 ? HALF : 4;
-    if constexpr (LZ) w14_gs_offs<A, SEL>(off, k);
-    auto last = [&](auto oc) {  // the butterfly of registers (o, o + HALF)
-        constexpr int o = decltype(oc)::value;
-        if constexpr (LZ) {
+    // (Up to) four butterflies at a time, stored as they finish; with PAIRS the replicas (hi, i0 = 0) and (hi, 1) of a butterfly finish
+    // together and leave as two 16-byte stores.  The folded butterfly is the same call for every register, written as a loop.  The
+    // lazy one takes each register's folds and offset from the schedule, so its register numbers have to be compile-time values.
+    constexpr bool PAIRS = w14_pairs<A, R0>();
+    constexpr int CHP = CH < 2 ? 1 : CH / 2;
+    if constexpr (LZ) {
+        w14_gs_offs<A, SEL>(off, k);
+        auto last = [&](auto oc) {  // the butterfly of registers (o, o + HALF)
             typedef typename A::GsLazy G;
-            constexpr bool FX = G::template fx<R0, SEL::PAIRS, IN>(10 + R0, o), FY = G::template fy<R0, SEL::PAIRS, IN>(10 + R0, o);
-            constexpr int MI = G::template mi<R0, SEL::PAIRS, IN>(10 + R0, o);
+            constexpr int o = decltype(oc)::value, MI = G::template mi<R0, PAIRS, IN>(10 + R0, o);
+            constexpr bool FX = G::template fx<R0, PAIRS, IN>(10 + R0, o), FY = G::template fy<R0, PAIRS, IN>(10 + R0, o);
             static_assert(MI >= 0 && MI < W14_OFFS, "no offset for this butterfly");
             if constexpr (PFX) A::template gs_last_plain_lazy<FX, FY>(x[o], x[o + HALF], wlast, k.m, off[MI]);
             else A::template gs_last_scaled_lazy<FX, FY>(x[o], x[o + HALF], k.ninv, k.ninv_w, k.m, off[MI]);
+        };
+        if constexpr (PAIRS) {
+            static_for<0, (REPS / 2) * (HALF / CHP)>([&](auto cc) {
+                constexpr int hi = decltype(cc)::value / (HALF / CHP), j0 = (decltype(cc)::value % (HALF / CHP)) * CHP;
+                FHE_SCHED_FENCE();
+                static_for<j0, j0 + CHP>([&](auto jc) {
+                    constexpr int j = decltype(jc)::value, o = ((2 * hi) << R0) + j, o1 = o + (1 << R0);
+                    last(std::integral_constant<int, o>{});
+                    last(std::integral_constant<int, o1>{});
+                    u64 *p = g + ((hi << (7 + R0)) | (t << 1));
+                    *reinterpret_cast<ulonglong2 *>(p + (j << 11)) = make_ulonglong2(x[o], x[o1]);
+                    *reinterpret_cast<ulonglong2 *>(p + ((j + HALF) << 11)) = make_ulonglong2(x[o + HALF], x[o1 + HALF]);
+                });
+            });
         } else {
-            if constexpr (PFX) A::template gs_last_plain<LAST_PH>(x[o], x[o + HALF], wlast, k);
-            else A::template gs_last_scaled<LAST_PH>(x[o], x[o + HALF], k);
+            static_for<0, REPS * (HALF / CH)>([&](auto cc) {
+                constexpr int pass = decltype(cc)::value / (HALF / CH), j0 = (decltype(cc)::value % (HALF / CH)) * CH;
+                FHE_SCHED_FENCE();
+                static_for<j0, j0 + CH>([&](auto jc) {
+                    constexpr int j = decltype(jc)::value, o = (pass << R0) + j;
+                    last(std::integral_constant<int, o>{});
+                    g[(j << 11) | (pass << (6 + R0)) | t] = x[o];
+                    g[((j + HALF) << 11) | (pass << (6 + R0)) | t] = x[o + HALF];
+                });
+            });
         }
-    };
-    if constexpr (w14_pairs<A, R0>()) {
-        // the replicas (hi, i0 = 0) and (hi, 1) of a butterfly finish together and leave as two 16-byte stores; (up to) four
-        // butterflies at a time, stored as they finish
-        constexpr int CHP = CH < 2 ? 1 : CH / 2;
+    } else if constexpr (PAIRS) {
         static_for<0, (REPS / 2) * (HALF / CHP)>([&](auto cc) {
             constexpr int hi = decltype(cc)::value / (HALF / CHP), j0 = (decltype(cc)::value % (HALF / CHP)) * CHP;
             FHE_SCHED_FENCE();
-            static_for<j0, j0 + CHP>([&](auto jc) {
-                constexpr int j = decltype(jc)::value, o = ((2 * hi) << R0) + j, o1 = o + (1 << R0);
-                last(std::integral_constant<int, o>{});
-                last(std::integral_constant<int, o1>{});
+#pragma unroll
+            for (int j = j0; j < j0 + CHP; ++j) {
+                const int o = ((2 * hi) << R0) + j, o1 = o + (1 << R0);
+                if constexpr (PFX) {
+                    A::template gs_last_plain<LAST_PH>(x[o], x[o + HALF], wlast, k);
+                    A::template gs_last_plain<LAST_PH>(x[o1], x[o1 + HALF], wlast, k);
+                } else {
+                    A::template gs_last_scaled<LAST_PH>(x[o], x[o + HALF], k);
+                    A::template gs_last_scaled<LAST_PH>(x[o1], x[o1 + HALF], k);
+                }
                 u64 *p = g + ((hi << (7 + R0)) | (t << 1));
                 *reinterpret_cast<ulonglong2 *>(p + (j << 11)) = make_ulonglong2(x[o], x[o1]);
                 *reinterpret_cast<ulonglong2 *>(p + ((j + HALF) << 11)) = make_ulonglong2(x[o + HALF], x[o1 + HALF]);
-            });
+            }
         });
     } else {
-        static_for<0, REPS * (HALF / CH)>([&](auto cc) {  // (up to) four butterflies at a time, stored as they finish
+        static_for<0, REPS * (HALF / CH)>([&](auto cc) {
             constexpr int pass = decltype(cc)::value / (HALF / CH), j0 = (decltype(cc)::value % (HALF / CH)) * CH;
             FHE_SCHED_FENCE();
-            static_for<j0, j0 + CH>([&](auto jc) {
-                constexpr int j = decltype(jc)::value, o = (pass << R0) + j;
-                last(std::integral_constant<int, o>{});
+#pragma unroll
+            for (int j = j0; j < j0 + CH; ++j) {
+                const int o = (pass << R0) + j;
+                if constexpr (PFX) A::template gs_last_plain<LAST_PH>(x[o], x[o + HALF], wlast, k);
+                else A::template gs_last_scaled<LAST_PH>(x[o], x[o + HALF], k);
                 g[(j << 11) | (pass << (6 + R0)) | t] = x[o];
                 g[((j + HALF) << 11) | (pass << (6 + R0)) | t] = x[o + HALF];
-            });
+            }
         });
     }
     STAMP(8);
@@ -987,14 +826,6 @@ __device__ __forceinline__ void inv_one_lazy(u64 (&x)[32], Tw7<A> (&d)[2], u64 *
     STAMP(9);
     STAMP_REAL(11);
     STAMP_FLUSH();
-}
-
-// the inverse of this instantiation: lazy where w14_lazy_inv_at says so
-template <class A, bool PFX, int R0, int IN, bool FUSED>
-__device__ __forceinline__ void inv_any(u64 (&x)[32], Tw7<A> (&d)[2], u64 *__restrict__ g, const typename A::K &k, u64 *lds, u64 *wl,
-                                        const int t, const int lane, const int w STAMP_ENTRY_PARAM) {
-    if constexpr (w14_lazy_inv_at<A, PFX, R0, IN, FUSED>()) inv_one_lazy<A, PFX, R0, IN>(x, d, g, k, lds, wl, t, lane, w STAMP_ENTRY_ARG);
-    else inv_one<A, PFX, R0>(x, d, g, k, lds, wl, t, lane, w STAMP_ENTRY_ARG);
 }
 
 // Which sub-polynomial a workgroup takes.  A launch over several moduli (the RNS limbs of CKKS: polynomial p uses descs[p % n_desc])
@@ -1077,7 +908,8 @@ __global__ __launch_bounds__(w14::threads<R0>(), 4) void ntt14w_inv_kernel(u64 *
     } else {
         w14::load_p3<0>(x, src); w14::load_p3<1>(x, src); w14::load_p3<2>(x, src); w14::load_p3<3>(x, src);
     }
-    w14::inv_any<A, PFX, R0, MUL ? 1 : 0, false>(x, d, g, k, lds, lds + w * w14::WSLOTS, t, lane, w STAMP_ENTRY_ARG);
+    constexpr int IN = MUL ? 1 : 0;
+    w14::inv_one<A, PFX, R0, IN, w14::w14_lazy_inv_at<A, PFX, R0, IN, false>()>(x, d, g, k, lds, lds + w * w14::WSLOTS, t, lane, w STAMP_ENTRY_ARG);
 }
 
 // util/src/ring/fft/zq.rs:14-19 with the left operand never leaving the chip: forward transform of polynomial s, pointwise product
@@ -1126,7 +958,7 @@ __global__ __launch_bounds__(w14::threads<R0>(), 4) void ntt14w_mul_kernel(u64 *
     if constexpr (w14::w14_p3_diag<A>()) w14::p3_diag_load<A, R0, 0>(reinterpret_cast<uint4(&)[7]>(d[0]), (wi << 8) | lane_i, k);
     else w14::tw7_load<A, true, R0, 0>(d[0], (wi << 8) | lane_i, k);
     if constexpr (!w14::w14_p3_diag<A>() && !w14::w14_p3_refill<A>()) w14::tw7_load<A, true, R0, 1>(d[1], (wi << 8) | lane_i, k);
-    w14::inv_any<A, false, R0, 1, true>(x, d, g, k, lds, lds + wi * w14::WSLOTS, ti, lane_i, wi STAMP_ENTRY_ARG);
+    w14::inv_one<A, false, R0, 1, w14::w14_lazy_inv_at<A, false, R0, 1, true>()>(x, d, g, k, lds, lds + wi * w14::WSLOTS, ti, lane_i, wi STAMP_ENTRY_ARG);
 }
 
 }  // namespace fhe
