@@ -614,6 +614,95 @@ void fhe_ckks_linear_transform_destroy(fhe_ckks_linear_transform *t);
 int fhe_ckks_linear_transform_apply(const fhe_ckks_linear_transform *t, const uint64_t *ct_b, const uint64_t *ct_a, uint64_t *out_b,
                                     uint64_t *out_a, size_t batch, fhe_mem mem, void *stream);
 
+/* ---- CKKS polynomial evaluation: a Chebyshev (or monomial) series on encrypted slots in one call.  NO REFERENCE LINE: `Ckks` has no
+ * such function (bootstrapping.rs stops before the modular reduction).  The pieces keep the reference's conventions: products are
+ * scheme/ckks/src/ckks.rs:250-263 `Ckks::mul` with its closing `rescale()`, the rescale is util/src/ring/rns.rs:99-111 (the K == 1 branch,
+ * NOT centred), and a real constant c becomes the integer trunc(c * scale), the fraction dropped toward zero as ckks.rs:186-198
+ * `Ckks::encode` drops it (exact here: c is an f64, so mantissa * scale fits 128 bits).  A constant slot vector is the constant
+ * polynomial, so adding one touches coefficient 0 of the b half only.  Every ciphertext is taken to carry the scale `scale`: a product or
+ * a real-mode combination leaves scale^2 / q_last, which the reference too treats as scale (all primes of a chain have one bit length).
+ *
+ * fhe_ckks_scaled_constant: trunc(c * scale) reduced into [0, q), negative values as q - |k| mod q.  c not finite or |c * scale| >= 2^126:
+ * FHE_ERR_INVALID. */
+int fhe_ckks_scaled_constant(double c, uint64_t scale, uint64_t q, uint64_t *out);
+/* ONE launch combines n_terms <= 16 ciphertexts with a constant.  Ciphertext j is ct_b[j], ct_a[j] [batch][limbs[j]][n], coefficient
+ * domain, limbs[j] >= l = the limb count of rns; only limbs 0 .. l of each are read (the level drop, exact in RNS, nothing is repacked).
+ *   real == 0   out = sum_j imul[j] ct_j + k0 e0, k0 = trunc(c0 scale); out_b, out_a [batch][l][n]; no level is consumed (cmul unused);
+ *   real != 0   out = rescale( sum_j k_j ct_j + k0 scale e0 ), k_j = trunc(cmul[j] scale); out [batch][l - 1][n]; l >= 2 (imul unused).
+ * The sum is accumulated unreduced in 128 bits and reduced once per output where every modulus is below 2^61, product by product
+ * otherwise: the same residues either way.  An output may alias an input only with real == 0 and limbs[j] == l (the same layout).
+ * A NULL argument, limbs[j] < l, n_terms outside 1 .. 16, a constant that is not finite or has |c scale| >= 2^126, scale == 0, l < 2 with
+ * real != 0: FHE_ERR_INVALID.  batch == 0: FHE_OK.  The per-limb constants are made on the host per call and the call waits for the stream
+ * before it returns (fhe_ckks_poly_apply uploads its constants once and does not). */
+int fhe_ckks_lincomb(const fhe_rns_ctx *rns, int real, int n_terms, const uint64_t *const *ct_b, const uint64_t *const *ct_a, const int *limbs,
+                     const int64_t *imul, const double *cmul, double c0, uint64_t scale, uint64_t *out_b, uint64_t *out_a, size_t n, size_t batch,
+                     fhe_mem mem, void *stream);
+/* fhe_ckks_mul whose operands already ARE in the evaluation domain (fhe_rns_ntt_fwd of both halves) on x_limbs, y_limbs >= L limbs, read
+ * on the prefix 0 .. L of rns; then, after the closing rescale, out = alpha out - ct_c with alpha in {1, 2} and ct_c (c_b, c_a
+ * [batch][c_limbs][n], coefficient domain, c_limbs >= L - 1, or both NULL: nothing subtracted).  Bit-identical to fhe_ckks_mul on the
+ * prefix-sliced operands followed by the integer-mode fhe_ckks_lincomb {alpha, -1}.  out_b, out_a [batch][L - 1][n]. */
+int fhe_ckks_mul_eval(const fhe_rns_ctx *rns, const fhe_ckks_key *rlk, const uint64_t *x_b, const uint64_t *x_a, int x_limbs, const uint64_t *y_b,
+                      const uint64_t *y_a, int y_limbs, int alpha, const uint64_t *c_b, const uint64_t *c_a, int c_limbs, uint64_t *out_b, uint64_t *out_a,
+                      size_t batch, fhe_mem mem, void *stream);
+/* The PLAN: a host-only schedule (no GPU is touched) over registers; register 0 is the input ciphertext and every other register is
+ * written exactly once, before it is read.  One op is one record:
+ *   kind == FHE_POLY_MUL   dst = alpha * (a * b) - c        a, b, c registers, alpha in {1, 2}, c == -1: nothing subtracted;
+ *   kind == FHE_POLY_LIN   dst = sum_{j < n_terms} coef[j] * src[j] + c0      mode 0: integer multipliers (coef[j] holds the integer), no
+ *                          level consumed; mode 1: real multipliers, one level consumed (fhe_ckks_lincomb's two modes).
+ * Fields a kind does not use are 0 (c: -1).  The level offset ("depth") of a register follows from the list: depth(0) = 0, a MUL gives
+ * max(depth a, depth b) + 1, a LIN max over its sources + mode; an op runs on the limbs its shallowest-level operand has and reads the
+ * others by prefix.  The result is the dst of the LAST op and is the deepest register.
+ * fhe_ckks_poly_plan_create builds the fixed baby-step / giant-step (Paterson-Stockmeyer) schedule of sum_j coeffs[j] T_j(x), x in
+ * [-1, 1] (basis 0, Chebyshev) or sum_j coeffs[j] x^j (basis 1), 0 <= degree <= 255:
+ *   - k = the smallest power of two >= 2 with k^2 >= degree + 1;
+ *   - powers T_i are made on demand by T_{a+b} = 2 T_a T_b - T_{a-b}, a the largest power of two below i (T_{2a} = 2 T_a^2 - 1 as a MUL
+ *     with alpha = 2 and an integer LIN adding -1; x^{a+b} = x^a x^b), so T_i sits at depth ceil(log2 i);
+ *   - the series is split recursively at the largest giant m = 2^j k <= its degree, p = quo T_m + rem (T_{m+i} = 2 T_m T_i - T_{m-i}), into
+ *     blocks of degree < k: a block is ONE real-mode LIN of baby powers, and a split is ONE MUL quo * T_m with the block of -rem as its
+ *     subtrahend;
+ *   - a term with coeffs[j] == 0.0 is left out structurally (a power nobody needs is never computed), an all-zero block is skipped
+ *     together with its product or subtrahend, and a constant series (degree 0, or everything else zero) is the single real-mode op
+ *     0.0 * input + c0.
+ * The depth is at most ceil(log2(degree + 1)) + 2.  fhe_ckks_poly_plan_from_ops takes a caller-made list (how the eval_mod recipe wraps a
+ * series in its scaling and double-angle steps) and checks the rules above; anything else is FHE_ERR_INVALID, as are degree > 255, a
+ * coefficient that is not finite and a NULL argument. */
+enum { FHE_POLY_MUL = 0, FHE_POLY_LIN = 1 };
+typedef struct {
+    int32_t kind, dst;
+    int32_t a, b, alpha, c;   /* MUL */
+    int32_t mode, n_terms;    /* LIN */
+    int32_t src[16];
+    double coef[16];
+    double c0;
+} fhe_ckks_poly_op;
+typedef struct fhe_ckks_poly_plan fhe_ckks_poly_plan;
+int fhe_ckks_poly_plan_create(const double *coeffs, int degree, int basis, fhe_ckks_poly_plan **out);
+int fhe_ckks_poly_plan_from_ops(const fhe_ckks_poly_op *ops, int n_ops, fhe_ckks_poly_plan **out);
+void fhe_ckks_poly_plan_destroy(fhe_ckks_poly_plan *plan);
+/* the multiplicative depth (= levels the evaluation consumes), the number of ops and of registers, the input included (any may be NULL) */
+int fhe_ckks_poly_plan_info(const fhe_ckks_poly_plan *plan, int *depth, int *n_ops, int *n_regs);
+/* the first `count` <= n_ops records in execution order */
+int fhe_ckks_poly_plan_ops(const fhe_ckks_poly_plan *plan, fhe_ckks_poly_op *out, int count);
+/* The plan bound to the caller's contexts: levels [n_levels >= depth + 1], levels[s] over qs[0 .. L - s) with the same ps on the same
+ * device (the rule of fhe_ckks_linear_transform_prepare), L >= depth + 1; `scale` of `Ckks::encode`; rlk_b, rlk_a ONE coefficient-domain
+ * relinearisation key [L + K][n] over levels[0] (`mem` says where it lives), cut down to every level a MUL runs on by removing the dropped
+ * q-limb rows and prepared once per level.  Every constant is reduced per (op, limb) here and uploaded.  The contexts are BORROWED; the
+ * plan and the caller's key are not needed after the call.  Mismatched contexts, too few levels, a constant out of range or a NULL
+ * argument: FHE_ERR_INVALID, nothing stays allocated. */
+typedef struct fhe_ckks_poly_eval fhe_ckks_poly_eval;
+int fhe_ckks_poly_prepare(const fhe_ckks_poly_plan *plan, const fhe_rns_ctx *const *levels, int n_levels, uint64_t scale, const uint64_t *rlk_b,
+                          const uint64_t *rlk_a, size_t n, fhe_mem mem, fhe_ckks_poly_eval **out);
+void fhe_ckks_poly_eval_destroy(fhe_ckks_poly_eval *eval);
+/* ct_b, ct_a [batch][L][n] over levels[0], coefficient domain -> out_b, out_a [batch][L - depth][n] over levels[depth]; host or device
+ * memory, on `stream`, nothing waits.  Bit-identical to replaying the op list through fhe_ckks_mul (on contiguous prefix slices) and
+ * fhe_ckks_lincomb.  Every register that feeds a MUL is forward-transformed ONCE and kept in the evaluation domain for all its uses (its
+ * prefix limbs serve the lower levels); a register that only feeds LIN ops is never transformed.  Stream-ordered workspace, in 8-byte
+ * words: 2 batch n (L - depth(g)) for every register g but the input and the result, the same again for every register that feeds a MUL,
+ * and 5 batch n l_max for the running product (l_max = the limbs of the highest-level MUL), plus the key switch's own.  batch == 0
+ * returns FHE_OK. */
+int fhe_ckks_poly_apply(const fhe_ckks_poly_eval *eval, const uint64_t *ct_b, const uint64_t *ct_a, uint64_t *out_b, uint64_t *out_a, size_t batch,
+                        fhe_mem mem, void *stream);
+
 /* ---- TFHE key material, k = 1 (rank k: fhe_tglwek_sk_encrypt / fhe_tggswk_encrypt at the end).  Draws are counter based (ChaCha20, as above): reproducible per
  * (generator key, stream_id), checked at decode level like the reference's own tests (its draws are unseeded). */
 /* util/src/misc/distribution.rs:49-54 `tdg(std_dev)`: torus Gaussian noise (Box-Muller deviate, fractional part scaled by 2^64) */

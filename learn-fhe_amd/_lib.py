@@ -210,6 +210,20 @@ def lib():
         L.fhe_ckks_linear_transform_destroy.argtypes = [vp]
         L.fhe_ckks_linear_transform_destroy.restype = None
         L.fhe_ckks_linear_transform_apply.argtypes = [vp, vp, vp, vp, vp, sz, ci, vp]
+        # CKKS polynomial evaluation (ckks_poly_api.hip)
+        L.fhe_ckks_scaled_constant.argtypes = [dbl, u64, u64, u64p]
+        L.fhe_ckks_lincomb.argtypes = [vp, ci, ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(ci), i64p, dblp, dbl, u64, vp, vp, sz, sz, ci, vp]
+        L.fhe_ckks_mul_eval.argtypes = [vp, vp, vp, vp, ci, vp, vp, ci, ci, vp, vp, ci, vp, vp, sz, ci, vp]
+        L.fhe_ckks_poly_plan_create.argtypes = [dblp, ci, ci, C.POINTER(vp)]
+        L.fhe_ckks_poly_plan_from_ops.argtypes = [vp, ci, C.POINTER(vp)]
+        L.fhe_ckks_poly_plan_destroy.argtypes = [vp]
+        L.fhe_ckks_poly_plan_destroy.restype = None
+        L.fhe_ckks_poly_plan_info.argtypes = [vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
+        L.fhe_ckks_poly_plan_ops.argtypes = [vp, vp, ci]
+        L.fhe_ckks_poly_prepare.argtypes = [vp, C.POINTER(vp), ci, u64, vp, vp, sz, ci, C.POINTER(vp)]
+        L.fhe_ckks_poly_eval_destroy.argtypes = [vp]
+        L.fhe_ckks_poly_eval_destroy.restype = None
+        L.fhe_ckks_poly_apply.argtypes = [vp, vp, vp, vp, vp, sz, ci, vp]
         # any TGLWE rank k (torusk_api.hip)
         L.fhe_tggswk_prepare.argtypes = [vp, ci, ci, ci, vp, sz, sz, ci, C.POINTER(vp)]
         L.fhe_tggswk_key_destroy.argtypes = [vp]

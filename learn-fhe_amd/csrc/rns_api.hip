@@ -1172,4 +1172,9 @@ int ckks_key_switch_dev(const fhe_rns_ctx *r, const fhe_ckks_key *key, const u64
     return key_switch_dev(r, key, a_in, add_b, add_a, out_b, out_a, batch, st);
 }
 int ckks_ring_status(const fhe_rns_ctx *r, size_t n) { return ckks_ring_ok(r, n); }
+// what csrc/ckks_poly_api.hip closes its products with: fhe_rns_rescale on device pointers
+int ckks_rescale_last_dev(const fhe_rns_ctx *r, const u64 *in, u64 *out, size_t n, size_t batch, hipStream_t st) {
+    const size_t L = r->L;
+    return launch_rescale(r, true, rescale_in_block(in, L * n, r->L - 1, 1, n), out, (L - 1) * n, nullptr, 0, n, batch, st);
+}
 }  // namespace fhe

@@ -38,4 +38,6 @@ int ckks_key_switch_dev(const fhe_rns_ctx *r, const fhe_ckks_key *key, const u64
                         size_t batch, hipStream_t st);
 // FHE_OK if a CKKS ring of degree n exists over every modulus of r on a device (rns_api.hip ckks_ring_ok)
 int ckks_ring_status(const fhe_rns_ctx *r, size_t n);
+// rns.rs:99-101 `rescale()` on device pointers (rns_api.hip, what fhe_rns_rescale launches): in [batch][L][n] -> out [batch][L-1][n]
+int ckks_rescale_last_dev(const fhe_rns_ctx *r, const u64 *in, u64 *out, size_t n, size_t batch, hipStream_t st);
 }  // namespace fhe
