@@ -703,6 +703,76 @@ void fhe_ckks_poly_eval_destroy(fhe_ckks_poly_eval *eval);
 int fhe_ckks_poly_apply(const fhe_ckks_poly_eval *eval, const uint64_t *ct_b, const uint64_t *ct_a, uint64_t *out_b, uint64_t *out_a, size_t batch,
                         fhe_mem mem, void *stream);
 
+/* ---- CKKS bootstrap: `mod_raise`, the conjugate split after `coeff_to_slot`, `eval_mod` on both halves, the join, `slot_to_coeff`, as
+ * single entries and as ONE call.  NO REFERENCE LINE: scheme/ckks/src/bootstrapping.rs ends at `coeff_to_slot` / `slot_to_coeff`.  The
+ * conventions are the reference's: `Ckks::encode` (ckks.rs:186-198) puts Re z_i scale in coefficient i and Im z_i scale in coefficient
+ * l + i (l = n / 2, z = sifft(m)); `Ckks::conjugate` (ckks.rs:279-282) is fhe_ckks_rotate with t = -1 and the key of `Ckks::cjk_gen`.
+ * With D = scale and q_0 = qs[0], a ciphertext that is meaningful mod q_0 decrypts after fhe_ckks_mod_raise to t = c + e + q_0 I (c the
+ * encoded coefficients, I an integer polynomial, |I_j| <= (|sk|_1 + 1) / 2); coeff_to_slot leaves w_i = (t_i + i t_{l+i}) / D in the slots
+ * (in some order, which the slot-wise steps do not care about); R = ct + conj(ct) holds 2 t_i / D and J = -X^(n/2) (ct - conj(ct)) holds
+ * 2 t_{l+i} / D (X^(n/2) multiplies every slot by i because 5^k = 1 mod 4: an exact negacyclic shift by n/2, no level, no noise);
+ * eval_mod with pre = D / (2 q_0) and post = q_0 / D maps both to about c_j / D; out = R' + X^(n/2) J' holds z again and slot_to_coeff
+ * returns m.
+ *
+ * ckks.rs:169-172 `Ckks::cjk_gen(param, sk)`: sk(X^-1) is formed on the device from the i64 key (avec.rs:34-50, as fhe_ckks_rtk_gen forms
+ * sk(X^(5^j))) and handed to fhe_ckks_ksk_gen: ksk_b, ksk_a [L+K][n].  n = 2 .. a power of two. */
+int fhe_ckks_cjk_gen(const fhe_rns_ctx *rns, const uint64_t *sk, size_t n, const fhe_rng *rng, uint64_t stream_id, uint64_t *ksk_b, uint64_t *ksk_a,
+                     fhe_mem mem, void *stream);
+/* ct_b, ct_a [batch][in_limbs][n], of which ONLY limb 0 (residues mod q_0 = the first modulus of rns) is read -> out_b, out_a
+ * [batch][L][n] over rns: every residue lifted to its centred integer in (-q_0 / 2, q_0 / 2] and reduced into every q-limb, a negative
+ * value v as q_l - (|v| mod q_l) with 0 staying 0.  Right for any base: |v| may exceed a smaller q_l many times over.  in_limbs < 1, a NULL
+ * argument, n not a ring degree of rns: FHE_ERR_INVALID.  batch == 0: FHE_OK. */
+int fhe_ckks_mod_raise(const fhe_rns_ctx *rns, const uint64_t *ct_b, const uint64_t *ct_a, int in_limbs, uint64_t *out_b, uint64_t *out_a, size_t n,
+                       size_t batch, fhe_mem mem, void *stream);
+/* ct = (ct_b, ct_a) and its conjugate cj = (cj_b, cj_a) (fhe_ckks_rotate with t = -1 on a copy of ct), each [batch][L][n] over the q-limbs
+ * of rns -> out_b, out_a [2 batch][L][n]: rows [0, batch) hold R = ct + cj, rows [batch, 2 batch) hold J = -X^(n/2) (ct - cj), one stacked
+ * batch for ONE fhe_ckks_poly_apply.  The outputs must not overlap the inputs. */
+int fhe_ckks_conj_split(const fhe_rns_ctx *rns, const uint64_t *ct_b, const uint64_t *ct_a, const uint64_t *cj_b, const uint64_t *cj_a, uint64_t *out_b,
+                        uint64_t *out_a, size_t n, size_t batch, fhe_mem mem, void *stream);
+/* the inverse layout: in_b, in_a [2 batch][L][n] (rows [0, batch) = R', rows [batch, 2 batch) = J') -> out_b, out_a [batch][L][n] =
+ * R' + X^(n/2) J'.  fhe_ckks_conj_join of fhe_ckks_conj_split(x, cx) is 2 x exactly.  NULL argument, n not a ring degree of rns:
+ * FHE_ERR_INVALID; batch == 0: FHE_OK (both entries). */
+int fhe_ckks_conj_join(const fhe_rns_ctx *rns, const uint64_t *in_b, const uint64_t *in_a, uint64_t *out_b, uint64_t *out_a, size_t n, size_t batch,
+                       fhe_mem mem, void *stream);
+/* The scaled-sine modular reduction as a plan, host only (no GPU is touched): slots x -> post / (2 pi) sin(2 pi pre x), right where
+ * |pre x| <= K.
+ *   1. u = (pre / K) x                                  one real-mode LIN;
+ *   2. y = the degree-`degree` Chebyshev interpolant of cos(2 pi (K u - 1/4) / 2^r) at the degree + 1 Chebyshev nodes of the first kind
+ *      (the definition numpy.polynomial.chebyshev.chebinterpolate uses), through fhe_ckks_poly_plan_create's own schedule;
+ *   3. r double-angle steps y <- 2 y^2 - 1              a MUL with alpha = 2 and an integer LIN adding -1 each;
+ *   4. the factor post / (2 pi)                         one real-mode LIN.
+ * With pre = post = 1 slots t = eps + I (I an integer, |t| <= K) come out as about eps; a bootstrap passes pre = scale / (2 q_0) and
+ * post = q_0 / scale (above).  K < 1, r < 0 (or more steps than a plan holds), degree outside 1 .. 255, a factor that is not finite, a
+ * NULL out: FHE_ERR_INVALID. */
+int fhe_ckks_eval_mod_plan_create(int K, int r, int degree, double pre, double post, fhe_ckks_poly_plan **out);
+/* The bootstrapper: the caller's prepared stages bound together.
+ *   levels   [n_levels >= depth + 1], levels[s] over qs[0 .. L - s) with the same ps on the same device (the rule of
+ *            fhe_ckks_linear_transform_prepare); depth = d_c2s + d_mod + d_s2c, the depths of the three stages;
+ *   c2s, eval, s2c   the coeff_to_slot transform, the eval_mod evaluator and the slot_to_coeff transform, prepared on levels[0 ..],
+ *            levels[d_c2s ..] and levels[d_c2s + d_mod ..]: the SAME context objects (checked by identity) and the same n.  BORROWED, as are
+ *            the contexts: all must outlive the bootstrapper;
+ *   cjk_b, cjk_a   ONE coefficient-domain conjugation key [L + K][n] over levels[0] (fhe_ckks_cjk_gen; `mem` says where it lives), cut
+ *            down to levels[d_c2s] by removing the dropped q-limb rows and prepared once; not needed after the call.
+ * Too few levels, stages bound to other contexts or another n, mismatched contexts or a NULL argument: FHE_ERR_INVALID, nothing stays
+ * allocated. */
+typedef struct fhe_ckks_bootstrap fhe_ckks_bootstrap;
+int fhe_ckks_bootstrap_prepare(const fhe_rns_ctx *const *levels, int n_levels, size_t n, const fhe_ckks_linear_transform *c2s,
+                               const fhe_ckks_poly_eval *eval, const fhe_ckks_linear_transform *s2c, const uint64_t *cjk_b, const uint64_t *cjk_a,
+                               fhe_mem mem, fhe_ckks_bootstrap **out);
+void fhe_ckks_bootstrap_destroy(fhe_ckks_bootstrap *bs);
+/* the levels the call consumes and the limbs L - depth of its result (either may be NULL) */
+int fhe_ckks_bootstrap_info(const fhe_ckks_bootstrap *bs, int *depth, int *out_limbs);
+/* ct_b, ct_a [batch][in_limbs][n] (limb 0 read) -> out_b, out_a [batch][L - depth][n] over levels[depth]; host or device memory, on
+ * `stream`, nothing waits.  Bit-identical to chaining the public entries by hand: fhe_ckks_mod_raise, fhe_ckks_linear_transform_apply,
+ * fhe_ckks_rotate (t = -1) on a copy, fhe_ckks_conj_split, fhe_ckks_poly_apply on the stacked 2 batch ciphertexts,
+ * fhe_ckks_conj_join, fhe_ckks_linear_transform_apply.  Stream-ordered workspace, in 8-byte words, with L1 = L - d_c2s and L2 = L1 - d_mod:
+ * 2 batch n L for the raised ciphertext, 2 batch n L1 each for the slots and their conjugate, 4 batch n L1 for the stacked pair,
+ * 4 batch n L2 for the reduced pair and 2 batch n L2 for the joined ciphertext, every block released in stream order as soon as its last
+ * reader is enqueued: at most batch n max(2 L + 2 L1, 8 L1) live at once, plus the running stage's own.  A NULL bootstrapper or argument,
+ * in_limbs < 1: FHE_ERR_INVALID.  batch == 0 returns FHE_OK. */
+int fhe_ckks_bootstrap_apply(const fhe_ckks_bootstrap *bs, const uint64_t *ct_b, const uint64_t *ct_a, int in_limbs, uint64_t *out_b, uint64_t *out_a,
+                             size_t batch, fhe_mem mem, void *stream);
+
 /* ---- TFHE key material, k = 1 (rank k: fhe_tglwek_sk_encrypt / fhe_tggswk_encrypt at the end).  Draws are counter based (ChaCha20, as above): reproducible per
  * (generator key, stream_id), checked at decode level like the reference's own tests (its draws are unseeded). */
 /* util/src/misc/distribution.rs:49-54 `tdg(std_dev)`: torus Gaussian noise (Box-Muller deviate, fractional part scaled by 2^64) */

@@ -8,6 +8,8 @@ from ._lib import FheError, build, lib, lib_path, set_option  # noqa: F401
 from . import circuit  # noqa: F401
 from . import ckks_poly  # noqa: F401
 from .ckks_poly import CkksPolyEval, CkksPolyPlan, eval_mod_plan  # noqa: F401
+from . import ckks_bootstrap  # noqa: F401
+from .ckks_bootstrap import CkksBootstrapper, bootstrap_eval_mod_plan, cjk_gen  # noqa: F401
 from .circuit import Circuit  # noqa: F401
 from .ring import (BootstrapKey, CkksDiagMatrix, CkksEncoder, CkksKey, CkksLinearPlan, CkksLinearTransform, CkksShard, Fhew, GadgetKey, NttContext, RnsContext, TggswKey, TorusContext,  # noqa: F401
                    ak_t, automorphism, bsgs_split, decompose, lwe_key_switch, lwe_lincomb, lwe_mod_switch, monomial_mul, rlwe_sample_extract, rq_add, rq_from_i64, rq_neg, rq_scalar_mul, rq_sub,

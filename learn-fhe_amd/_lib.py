@@ -224,6 +224,17 @@ def lib():
         L.fhe_ckks_poly_eval_destroy.argtypes = [vp]
         L.fhe_ckks_poly_eval_destroy.restype = None
         L.fhe_ckks_poly_apply.argtypes = [vp, vp, vp, vp, vp, sz, ci, vp]
+        # CKKS bootstrap (ckks_bootstrap_api.hip)
+        L.fhe_ckks_cjk_gen.argtypes = [vp, vp, sz, vp, u64, vp, vp, ci, vp]
+        L.fhe_ckks_mod_raise.argtypes = [vp, vp, vp, ci, vp, vp, sz, sz, ci, vp]
+        L.fhe_ckks_conj_split.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, sz, ci, vp]
+        L.fhe_ckks_conj_join.argtypes = [vp, vp, vp, vp, vp, sz, sz, ci, vp]
+        L.fhe_ckks_eval_mod_plan_create.argtypes = [ci, ci, ci, dbl, dbl, C.POINTER(vp)]
+        L.fhe_ckks_bootstrap_prepare.argtypes = [C.POINTER(vp), ci, sz, vp, vp, vp, vp, vp, ci, C.POINTER(vp)]
+        L.fhe_ckks_bootstrap_destroy.argtypes = [vp]
+        L.fhe_ckks_bootstrap_destroy.restype = None
+        L.fhe_ckks_bootstrap_info.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]
+        L.fhe_ckks_bootstrap_apply.argtypes = [vp, vp, vp, ci, vp, vp, sz, ci, vp]
         # any TGLWE rank k (torusk_api.hip)
         L.fhe_tggswk_prepare.argtypes = [vp, ci, ci, ci, vp, sz, sz, ci, C.POINTER(vp)]
         L.fhe_tggswk_key_destroy.argtypes = [vp]

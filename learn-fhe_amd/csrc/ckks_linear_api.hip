@@ -439,3 +439,10 @@ int fhe_ckks_linear_transform_apply(const fhe_ckks_linear_transform *t, const ui
 }
 
 }  // extern "C"
+
+namespace fhe {
+const std::vector<const fhe_rns_ctx *> &ckks_linear_transform_levels(const fhe_ckks_linear_transform *t, size_t *n) {
+    *n = t->n;
+    return t->levels;
+}
+}  // namespace fhe

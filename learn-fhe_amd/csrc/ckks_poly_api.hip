@@ -559,3 +559,10 @@ int fhe_ckks_poly_apply(const fhe_ckks_poly_eval *ev, const uint64_t *ct_b, cons
 }
 
 }  // extern "C"
+
+namespace fhe {
+const std::vector<const fhe_rns_ctx *> &ckks_poly_eval_levels(const fhe_ckks_poly_eval *ev, size_t *n) {
+    *n = ev->n;
+    return ev->levels;
+}
+}  // namespace fhe
