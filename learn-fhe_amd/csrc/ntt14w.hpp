@@ -836,6 +836,22 @@ __device__ __forceinline__ unsigned sub_of_block(int pb, unsigned n_desc) {
     if (gridDim.y == 1) return blockIdx.x;
     return ((((blockIdx.x >> pb) * n_desc) + blockIdx.y) << pb) | (blockIdx.x & ((1u << pb) - 1));
 }
+// The inverse takes the same map from the far end: block (x, y) does the work of block (gridDim.x - 1 - x, gridDim.y - 1 - y), so a
+// launch begins on the polynomials an ascending launch over the same buffer touched LAST -- the ones the Infinity Cache still holds
+// when the buffer is larger than the cache -- and ends on polynomial 0, where the next ascending launch begins.  Forward followed by
+// inverse over one batch is the usual shape (ring product, key switch, round trip).  The map stays a bijection of the grid onto the
+// sub-polynomials and everything a workgroup addresses (descriptor, prefix, src, mul, dst2) follows from `sub`, so results are the
+// same; with several moduli the dispatch stays modulus by modulus, last modulus first.  A fixed property of the direction: no host state.
+// Lab switch: a policy that declares W14_ASCENDING_INV keeps the ascending order for its own instantiations (tools/ntt_lab2.hip).
+template <class A, class = void> struct w14_ascending_inv { static constexpr bool value = false; };
+template <class A> struct w14_ascending_inv<A, decltype((void)A::W14_ASCENDING_INV)> { static constexpr bool value = true; };
+template <class A>
+__device__ __forceinline__ unsigned sub_of_block_inv(int pb, unsigned n_desc) {
+    if constexpr (w14_ascending_inv<A>::value) return sub_of_block(pb, n_desc);
+    const unsigned bx = gridDim.x - 1 - blockIdx.x, by = gridDim.y - 1 - blockIdx.y;
+    if (gridDim.y == 1) return bx;
+    return ((((bx >> pb) * n_desc) + by) << pb) | (bx & ((1u << pb) - 1));
+}
 
 }  // namespace w14
 
@@ -873,7 +889,7 @@ __global__ __launch_bounds__(w14::threads<R0>(), 4) void ntt14w_inv_kernel(u64 *
     u64 *lds = reinterpret_cast<u64 *>(smem_raw);
     const int t = threadIdx.x, lane = t & 63;
     const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-    const unsigned sub = w14::sub_of_block(PFX ? pb : 0, n_desc);
+    const unsigned sub = w14::sub_of_block_inv<A>(PFX ? pb : 0, n_desc);
     const unsigned poly = PFX ? sub >> pb : sub;
     const ModDesc &D = descs[n_desc == 1 ? 0 : poly % n_desc];
     const typename A::K k = A::make(D, LOG_N, PFX ? pb : 0, PFX ? int(sub & ((1u << pb) - 1)) : 0);

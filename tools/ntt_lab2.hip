@@ -20,6 +20,9 @@ struct DSOld : ArithDS<60> {  // the pass-0 side as it was dealt before the coef
 struct DSFoldedInv : ArithDS<60> {  // the inverse as it was before the lazy butterflies: every product folded, sums every third layer (same results)
     static constexpr bool W14_FOLDED_GS = true;
 };
+struct DSAscInv : ArithDS<60> {  // the inverse walking the batch upwards as the forward does, as it did before it began at the far end (same results)
+    static constexpr bool W14_ASCENDING_INV = true;
+};
 struct DSNoTw : ArithDS<60> {  // ablation: butterflies with a computed twiddle, no twiddle loads (wrong results, same work)
     template <bool INV> static __device__ __forceinline__ TwRaw fetch(const K &k, int idx) { return uint4{k.ninv.x + (unsigned)idx, k.ninv.y, k.ninv.z ^ (unsigned)idx, k.ninv.w}; }
 };
@@ -146,6 +149,7 @@ int main(int argc, char **argv) {
         {"wave-local, PM60", ntt14w_fwd_kernel<ArithPM<60>, false>, ntt14w_inv_kernel<ArithPM<60>, false>, 0, 0, 1},
         {"wave-local, DS60", ntt14w_fwd_kernel<ArithDS<60>, false>, ntt14w_inv_kernel<ArithDS<60>, false>, 0, 0, 1},
         {"DS60, folded inverse (old)", ntt14w_fwd_kernel<DSFoldedInv, false>, ntt14w_inv_kernel<DSFoldedInv, false>, 0, 0, 1},
+        {"DS60, ascending inverse (old)", ntt14w_fwd_kernel<DSAscInv, false>, ntt14w_inv_kernel<DSAscInv, false>, 0, 0, 1},
         {"DS60, 8-byte pass-0 side (old)", ntt14w_fwd_kernel<DSOld, false>, ntt14w_inv_kernel<DSOld, false>, 0, 0, 1},
         {"wave-local, Shoup", ntt14w_fwd_kernel<ArithShoup, false>, ntt14w_inv_kernel<ArithShoup, false>, 0, 0, 1},
         {"wave-local DS60, no twiddle loads", ntt14w_fwd_kernel<DSNoTw, false>, ntt14w_inv_kernel<DSNoTw, false>, 0, 0, 1},
@@ -205,7 +209,7 @@ int main(int argc, char **argv) {
         printf("%-32s fwd %.4f ms %5.0f GB/s (%.3f of 8 TB/s) | inv %.4f ms %5.0f GB/s (%.3f)\n", v.name, v.sf / reps, bytes / (v.sf / reps * 1e-3) / 1e9,
                bytes / (v.sf / reps * 1e-3) / 8e12, v.si / reps, bytes / (v.si / reps * 1e-3) / 1e9, bytes / (v.si / reps * 1e-3) / 8e12);
 #ifdef NTT14_STAMPS
-    for (int vi : {0, 1, 3})  // PM60, DS60 (coefficient pairs), DS60 with the 8-byte pass-0 side
+    for (int vi : {0, 1, 4})  // PM60, DS60 (coefficient pairs), DS60 with the 8-byte pass-0 side
     for (int dir : {0, 1}) {   // where does a workgroup spend its life?
         auto &v = vs[vi];
         for (int r = 0; r < 40; ++r) hipLaunchKernelGGL(dir ? v.i : v.f, dim3(GRID(v)), dim3(N14_THREADS), N14_LDS_BYTES, 0, d, (const ModDesc *)d_desc, 1u, (unsigned)batch, 0, NttIo());
