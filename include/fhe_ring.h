@@ -354,6 +354,25 @@ int fhe_tlwe_key_switch(int log_b, int d, const uint64_t *ksk_a, const uint64_t 
 int fhe_tfhe_bootstrap(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, int ks_log_b, int ks_d, const uint64_t *ksk_a,
                        const uint64_t *ksk_b, const uint64_t *v, const uint64_t *lwe_a, const uint64_t *lwe_b, uint64_t *out_a,
                        uint64_t *out_b, size_t batch, fhe_mem mem, void *stream);
+/* scheme/tfhe/src/bootstrapping.rs:84-96 `blind_rotate` with one test polynomial PER CIPHERTEXT (bootstrapping.rs:118-128 `table` builds
+ * one per function, 141-165 bootstraps through three of them): tables [n_tables][n] encoded, table_of [batch]; ciphertext i rotates
+ * tables[table_of[i]].  n_tables <= 65536.  The result for ciphertext i is bit-identical, in every key form, to fhe_tfhe_blind_rotate
+ * with v = tables[table_of[i]].  Host memory: an index >= n_tables is FHE_ERR_INVALID.  Device memory: the caller guarantees
+ * table_of[i] < n_tables; the kernels clamp nothing. */
+int fhe_tfhe_blind_rotate_tables(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, const uint64_t *a_tilde, const uint64_t *b_tilde,
+                                 const uint64_t *tables, size_t n_tables, const uint32_t *table_of, uint64_t *out_a, uint64_t *out_b,
+                                 size_t batch, fhe_mem mem, void *stream);
+/* scheme/tfhe/src/bootstrapping.rs:78-82 `Bootstrapping::bootstrap` through tables[table_of[i]] for ciphertext i; tables and indices as
+ * above, everything else as fhe_tfhe_bootstrap, whose bits it reproduces table by table. */
+int fhe_tfhe_bootstrap_tables(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, int ks_log_b, int ks_d, const uint64_t *ksk_a,
+                              const uint64_t *ksk_b, const uint64_t *tables, size_t n_tables, const uint32_t *table_of,
+                              const uint64_t *lwe_a, const uint64_t *lwe_b, uint64_t *out_a, uint64_t *out_b, size_t batch, fhe_mem mem,
+                              void *stream);
+/* scheme/tfhe/src/tlwe.rs:22-75 (Add, Sub, Neg and scalar Mul on `TlweCiphertext`, composed): out = constant + sum_{j < k} weight[j] * ct_j
+ * over Z/2^64, wrapping; in_a[j] [batch][n], in_b[j] [batch]; the constant is added to b only.  1 <= k <= 16.  out must not overlap an
+ * input. */
+int fhe_tlwe_lincomb(int k, const int32_t *weight, const uint64_t *const *in_a, const uint64_t *const *in_b, uint64_t constant,
+                     uint64_t *out_a, uint64_t *out_b, size_t n, size_t batch, fhe_mem mem, void *stream);
 
 /* ---- TFHE torus path at any TGLWE rank k (the reference's `TglweParam::n`: tglwe.rs:11-35; its TGLWE / TGGSW tests run at k = 2,
  * N = 256, base 2^8, d = 8: tglwe.rs:138-166, tggsw.rs:134-181) ------------------------------------------------------------- */
@@ -831,6 +850,37 @@ int fhe_fhew_circuit_run(const fhe_fhew_circuit *c, const fhe_bootstrap_key *bk,
                          const uint64_t *lwe_ksk_a, const uint64_t *lwe_ksk_b,
                          const uint64_t *in_a  /* [n_inputs][batch][N] */,  const uint64_t *in_b  /* [n_inputs][batch] */,
                          uint64_t *out_a       /* [n_outputs][batch][N] */, uint64_t *out_b       /* [n_outputs][batch] */,
+                         size_t batch, fhe_mem mem, void *stream);
+
+/* ---- TFHE look-up-table circuits: scheme/tfhe/src/bootstrapping.rs:118-165 bootstraps a `log_p`-bit message with one padding bit through
+ * a table per function (`identity`, `double`, `parity`).  Arithmetic in that style -- radix integers of message + carry blocks,
+ * comparisons, a bivariate function through 4x + y -- is a NETLIST of two steps: a free integer combination of TLWE ciphertexts
+ * (tlwe.rs:22-75) and one programmable bootstrap (bootstrapping.rs:78-82) through the table of the node.  Prepared once, run in one call:
+ * the nodes of one level, across the whole batch, form one batch of bootstraps, each job with its own table. */
+typedef struct fhe_tfhe_circuit fhe_tfhe_circuit;
+typedef struct { uint32_t wire; int32_t weight; } fhe_tfhe_term;
+typedef struct { uint32_t first_term, n_terms; uint64_t constant; uint32_t table; uint32_t pad; } fhe_tfhe_node;
+/* Wire w < n_inputs is input w, wire n_inputs + g is node g = bootstrap(tables[table], constant + sum of weight * wire over
+ * terms[first_term .. first_term + n_terms - 1]); a node reads wires below its own only; outputs[] may repeat a wire or name an input.
+ * FHE_ERR_INVALID (and no handle) for: a term range outside terms, n_terms == 0 or > 16, a forward or out-of-range wire, a weight of 0,
+ * table >= n_tables, n_inputs == 0, n_outputs == 0, more than 2^24 wires, n_tables > 65536.  Nodes no output depends on are dropped;
+ * every live node gets the level 1 + max(level of its inputs), inputs at level 0.  Host only: needs no device. */
+int  fhe_tfhe_circuit_create(const fhe_tfhe_node *nodes, size_t n_nodes, const fhe_tfhe_term *terms, size_t n_terms, size_t n_inputs,
+                             size_t n_tables, const uint32_t *outputs, size_t n_outputs, fhe_tfhe_circuit **out);
+void fhe_tfhe_circuit_destroy(fhe_tfhe_circuit *c);
+/* levels, nodes that are kept, nodes of the widest level (each pointer may be NULL) */
+int  fhe_tfhe_circuit_info(const fhe_tfhe_circuit *c, size_t *n_levels, size_t *n_live_nodes, size_t *max_width);
+int  fhe_tfhe_circuit_levels(const fhe_tfhe_circuit *c, uint32_t *level_of_node /* [n_nodes], 0 = dead */);
+/* The netlist on `batch` ciphertexts per wire: bit-identical, in every key form, to running the live nodes one by one through
+ * fhe_tlwe_lincomb and fhe_tfhe_bootstrap with v = tables[table].  Per level ONE pass over (nodes of the level) x batch jobs: a front
+ * kernel (gather, weighted sum + constant, `mod_switch` of bootstrapping.rs:99-104, the table index of every job), the blind rotation
+ * with a table per ciphertext (84-96), sample_extract(0) (tglwe.rs:115-127), the key switch (tlwe.rs:144-153) straight into the wire
+ * table; then one copy of the output wires.  tables [n_tables][n] with the n_tables of create; keys as for fhe_tfhe_bootstrap.  The
+ * outputs must not overlap the inputs.  Device-memory calls are asynchronous; host-memory calls mirror inputs, tables and outputs once. */
+int fhe_tfhe_circuit_run(const fhe_tfhe_circuit *c, const fhe_torus_ctx *t, const fhe_tggsw_key *brk, int ks_log_b, int ks_d,
+                         const uint64_t *ksk_a, const uint64_t *ksk_b, const uint64_t *tables /* [n_tables][n] */,
+                         const uint64_t *in_a  /* [n_inputs][batch][n_lwe] */,  const uint64_t *in_b  /* [n_inputs][batch] */,
+                         uint64_t *out_a       /* [n_outputs][batch][n_lwe] */, uint64_t *out_b       /* [n_outputs][batch] */,
                          size_t batch, fhe_mem mem, void *stream);
 
 #ifdef __cplusplus

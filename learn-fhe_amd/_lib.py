@@ -121,6 +121,16 @@ def lib():
         L.fhe_fhew_circuit_info.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
         L.fhe_fhew_circuit_levels.argtypes = [vp, u32p]
         L.fhe_fhew_circuit_run.argtypes = [vp, vp, C.c_uint64, ci, ci, vp, vp, vp, vp, vp, vp, sz, ci, vp]
+        # TFHE look-up-table circuits (torus_api.hip, tfhe_circuit_api.hip)
+        L.fhe_tfhe_blind_rotate_tables.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp, vp, sz, ci, vp]
+        L.fhe_tfhe_bootstrap_tables.argtypes = [vp, vp, ci, ci, vp, vp, vp, sz, vp, vp, vp, vp, vp, sz, ci, vp]
+        L.fhe_tlwe_lincomb.argtypes = [ci, C.POINTER(C.c_int32), vp, vp, C.c_uint64, vp, vp, sz, sz, ci, vp]
+        L.fhe_tfhe_circuit_create.argtypes = [vp, sz, vp, sz, sz, sz, u32p, sz, C.POINTER(vp)]
+        L.fhe_tfhe_circuit_destroy.argtypes = [vp]
+        L.fhe_tfhe_circuit_destroy.restype = None
+        L.fhe_tfhe_circuit_info.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
+        L.fhe_tfhe_circuit_levels.argtypes = [vp, u32p]
+        L.fhe_tfhe_circuit_run.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, sz, ci, vp]
         L.fhe_torus_ctx_create.argtypes = [ci, C.POINTER(vp)]
         L.fhe_torus_ctx_destroy.argtypes = [vp]
         L.fhe_torus_ctx_destroy.restype = None

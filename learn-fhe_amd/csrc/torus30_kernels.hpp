@@ -182,8 +182,8 @@ __global__ __launch_bounds__(W::THREADS, W::MIN_WAVES) void torus30_cmux_kernel(
 
 template <class W>
 __global__ __launch_bounds__(W::THREADS, W::MIN_WAVES) void torus30_blind_rotate_kernel(
-    const u64 *__restrict__ v, const u64 *__restrict__ a_tilde, const u64 *__restrict__ b_tilde, unsigned n_lwe, unsigned batch,
-    const unsigned *__restrict__ rows, size_t plane, TDecomp P, Torus30Consts T, u64 *__restrict__ out_a, u64 *__restrict__ out_b) {
+    const u64 *__restrict__ v, const unsigned *__restrict__ table_of, const u64 *__restrict__ a_tilde, const u64 *__restrict__ b_tilde, unsigned n_lwe,
+    unsigned batch, const unsigned *__restrict__ rows, size_t plane, TDecomp P, Torus30Consts T, u64 *__restrict__ out_a, u64 *__restrict__ out_b) {
     constexpr int E = W::E, N = W::N;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int lane = W::lane(), team = W::team();
@@ -191,6 +191,7 @@ __global__ __launch_bounds__(W::THREADS, W::MIN_WAVES) void torus30_blind_rotate
     if (ct >= batch) return;
     u64 *lds = reinterpret_cast<u64 *>(smem_raw) + team * W::TORUS_LDS_WORDS;
     u64 ca[E], cb[E];
+    if (table_of != nullptr) v += size_t(__builtin_amdgcn_readfirstlane(table_of[ct])) * N;  // this ciphertext's own table
     wave_load<W>(cb, v, lane);
 #pragma unroll
     for (int e = 0; e < E; ++e) ca[e] = 0;
@@ -340,8 +341,8 @@ __device__ __forceinline__ void team_torus_cmux30_pk(u64 (&ca)[W::E], u64 (&cb)[
 // that batch idle), 20.8 k against 21.8 k at 1280, 21.8 k against 26.4 k at 4096 -- recomputed addresses cost more than a fifth team hides.
 template <class W>
 __global__ __launch_bounds__(W::THREADS, W::MIN_WAVES) void torus30_blind_rotate_pk_kernel(
-    const u64 *__restrict__ v, const u64 *__restrict__ a_tilde, const u64 *__restrict__ b_tilde, unsigned n_lwe, unsigned batch,
-    const unsigned *__restrict__ rows, size_t plane, TDecomp P, Torus30Consts T, u64 *__restrict__ out_a, u64 *__restrict__ out_b) {
+    const u64 *__restrict__ v, const unsigned *__restrict__ table_of, const u64 *__restrict__ a_tilde, const u64 *__restrict__ b_tilde, unsigned n_lwe,
+    unsigned batch, const unsigned *__restrict__ rows, size_t plane, TDecomp P, Torus30Consts T, u64 *__restrict__ out_a, u64 *__restrict__ out_b) {
     constexpr int E = W::E, N = W::N;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int lane = W::lane(), team = W::team();
@@ -351,6 +352,7 @@ __global__ __launch_bounds__(W::THREADS, W::MIN_WAVES) void torus30_blind_rotate
     // cfg5 (N = 2^10, d = 3) 31 232 bytes -- FIVE teams per CU where the 8-limb maximum would leave room for four
     u64 *lds = reinterpret_cast<u64 *>(smem_raw) + team * (W::TORUS_LDS_WORDS + W::torus_dig_words(2 * P.d));
     u64 ca[E], cb[E];
+    if (table_of != nullptr) v += size_t(__builtin_amdgcn_readfirstlane(table_of[ct])) * N;  // this ciphertext's own table
     wave_load<W>(cb, v, lane);
 #pragma unroll
     for (int e = 0; e < E; ++e) ca[e] = 0;

@@ -2,6 +2,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -254,8 +256,8 @@ int fhe_torus_mul(const fhe_torus_ctx *t, uint64_t *a, const uint64_t *b, int lo
 
 void fhe_tggsw_key_destroy(fhe_tggsw_key *k) {
     if (!k) return;
-    if (k->t && k->t->device >= 0) {
-        DeviceGuard guard(k->t->device);
+    if (k->device >= 0) {
+        DeviceGuard guard(k->device);
         if (k->d_rows[0]) (void)hipFree(k->d_rows[0]);
         if (k->d_rows30) (void)hipFree(k->d_rows30);
         if (k->d_rowsf) (void)hipFree(k->d_rowsf);
@@ -338,7 +340,7 @@ int fhe_tggsw_prepare(const fhe_torus_ctx *t, int log_b, int d, const uint64_t *
     if (rc != FHE_OK) { if (dst) (void)hipFree(dst); if (dst30) (void)hipFree(dst30); if (dstx3) (void)hipFree(dstx3); return rc; }
     fhe_tggsw_key *k = new (std::nothrow) fhe_tggsw_key();
     if (!k) { if (dst) (void)hipFree(dst); if (dst30) (void)hipFree(dst30); if (dstx3) (void)hipFree(dstx3); return FHE_ERR_INVALID; }
-    k->t = t; k->log_n = log_n; k->log_b = log_b; k->d = d; k->count = count; k->P = P;
+    k->t = t; k->device = t->device; k->log_n = log_n; k->log_b = log_b; k->d = d; k->count = count; k->P = P;
     k->d_rows[0] = dst; k->d_rows[1] = dst ? dst + 2 * words : nullptr; k->d_rows30 = dst30; k->d_rowsx3 = dstx3;
     *out = k;
     return FHE_OK;
@@ -372,7 +374,7 @@ int fhe_tggsw_prepare_fft64(const fhe_torus_ctx *t, int log_b, int d, const uint
     if (rc != FHE_OK || hipStreamSynchronize(st) != hipSuccess) { (void)hipFree(dst); return FHE_ERR_HIP; }
     fhe_tggsw_key *k = new (std::nothrow) fhe_tggsw_key();
     if (!k) { (void)hipFree(dst); return FHE_ERR_INVALID; }
-    k->t = t; k->log_n = log_n; k->log_b = log_b; k->d = d; k->count = count; k->P = P; k->d_rowsf = dst;
+    k->t = t; k->device = t->device; k->log_n = log_n; k->log_b = log_b; k->d = d; k->count = count; k->P = P; k->d_rowsf = dst;
     *out = k;
     return FHE_OK;
 }
@@ -452,6 +454,99 @@ int fhe_tfhe_mod_switch(const uint64_t *in, uint64_t *out, size_t count, size_t 
     return mo.sync_out(st);
 }
 
+}  // extern "C"
+namespace {
+// bootstrapping.rs:84-96 on device buffers: acc = (0, v).rotate(-b), then fold cmux(brk_i, acc, acc.rotate(a_i)) (91-95): one launch, the
+// accumulator never leaves the registers of the team that owns the ciphertext.  table_of null: v [n] serves the batch; else v is
+// [n_tables][n] and ciphertext i starts from row table_of[i] (device array, in range: the kernels do not clamp).
+int blind_rotate_dev(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, const u64 *at, const u64 *bt, const u64 *v, const unsigned *table_of, u64 *oa,
+                     u64 *ob, size_t batch, hipStream_t st) {
+    const size_t n = size_t(1) << brk->log_n, n_lwe = brk->count;
+    if (batch > 0x7fffffffull || n_lwe > 0x7fffffffull) return FHE_ERR_UNSUPPORTED;
+    if (brk->d_rowsf) {  // fft64 mode
+        return with_torus<TorusRingF>(brk->log_n, [&](auto wr) {
+            using WR = typename decltype(wr)::type;
+            return fhe::launch_teams<fhe::torusf_blind_rotate_kernel<WR, TF_MIN_WAVES>, WR>(batch, fhe::TorusF<WR>::LDS_BYTES, st, v, table_of, at, bt,
+                                                                                            (unsigned)n_lwe, (unsigned)batch, (const double2 *)brk->d_rowsf,
+                                                                                            brk->P, (const double2 *)t->d_twf, oa, ob);
+        });
+    }
+    if (brk->d_rowsx3) {  // exact, three key pieces through f64 transforms
+        return with_torus<TorusRingF>(brk->log_n, [&](auto wr) {
+            using WR = typename decltype(wr)::type;
+            return fhe::launch_teams<fhe::torusx3_blind_rotate_kernel<WR, TF_MIN_WAVES>, WR>(batch, fhe::TorusX3<WR>::lds_bytes(2 * brk->d), st, v, table_of, at,
+                                                                                             bt, (unsigned)n_lwe, (unsigned)batch,
+                                                                                             (const double2 *)brk->d_rowsx3, brk->P,
+                                                                                             (const double2 *)t->d_twf, oa, ob);
+        });
+    }
+    if (brk->d_rows30) {  // three 30-bit primes
+        const size_t plane = brk->count * size_t(2 * brk->d) * 2 * n;
+        // base <= 2^8 and at most 8 limbs (cfg5: base 2^7, d = 3): the CMUX digits are computed once and parked as bytes, the
+        // multiply-accumulate runs unreduced (torus30_kernels.hpp); lab switch NO_PACKED_DIGITS keeps the older kernel (bit-identical)
+        // (a digit of base 2^8 ranges over [-128, 128]: one value too many for a byte)
+        const bool packed = brk->P.log_b <= 7 && 2 * brk->d <= 8 && brk->log_n >= 8 && fhe::opt(fhe::OPT_NO_PACKED_DIGITS) == 0;
+        if (packed) {
+            return with_torus<TorusRing30>(brk->log_n, [&](auto wr) {
+                using WR = typename decltype(wr)::type;
+                return fhe::launch_teams<fhe::torus30_blind_rotate_pk_kernel<WR>, WR>(batch, WR::torus_pk_lds_bytes(2 * brk->d), st, v, table_of, at, bt,
+                                                                                      (unsigned)n_lwe, (unsigned)batch, (const unsigned *)brk->d_rows30, plane,
+                                                                                      brk->P, t->T30, oa, ob);
+            });
+        }
+        return with_torus<TorusRing30>(brk->log_n, [&](auto wr) {
+            using WR = typename decltype(wr)::type;
+            return fhe::launch_teams<fhe::torus30_blind_rotate_kernel<WR>, WR>(batch, WR::TORUS_LDS_BYTES, st, v, table_of, at, bt, (unsigned)n_lwe,
+                                                                               (unsigned)batch, (const unsigned *)brk->d_rows30, plane, brk->P, t->T30, oa, ob);
+        });
+    }
+    return with_torus<TorusRing>(brk->log_n, [&](auto wr) {
+        using WR = typename decltype(wr)::type;
+        return fhe::launch_teams<fhe::torus_blind_rotate_kernel<WR>, WR>(batch, WR::TORUS_LDS_BYTES, st, v, table_of, at, bt, (unsigned)n_lwe, (unsigned)batch,
+                                                                         (const u64 *)brk->d_rows[0], (const u64 *)brk->d_rows[1], brk->P, t->T, oa, ob);
+    });
+}
+
+// The table index of every ciphertext on the device.  Device memory: the caller's array as it is (its range is the caller's to guarantee).
+// Host memory: every index checked against n_tables, then mirrored (two indices to a word; the staging copy lives as long as this does).
+struct TableOf {
+    std::vector<u64> staged;
+    std::unique_ptr<Mirror> m;
+    const unsigned *d = nullptr;
+    int rc = FHE_OK;
+    TableOf(const uint32_t *table_of, size_t batch, size_t n_tables, fhe_mem mem, hipStream_t st) {
+        if (mem == FHE_MEM_DEVICE) { d = table_of; return; }
+        for (size_t i = 0; i < batch; ++i)
+            if (table_of[i] >= n_tables) { rc = FHE_ERR_INVALID; return; }
+        staged.assign((batch + 1) / 2, 0);
+        std::memcpy(staged.data(), table_of, batch * sizeof(uint32_t));
+        m.reset(new Mirror(staged.data(), staged.size(), mem, true, st));
+        rc = m->rc;
+        d = (const unsigned *)m->d;
+    }
+};
+constexpr size_t MAX_TABLES = 65536;
+
+// fhe_tfhe_blind_rotate (table_of null, n_tables = 1: v [n]) and fhe_tfhe_blind_rotate_tables
+int blind_rotate_any(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, const uint64_t *a_tilde, const uint64_t *b_tilde, const uint64_t *v,
+                     size_t n_tables, const uint32_t *table_of, uint64_t *out_a, uint64_t *out_b, size_t batch, fhe_mem mem, void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    DeviceGuard guard(t->device);
+    if (!guard.ok) return FHE_ERR_HIP;
+    const size_t n = size_t(1) << brk->log_n, n_lwe = brk->count;
+    TableOf tof(table_of, table_of ? batch : 0, n_tables, table_of ? mem : FHE_MEM_DEVICE, st);
+    if (tof.rc != FHE_OK) return tof.rc;
+    Mirror ma(a_tilde, n_lwe * batch, mem, true, st), mb(b_tilde, batch, mem, true, st), mv(v, n_tables * n, mem, true, st);
+    Mirror moa(out_a, n * batch, mem, false, st), mob(out_b, n * batch, mem, false, st);
+    if (ma.rc | mb.rc | mv.rc | moa.rc | mob.rc) return FHE_ERR_HIP;
+    int rc = blind_rotate_dev(t, brk, ma.d, mb.d, mv.d, tof.d, moa.d, mob.d, batch, st);
+    if (rc == FHE_OK) rc = moa.sync_out(st);
+    if (rc == FHE_OK) rc = mob.sync_out(st);
+    return rc;
+}
+}  // namespace
+extern "C" {
+
 // scheme/tfhe/src/bootstrapping.rs:84-96 `blind_rotate` for a batch (k = 1): brk = key (n_lwe TGGSW ciphertexts);
 // a_tilde [batch][n_lwe], b_tilde [batch]: the mod-switched TLWE ciphertexts (values mod 2N); v: the ENCODED test polynomial
 // (Tglwe::encode(v), [n] torus values, shared by the batch); out_a, out_b [batch][n].
@@ -459,65 +554,20 @@ int fhe_tfhe_blind_rotate(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, cons
                           const uint64_t *v, uint64_t *out_a, uint64_t *out_b, size_t batch, fhe_mem mem, void *stream) {
     if (!t || !brk || brk->t != t || ((!a_tilde || !b_tilde || !v || !out_a || !out_b) && batch)) return FHE_ERR_INVALID;
     if (batch == 0) return FHE_OK;
-    hipStream_t st = (hipStream_t)stream;
-    DeviceGuard guard(t->device);
-    if (!guard.ok) return FHE_ERR_HIP;
-    const size_t n = size_t(1) << brk->log_n, n_lwe = brk->count;
-    Mirror ma(a_tilde, n_lwe * batch, mem, true, st), mb(b_tilde, batch, mem, true, st), mv(v, n, mem, true, st);
-    Mirror moa(out_a, n * batch, mem, false, st), mob(out_b, n * batch, mem, false, st);
-    if (ma.rc | mb.rc | mv.rc | moa.rc | mob.rc) return FHE_ERR_HIP;
-    if (batch > 0x7fffffffull || n_lwe > 0x7fffffffull) return FHE_ERR_UNSUPPORTED;
-    // acc = (0, v).rotate(-b), then fold cmux(brk_i, acc, acc.rotate(a_i)) (bootstrapping.rs:91-95): one launch, the
-    // accumulator never leaves the registers of the team that owns the ciphertext
-    int rc = FHE_OK;
-    if (brk->d_rowsf) {  // fft64 mode
-        rc = with_torus<TorusRingF>(brk->log_n, [&](auto wr) {
-            using WR = typename decltype(wr)::type;
-            return fhe::launch_teams<fhe::torusf_blind_rotate_kernel<WR, TF_MIN_WAVES>, WR>(batch, fhe::TorusF<WR>::LDS_BYTES, st, (const u64 *)mv.d,
-                                                                                            (const u64 *)ma.d, (const u64 *)mb.d, (unsigned)n_lwe,
-                                                                                            (unsigned)batch, (const double2 *)brk->d_rowsf, brk->P,
-                                                                                            (const double2 *)t->d_twf, moa.d, mob.d);
-        });
-    } else if (brk->d_rowsx3) {  // exact, three key pieces through f64 transforms
-        rc = with_torus<TorusRingF>(brk->log_n, [&](auto wr) {
-            using WR = typename decltype(wr)::type;
-            return fhe::launch_teams<fhe::torusx3_blind_rotate_kernel<WR, TF_MIN_WAVES>, WR>(batch, fhe::TorusX3<WR>::lds_bytes(2 * brk->d), st,
-                                                                                             (const u64 *)mv.d, (const u64 *)ma.d, (const u64 *)mb.d,
-                                                                                             (unsigned)n_lwe, (unsigned)batch, (const double2 *)brk->d_rowsx3,
-                                                                                             brk->P, (const double2 *)t->d_twf, moa.d, mob.d);
-        });
-    } else if (brk->d_rows30) {  // three 30-bit primes
-        const size_t plane = brk->count * size_t(2 * brk->d) * 2 * n;
-        // base <= 2^8 and at most 8 limbs (cfg5: base 2^7, d = 3): the CMUX digits are computed once and parked as bytes, the
-        // multiply-accumulate runs unreduced (torus30_kernels.hpp); lab switch NO_PACKED_DIGITS keeps the older kernel (bit-identical)
-        // (a digit of base 2^8 ranges over [-128, 128]: one value too many for a byte)
-        const bool packed = brk->P.log_b <= 7 && 2 * brk->d <= 8 && brk->log_n >= 8 && fhe::opt(fhe::OPT_NO_PACKED_DIGITS) == 0;
-        if (packed) {
-            rc = with_torus<TorusRing30>(brk->log_n, [&](auto wr) {
-                using WR = typename decltype(wr)::type;
-                return fhe::launch_teams<fhe::torus30_blind_rotate_pk_kernel<WR>, WR>(batch, WR::torus_pk_lds_bytes(2 * brk->d), st, (const u64 *)mv.d,
-                                                                                      (const u64 *)ma.d, (const u64 *)mb.d, (unsigned)n_lwe, (unsigned)batch,
-                                                                                      (const unsigned *)brk->d_rows30, plane, brk->P, t->T30, moa.d, mob.d);
-            });
-        } else {
-            rc = with_torus<TorusRing30>(brk->log_n, [&](auto wr) {
-                using WR = typename decltype(wr)::type;
-                return fhe::launch_teams<fhe::torus30_blind_rotate_kernel<WR>, WR>(batch, WR::TORUS_LDS_BYTES, st, (const u64 *)mv.d, (const u64 *)ma.d,
-                                                                                   (const u64 *)mb.d, (unsigned)n_lwe, (unsigned)batch,
-                                                                                   (const unsigned *)brk->d_rows30, plane, brk->P, t->T30, moa.d, mob.d);
-            });
-        }
-    } else {
-        rc = with_torus<TorusRing>(brk->log_n, [&](auto wr) {
-            using WR = typename decltype(wr)::type;
-            return fhe::launch_teams<fhe::torus_blind_rotate_kernel<WR>, WR>(batch, WR::TORUS_LDS_BYTES, st, (const u64 *)mv.d, (const u64 *)ma.d,
-                                                                             (const u64 *)mb.d, (unsigned)n_lwe, (unsigned)batch, (const u64 *)brk->d_rows[0],
-                                                                             (const u64 *)brk->d_rows[1], brk->P, t->T, moa.d, mob.d);
-        });
-    }
-    if (rc == FHE_OK) rc = moa.sync_out(st);
-    if (rc == FHE_OK) rc = mob.sync_out(st);
-    return rc;
+    return blind_rotate_any(t, brk, a_tilde, b_tilde, v, 1, nullptr, out_a, out_b, batch, mem, stream);
+}
+
+// The same with one test polynomial PER CIPHERTEXT: tables [n_tables][n] encoded (bootstrapping.rs:118-128 `table` builds one per
+// function), ciphertext i rotates tables[table_of[i]].  Per ciphertext the arithmetic is that of fhe_tfhe_blind_rotate with
+// v = tables[table_of[i]]: the same bits in every key form.  Host memory: an index >= n_tables is FHE_ERR_INVALID; device memory: the
+// caller guarantees the range (nothing is clamped).
+int fhe_tfhe_blind_rotate_tables(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, const uint64_t *a_tilde, const uint64_t *b_tilde,
+                                 const uint64_t *tables, size_t n_tables, const uint32_t *table_of, uint64_t *out_a, uint64_t *out_b, size_t batch,
+                                 fhe_mem mem, void *stream) {
+    if (!t || !brk || brk->t != t || n_tables == 0 || n_tables > MAX_TABLES || !tables) return FHE_ERR_INVALID;
+    if ((!a_tilde || !b_tilde || !table_of || !out_a || !out_b) && batch) return FHE_ERR_INVALID;
+    if (batch == 0) return FHE_OK;
+    return blind_rotate_any(t, brk, a_tilde, b_tilde, tables, n_tables, table_of, out_a, out_b, batch, mem, stream);
 }
 
 // scheme/tfhe/src/tglwe.rs:115-127 `sample_extract(ct, i)` (k = 1): ct_a, ct_b [batch][n] -> TLWE (out_a [batch][n], out_b [batch])
@@ -584,6 +634,40 @@ int fhe_tlwe_key_switch(int log_b, int d, const uint64_t *ksk_a, const uint64_t 
     return rc != FHE_OK ? rc : mob.sync_out(st);
 }
 
+}  // extern "C"
+namespace {
+// fhe_tfhe_bootstrap (table_of null, n_tables = 1: v [n]) and fhe_tfhe_bootstrap_tables
+int bootstrap_any(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, int ks_log_b, int ks_d, const uint64_t *ksk_a, const uint64_t *ksk_b,
+                  const uint64_t *v, size_t n_tables, const uint32_t *table_of, const uint64_t *lwe_a, const uint64_t *lwe_b, uint64_t *out_a,
+                  uint64_t *out_b, size_t batch, fhe_mem mem, void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    DeviceGuard guard(t->device);
+    if (!guard.ok) return FHE_ERR_HIP;
+    const size_t n = size_t(1) << brk->log_n, n_lwe = brk->count, rows = n * ks_d;
+    TableOf tof(table_of, table_of ? batch : 0, n_tables, table_of ? mem : FHE_MEM_DEVICE, st);
+    if (tof.rc != FHE_OK) return tof.rc;
+    Mirror mka(ksk_a, rows * n_lwe, mem, true, st), mkb(ksk_b, rows, mem, true, st), mv(v, n_tables * n, mem, true, st),
+        ma(lwe_a, n_lwe * batch, mem, true, st), mb(lwe_b, batch, mem, true, st), moa(out_a, n_lwe * batch, mem, false, st),
+        mob(out_b, batch, mem, false, st);
+    if (mka.rc | mkb.rc | mv.rc | ma.rc | mb.rc | moa.rc | mob.rc) return FHE_ERR_HIP;
+    StreamWs ws((batch * n_lwe + batch + 3 * batch * n + batch) * sizeof(u64), st);  // a~ | b~ | acc.a | acc.b | extracted a | b
+    if (ws.rc != FHE_OK) return ws.rc;
+    u64 *at = ws.as<u64>(), *bt = at + batch * n_lwe, *ra = bt + batch, *rb = ra + batch * n, *ea = rb + batch * n, *eb = ea + batch * n;
+    typedef uint64_t U;
+    int rc = fhe_tfhe_mod_switch((const U *)ma.d, (U *)at, batch * n_lwe, n, FHE_MEM_DEVICE, stream);
+    if (rc == FHE_OK) rc = fhe_tfhe_mod_switch((const U *)mb.d, (U *)bt, batch, n, FHE_MEM_DEVICE, stream);
+    if (rc == FHE_OK) rc = blind_rotate_dev(t, brk, at, bt, mv.d, tof.d, ra, rb, batch, st);
+    if (rc == FHE_OK) rc = fhe_tglwe_sample_extract((const U *)ra, (const U *)rb, n, 0, (U *)ea, (U *)eb, batch, FHE_MEM_DEVICE, stream);
+    if (rc == FHE_OK)
+        rc = fhe_tlwe_key_switch(ks_log_b, ks_d, (const U *)mka.d, (const U *)mkb.d, (const U *)ea, (const U *)eb, n, n_lwe, (U *)moa.d, (U *)mob.d, batch,
+                                 FHE_MEM_DEVICE, stream);
+    if (rc == FHE_OK) rc = moa.sync_out(st);
+    if (rc == FHE_OK) rc = mob.sync_out(st);
+    return rc;
+}
+}  // namespace
+extern "C" {
+
 // scheme/tfhe/src/bootstrapping.rs:78-82 `Bootstrapping::bootstrap` for `batch` TLWE ciphertexts in ONE call: mod switch (99-104),
 // blind rotation (84-96), sample_extract(0) (tglwe.rs:115-127), TLWE key switch (tlwe.rs:144-153), all on `stream`, intermediates
 // in stream-ordered scratch.  Bit-identical to the four separate calls.
@@ -595,28 +679,48 @@ int fhe_tfhe_bootstrap(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, int ks_
     if (rc != FHE_OK) return rc;
     if (!t || !brk || brk->t != t || !ksk_a || !ksk_b || !v || ((!lwe_a || !lwe_b || !out_a || !out_b) && batch)) return FHE_ERR_INVALID;
     if (batch == 0) return FHE_OK;
+    return bootstrap_any(t, brk, ks_log_b, ks_d, ksk_a, ksk_b, v, 1, nullptr, lwe_a, lwe_b, out_a, out_b, batch, mem, stream);
+}
+
+// The same through one table per ciphertext (bootstrapping.rs:118-165: a table per function): tables [n_tables][n] encoded, ciphertext i
+// goes through tables[table_of[i]]; indices as for fhe_tfhe_blind_rotate_tables.  Bit-identical to fhe_tfhe_bootstrap with that table.
+int fhe_tfhe_bootstrap_tables(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, int ks_log_b, int ks_d, const uint64_t *ksk_a, const uint64_t *ksk_b,
+                              const uint64_t *tables, size_t n_tables, const uint32_t *table_of, const uint64_t *lwe_a, const uint64_t *lwe_b,
+                              uint64_t *out_a, uint64_t *out_b, size_t batch, fhe_mem mem, void *stream) {
+    fhe::TDecomp P;
+    int rc = make_tdecomp(ks_log_b, ks_d, &P);
+    if (rc != FHE_OK) return rc;
+    if (!t || !brk || brk->t != t || !ksk_a || !ksk_b || !tables || n_tables == 0 || n_tables > MAX_TABLES) return FHE_ERR_INVALID;
+    if ((!table_of || !lwe_a || !lwe_b || !out_a || !out_b) && batch) return FHE_ERR_INVALID;
+    if (batch == 0) return FHE_OK;
+    return bootstrap_any(t, brk, ks_log_b, ks_d, ksk_a, ksk_b, tables, n_tables, table_of, lwe_a, lwe_b, out_a, out_b, batch, mem, stream);
+}
+
+// scheme/tfhe/src/tlwe.rs:22-75 (Add, Sub, Neg and scalar Mul on `TlweCiphertext`, composed): out = constant + sum_{j < k} weight[j] * ct_j
+// over Z/2^64, wrapping, on a [batch][n] and b [batch] alike; the constant goes to b only.  k <= 16; out must not overlap an input.
+int fhe_tlwe_lincomb(int k, const int32_t *weight, const uint64_t *const *in_a, const uint64_t *const *in_b, uint64_t constant, uint64_t *out_a,
+                     uint64_t *out_b, size_t n, size_t batch, fhe_mem mem, void *stream) {
+    if (k < 1 || k > fhe::TLWE_LINCOMB_MAX || !weight || !in_a || !in_b || n == 0 || ((!out_a || !out_b) && batch)) return FHE_ERR_INVALID;
+    for (int j = 0; j < k; ++j)
+        if ((!in_a[j] || !in_b[j]) && batch) return FHE_ERR_INVALID;
+    if (batch == 0) return FHE_OK;
+    PtrDeviceGuard pguard(out_a, mem);
+    if (!pguard.ok) return FHE_ERR_HIP;
     hipStream_t st = (hipStream_t)stream;
-    DeviceGuard guard(t->device);
-    if (!guard.ok) return FHE_ERR_HIP;
-    const size_t n = size_t(1) << brk->log_n, n_lwe = brk->count, rows = n * ks_d;
-    Mirror mka(ksk_a, rows * n_lwe, mem, true, st), mkb(ksk_b, rows, mem, true, st), mv(v, n, mem, true, st),
-        ma(lwe_a, n_lwe * batch, mem, true, st), mb(lwe_b, batch, mem, true, st), moa(out_a, n_lwe * batch, mem, false, st),
-        mob(out_b, batch, mem, false, st);
-    if (mka.rc | mkb.rc | mv.rc | ma.rc | mb.rc | moa.rc | mob.rc) return FHE_ERR_HIP;
-    StreamWs ws((batch * n_lwe + batch + 3 * batch * n + batch) * sizeof(u64), st);  // a~ | b~ | acc.a | acc.b | extracted a | b
-    if (ws.rc != FHE_OK) return ws.rc;
-    u64 *at = ws.as<u64>(), *bt = at + batch * n_lwe, *ra = bt + batch, *rb = ra + batch * n, *ea = rb + batch * n, *eb = ea + batch * n;
-    typedef uint64_t U;
-    rc = fhe_tfhe_mod_switch((const U *)ma.d, (U *)at, batch * n_lwe, n, FHE_MEM_DEVICE, stream);
-    if (rc == FHE_OK) rc = fhe_tfhe_mod_switch((const U *)mb.d, (U *)bt, batch, n, FHE_MEM_DEVICE, stream);
-    if (rc == FHE_OK) rc = fhe_tfhe_blind_rotate(t, brk, (const U *)at, (const U *)bt, (const U *)mv.d, (U *)ra, (U *)rb, batch, FHE_MEM_DEVICE, stream);
-    if (rc == FHE_OK) rc = fhe_tglwe_sample_extract((const U *)ra, (const U *)rb, n, 0, (U *)ea, (U *)eb, batch, FHE_MEM_DEVICE, stream);
-    if (rc == FHE_OK)
-        rc = fhe_tlwe_key_switch(ks_log_b, ks_d, (const U *)mka.d, (const U *)mkb.d, (const U *)ea, (const U *)eb, n, n_lwe, (U *)moa.d, (U *)mob.d, batch,
-                                 FHE_MEM_DEVICE, stream);
-    if (rc == FHE_OK) rc = moa.sync_out(st);
-    if (rc == FHE_OK) rc = mob.sync_out(st);
-    return rc;
+    std::unique_ptr<Mirror> ma[fhe::TLWE_LINCOMB_MAX], mb[fhe::TLWE_LINCOMB_MAX];
+    fhe::TlweLinComb L{};
+    L.k = k;
+    for (int j = 0; j < k; ++j) {
+        ma[j].reset(new Mirror(in_a[j], n * batch, mem, true, st));
+        mb[j].reset(new Mirror(in_b[j], batch, mem, true, st));
+        if (ma[j]->rc | mb[j]->rc) return FHE_ERR_HIP;
+        L.a[j] = ma[j]->d; L.b[j] = mb[j]->d; L.w[j] = weight[j];
+    }
+    Mirror moa(out_a, n * batch, mem, false, st), mob(out_b, batch, mem, false, st);
+    if (moa.rc | mob.rc) return FHE_ERR_HIP;
+    FHE_TRY(fhe::launch<fhe::tlwe_lincomb_kernel>(grid_for(n * batch + batch), 256, 0, st, L, (u64)constant, moa.d, mob.d, n * batch, batch));
+    int rc = moa.sync_out(st);
+    return rc != FHE_OK ? rc : mob.sync_out(st);
 }
 
 // ---- TFHE key material on the device -----------------------------------------------------

@@ -23,6 +23,7 @@ struct fhe_torus_ctx {
 
 struct fhe_tggsw_key {
     const fhe_torus_ctx *t = nullptr;
+    int device = -1;  // t's device, kept here: destroying the key must not read a context that may be gone already
     int log_n = 0, log_b = 0, d = 0;
     size_t count = 0;
     u64 *d_rows[2] = {nullptr, nullptr};  // per prime: [count][2d][2][N] evaluation domain, key_perm layout

@@ -216,10 +216,13 @@ __global__ __launch_bounds__(W::THREADS, W::MIN_WAVES) void torus_cmux_kernel(
 // scheme/tfhe/src/bootstrapping.rs:84-96 `blind_rotate` (k = 1), the whole fold in ONE launch: acc = (0, v X^-b), then
 // acc <- cmux(brk_i, acc, acc X^(a_i)) for i = 0 .. n_lwe-1, the accumulator in the team's registers throughout.
 // rows0 / rows1: the key set [n_lwe][2d][2][N] per prime (key_perm layout); a_tilde [batch][n_lwe], b_tilde [batch] mod 2N.
+// table_of (all five blind-rotation kernels): null = every ciphertext starts from v; else ciphertext ct starts from
+// v + table_of[ct] * N (v: [n_tables][N]).  The index is uniform across the team, read once and kept scalar; it is NOT range-checked
+// here: the entry points check host-memory indices, device-memory callers guarantee table_of[ct] < n_tables.
 template <class W>
 __global__ __launch_bounds__(W::THREADS, W::MIN_WAVES) void torus_blind_rotate_kernel(
-    const u64 *__restrict__ v, const u64 *__restrict__ a_tilde, const u64 *__restrict__ b_tilde, unsigned n_lwe, unsigned batch,
-    const u64 *__restrict__ rows0, const u64 *__restrict__ rows1, TDecomp P, TorusConsts T, u64 *__restrict__ out_a, u64 *__restrict__ out_b) {
+    const u64 *__restrict__ v, const unsigned *__restrict__ table_of, const u64 *__restrict__ a_tilde, const u64 *__restrict__ b_tilde, unsigned n_lwe,
+    unsigned batch, const u64 *__restrict__ rows0, const u64 *__restrict__ rows1, TDecomp P, TorusConsts T, u64 *__restrict__ out_a, u64 *__restrict__ out_b) {
     constexpr int E = W::E, N = W::N;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int lane = W::lane(), team = W::team();
@@ -227,6 +230,7 @@ __global__ __launch_bounds__(W::THREADS, W::MIN_WAVES) void torus_blind_rotate_k
     if (ct >= batch) return;
     u64 *lds = reinterpret_cast<u64 *>(smem_raw) + team * W::TORUS_LDS_WORDS;
     u64 ca[E], cb[E];
+    if (table_of != nullptr) v += size_t(__builtin_amdgcn_readfirstlane(table_of[ct])) * N;  // this ciphertext's own table
     wave_load<W>(cb, v, lane);
 #pragma unroll
     for (int e = 0; e < E; ++e) ca[e] = 0;
@@ -312,6 +316,24 @@ FHE_HEADER_KERNEL void tlwe_key_switch_kernel(const u64 *__restrict__ ct_a, cons
 // out = x + y (sub = 0) or x - y (sub = 1), wrapping mod 2^64 (util/src/torus.rs:40-60)
 FHE_HEADER_KERNEL void torus_addsub_kernel(const u64 *__restrict__ x, const u64 *__restrict__ y, u64 *__restrict__ out, size_t count, int sub) {
     for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < count; i += size_t(gridDim.x) * blockDim.x) out[i] = sub ? x[i] - y[i] : x[i] + y[i];
+}
+// scheme/tfhe/src/tlwe.rs:22-75 (Add / Sub / Neg / scalar Mul on TlweCiphertext, composed): out = constant + sum_t w[t] * ct_t, wrapping
+// mod 2^64; a [batch][n] and b [batch] of every term, the constant on b only.  Items 0 .. n batch - 1 are the a words, the rest the b words.
+constexpr int TLWE_LINCOMB_MAX = 16;
+struct TlweLinComb {
+    const u64 *a[TLWE_LINCOMB_MAX], *b[TLWE_LINCOMB_MAX];
+    int w[TLWE_LINCOMB_MAX];
+    int k;
+};
+FHE_HEADER_KERNEL void tlwe_lincomb_kernel(TlweLinComb L, u64 constant, u64 *__restrict__ out_a, u64 *__restrict__ out_b, size_t words_a, size_t batch) {
+    const size_t total = words_a + batch;
+    for (size_t idx = blockIdx.x * size_t(blockDim.x) + threadIdx.x; idx < total; idx += size_t(gridDim.x) * blockDim.x) {
+        const bool is_b = idx >= words_a;
+        const size_t i = is_b ? idx - words_a : idx;
+        u64 acc = is_b ? constant : 0;
+        for (int t = 0; t < L.k; ++t) acc += u64(int64_t(L.w[t])) * (is_b ? L.b[t] : L.a[t])[i];
+        (is_b ? out_b : out_a)[i] = acc;
+    }
 }
 // scheme/tfhe/src/tglwe.rs:61-66 `rotate(i)` = every polynomial times X^i (util/src/ring.rs:299-313, 380-406 on T64): k = i mod 2N,
 // rotate right by k mod N, negate what wraps (and everything once more if k >= N).  in, out [polys][n], in != out

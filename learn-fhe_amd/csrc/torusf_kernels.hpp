@@ -259,7 +259,7 @@ __global__ __launch_bounds__(W::THREADS, MIN_WAVES) void torusf_cmux_kernel(u64 
 
 // bootstrapping.rs:84-96 in one launch, as torus30_blind_rotate_kernel; rows: [n_lwe][2d][2][M] complex
 template <class W, int MIN_WAVES>
-__global__ __launch_bounds__(W::THREADS, MIN_WAVES) void torusf_blind_rotate_kernel(const u64 *__restrict__ v, const u64 *__restrict__ a_tilde,
+__global__ __launch_bounds__(W::THREADS, MIN_WAVES) void torusf_blind_rotate_kernel(const u64 *__restrict__ v, const unsigned *__restrict__ table_of, const u64 *__restrict__ a_tilde,
                                                                                     const u64 *__restrict__ b_tilde, unsigned n_lwe, unsigned batch,
                                                                                     const double2 *__restrict__ rows, TDecomp P,
                                                                                     const double2 *__restrict__ tw, u64 *__restrict__ out_a,
@@ -272,6 +272,7 @@ __global__ __launch_bounds__(W::THREADS, MIN_WAVES) void torusf_blind_rotate_ker
     if (ct >= batch) return;
     u64 *lds = reinterpret_cast<u64 *>(smem_raw) + team * TorusF<W>::LDS_WORDS;
     u64 ca[2 * E], cb[2 * E];
+    if (table_of != nullptr) v += size_t(__builtin_amdgcn_readfirstlane(table_of[ct])) * N;  // this ciphertext's own table
     pairs_load<W>(cb, v, lane);
 #pragma unroll
     for (int e = 0; e < 2 * E; ++e) ca[e] = 0;
@@ -493,7 +494,7 @@ __global__ __launch_bounds__(W::THREADS, MIN_WAVES) void torusx3_cmux_kernel(u64
 
 // bootstrapping.rs:84-96 in one launch; rows: [n_lwe][2d][2][3][M] complex
 template <class W, int MIN_WAVES>
-__global__ __launch_bounds__(W::THREADS, MIN_WAVES) void torusx3_blind_rotate_kernel(const u64 *__restrict__ v, const u64 *__restrict__ a_tilde,
+__global__ __launch_bounds__(W::THREADS, MIN_WAVES) void torusx3_blind_rotate_kernel(const u64 *__restrict__ v, const unsigned *__restrict__ table_of, const u64 *__restrict__ a_tilde,
                                                                                      const u64 *__restrict__ b_tilde, unsigned n_lwe, unsigned batch,
                                                                                      const double2 *__restrict__ rows, TDecomp P,
                                                                                      const double2 *__restrict__ tw, u64 *__restrict__ out_a,
@@ -506,6 +507,7 @@ __global__ __launch_bounds__(W::THREADS, MIN_WAVES) void torusx3_blind_rotate_ke
     if (ct >= batch) return;
     u64 *lds = reinterpret_cast<u64 *>(smem_raw) + team * TorusX3<W>::lds_words(2 * P.d);
     u64 ca[2 * E], cb[2 * E];
+    if (table_of != nullptr) v += size_t(__builtin_amdgcn_readfirstlane(table_of[ct])) * N;  // this ciphertext's own table
     pairs_load<W>(cb, v, lane);
 #pragma unroll
     for (int e = 0; e < 2 * E; ++e) ca[e] = 0;

@@ -12,6 +12,7 @@
 
 struct fhe_tggswk_key {
     const fhe_torus_ctx *t = nullptr;
+    int device = -1;  // t's device, kept here: destroying the key must not read a context that may be gone already
     int k = 0, log_n = 0;
     size_t count = 0;
     u64 *d_eval = nullptr;  // [count][(k + 1) d][k + 1][2 primes][n], evaluation domain
@@ -96,8 +97,8 @@ extern "C" {
 
 void fhe_tggswk_key_destroy(fhe_tggswk_key *key) {
     if (!key) return;
-    if (key->t && key->t->device >= 0 && key->d_eval) {
-        DeviceGuard guard(key->t->device);
+    if (key->device >= 0 && key->d_eval) {
+        DeviceGuard guard(key->device);
         (void)hipFree(key->d_eval);
     }
     delete key;
@@ -129,7 +130,7 @@ int fhe_tggswk_prepare(const fhe_torus_ctx *t, int k, int log_b, int d, const ui
     if (rc == FHE_OK && hipStreamSynchronize(st) != hipSuccess) rc = FHE_ERR_HIP;
     fhe_tggswk_key *key = rc == FHE_OK ? new (std::nothrow) fhe_tggswk_key() : nullptr;
     if (!key) { (void)hipFree(eval); return rc != FHE_OK ? rc : FHE_ERR_INVALID; }
-    key->t = t; key->k = k; key->log_n = log_n; key->count = count; key->d_eval = eval; key->P = P;
+    key->t = t; key->device = t->device; key->k = k; key->log_n = log_n; key->count = count; key->d_eval = eval; key->P = P;
     *out = key;
     return FHE_OK;
 }

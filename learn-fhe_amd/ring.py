@@ -24,6 +24,15 @@ def _buf(x):
     return C.c_void_p(x.ctypes.data), x.size, L.MEM_HOST, C.c_void_p(0)
 
 
+def _buf32(x):
+    """_buf for arrays of 32-bit indices (numpy uint32, or a torch int32 CUDA tensor) -> (pointer, element count, mem kind)"""
+    if _is_torch(x):
+        assert x.is_cuda and x.is_contiguous() and x.element_size() == 4
+        return C.c_void_p(x.data_ptr()), x.numel(), L.MEM_DEVICE
+    assert isinstance(x, np.ndarray) and x.dtype == np.uint32 and x.flags["C_CONTIGUOUS"]
+    return C.c_void_p(x.ctypes.data), x.size, L.MEM_HOST
+
+
 def _cbuf(x):
     """_buf for complex128 slot arrays -> (pointer, complex element count, mem kind, stream handle)"""
     if _is_torch(x):
@@ -895,6 +904,46 @@ class TggswKey:
         L.check(L.lib().fhe_tfhe_bootstrap(self.t.handle, self._h, ks_log_b, ks_d, pka, pkb, pv, pa, pb, poa, pob, batch, mem, st),
                 "fhe_tfhe_bootstrap")
         return out_a, out_b
+
+    def blind_rotate_tables(self, a_tilde, b_tilde, tables, table_of):
+        """bootstrapping.rs:84-96 with one test polynomial per ciphertext: tables [n_tables][n] encoded, table_of [batch] (uint32 /
+        torch int32); ciphertext i rotates tables[table_of[i]]."""
+        pa, _, mem, st = _buf(a_tilde)
+        pb, batch, _, _ = _buf(b_tilde)
+        pt, cnt, _, _ = _buf(tables)
+        pi, n_idx, mem_i = _buf32(table_of)
+        assert n_idx == batch and mem_i == mem
+        out_a, out_b = _like(a_tilde, (batch, self.n)), _like(a_tilde, (batch, self.n))
+        L.check(L.lib().fhe_tfhe_blind_rotate_tables(self.t.handle, self._h, pa, pb, pt, cnt // self.n, pi, _buf(out_a)[0], _buf(out_b)[0], batch, mem, st),
+                "fhe_tfhe_blind_rotate_tables")
+        return out_a, out_b
+
+    def bootstrap_tables(self, ks_log_b, ks_d, ksk_a, ksk_b, tables, table_of, lwe_a, lwe_b):
+        """bootstrapping.rs:78-82 in one call, ciphertext i through tables[table_of[i]] -> (a [batch][n_lwe], b [batch])."""
+        pka, _, mem, st = _buf(ksk_a)
+        pt, cnt, _, _ = _buf(tables)
+        pi, n_idx, mem_i = _buf32(table_of)
+        pb, batch, _, _ = _buf(lwe_b)
+        assert n_idx == batch and mem_i == mem
+        out_a, out_b = _like(lwe_a, (batch, self.count)), _like(lwe_a, (batch,))
+        L.check(L.lib().fhe_tfhe_bootstrap_tables(self.t.handle, self._h, ks_log_b, ks_d, pka, _buf(ksk_b)[0], pt, cnt // self.n, pi, _buf(lwe_a)[0], pb,
+                                                  _buf(out_a)[0], _buf(out_b)[0], batch, mem, st), "fhe_tfhe_bootstrap_tables")
+        return out_a, out_b
+
+
+def tlwe_lincomb(weights, cts, constant=0):
+    """scheme/tfhe/src/tlwe.rs:22-75 composed: constant + sum_j weights[j] * cts[j] over Z/2^64; cts: (a [batch][n], b [batch]) pairs;
+    the constant goes to b only.  -> (a, b)"""
+    k = len(cts)
+    bufs_a, bufs_b = [_buf(a) for a, _ in cts], [_buf(b) for _, b in cts]
+    batch = bufs_b[0][1]
+    n = bufs_a[0][1] // batch
+    pa, pb = (C.c_void_p * k)(*[x[0] for x in bufs_a]), (C.c_void_p * k)(*[x[0] for x in bufs_b])
+    w = (C.c_int32 * k)(*[int(x) for x in weights])
+    out_a, out_b = _like(cts[0][0], (batch, n)), _like(cts[0][0], (batch,))
+    L.check(L.lib().fhe_tlwe_lincomb(k, w, pa, pb, int(constant) % (1 << 64), _buf(out_a)[0], _buf(out_b)[0], n, batch, bufs_a[0][2], bufs_a[0][3]),
+            "fhe_tlwe_lincomb")
+    return out_a, out_b
 
 
 class TggswKeyK:
