@@ -883,6 +883,51 @@ int fhe_tfhe_circuit_run(const fhe_tfhe_circuit *c, const fhe_torus_ctx *t, cons
                          uint64_t *out_a       /* [n_outputs][batch][n_lwe] */, uint64_t *out_b       /* [n_outputs][batch] */,
                          size_t batch, fhe_mem mem, void *stream);
 
+/* ---- Many-LUT programmable bootstrap: several tables from ONE blind rotation (PBSmanyLUT, Chillotti-Ligier-Orfila-Tap 2021) over the
+ * reference's pieces, scheme/tfhe/src/bootstrapping.rs:78-128 and tglwe.rs:115-127.  v = log_funcs, 0 <= v <= 4, is the log2 of the number
+ * of functions one rotation serves: the ciphertext is mod-switched to multiples of 2^v, ONE test polynomial that interleaves the 2^v
+ * tables, P[c] = L_{c mod 2^v}[c - (c mod 2^v)] (L_i the ordinary table of function i: n / (2p) must be a multiple of 2^v), is rotated,
+ * and coefficients 0 .. 2^v - 1 are extracted: coefficient i holds f_i of the message.  NOT bit-identical to an ordinary bootstrap
+ * through L_i (the accumulator differs); the two agree at decode level.  The mod-switch drift grows by 2^v: with a binary key of
+ * dimension n_lwe the worst case is 2^v (n_lwe + 1) / 2 of 2n positions against a half-slot of n / (2p) -- the caller's condition. */
+/* bootstrapping.rs:99-104 `mod_switch` to multiples of 2^log_funcs: rounding_shr(v, 64 - log2(2 big_n) + log_funcs) << log_funcs, i.e.
+ * the reference's mod_switch for big_n >> log_funcs, shifted left.  log_funcs = 0: the bits of fhe_tfhe_mod_switch.  log_funcs > 4 or
+ * 2^log_funcs > big_n: FHE_ERR_INVALID. */
+int fhe_tfhe_mod_switch_many(const uint64_t *in, uint64_t *out, size_t count, size_t big_n, int log_funcs, fhe_mem mem, void *stream);
+/* tglwe.rs:115-127 `sample_extract(ct, i)` for i = 0 .. 2^log_funcs - 1 in one pass that reads every ciphertext once: ct_a, ct_b
+ * [batch][n] -> out_a [batch][2^log_funcs][n], out_b [batch][2^log_funcs]; row (c, i) has the bits of fhe_tglwe_sample_extract with
+ * index = i.  log_funcs > 4 or 2^log_funcs > n: FHE_ERR_INVALID; 2^log_funcs * batch beyond 31 bits: FHE_ERR_UNSUPPORTED. */
+int fhe_tglwe_sample_extract_many(const uint64_t *ct_a, const uint64_t *ct_b, size_t n, int log_funcs, uint64_t *out_a, uint64_t *out_b,
+                                  size_t batch, fhe_mem mem, void *stream);
+/* bootstrapping.rs:78-82 `Bootstrapping::bootstrap` with 2^log_funcs outputs per ciphertext: fhe_tfhe_mod_switch_many, 99-104 ->
+ * fhe_tfhe_blind_rotate_tables, 84-96, on the INTERLEAVED tables [n_tables][n], table_of [batch] -> fhe_tglwe_sample_extract with
+ * index = i, i < 2^log_funcs, tglwe.rs:115-127 -> fhe_tlwe_key_switch, tlwe.rs:144-153: out_a [batch][2^log_funcs][n_lwe], out_b [batch][2^log_funcs], bit-identical to
+ * those calls chained, in every key form (fft64: on the same device).  Everything else as fhe_tfhe_bootstrap_tables.  log_funcs > 4:
+ * FHE_ERR_INVALID; 2^log_funcs * batch beyond 31 bits: FHE_ERR_UNSUPPORTED. */
+int fhe_tfhe_bootstrap_many(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, int ks_log_b, int ks_d, const uint64_t *ksk_a,
+                            const uint64_t *ksk_b, const uint64_t *tables, size_t n_tables, const uint32_t *table_of, int log_funcs,
+                            const uint64_t *lwe_a, const uint64_t *lwe_b, uint64_t *out_a, uint64_t *out_b, size_t batch, fhe_mem mem,
+                            void *stream);
+/* A node of fhe_tfhe_circuit_create_many under either name: `many.log_funcs` is `node.pad`, the same 24 bytes. */
+typedef union {
+    fhe_tfhe_node node;
+    struct { uint32_t first_term, n_terms; uint64_t constant; uint32_t table; uint32_t log_funcs; } many;
+} fhe_tfhe_node_many;
+/* fhe_tfhe_circuit_create with many-LUT nodes (bootstrapping.rs:78-128, tglwe.rs:115-127): the node's fourth 32-bit field is log_funcs.
+ * Node g = ONE blind rotation of tables[table], an interleaved table of 2^log_funcs functions, and owns 2^log_funcs consecutive wires:
+ * the wire of (g, i) is n_inputs + sum_{h < g} 2^log_funcs_h + i; a node reads wires below its own first wire only.  Rejections: those
+ * of fhe_tfhe_circuit_create, and log_funcs > 4; the cap of 2^24 wires counts output wires.  A node is live when any of its outputs
+ * is; only live OUTPUTS get a place in the wire table, an extraction and a key-switch row.  With every log_funcs == 0 the circuit is
+ * that of fhe_tfhe_circuit_create.  _run, _info, _levels and _destroy take the handle; per level _run launches the front with a shift
+ * per node, the blind rotation (one job per NODE), one extraction pass over the live outputs and the key switch (one row per live
+ * OUTPUT); the workspace is sized inside.  Bit-identical to the live nodes one by one through fhe_tlwe_lincomb and
+ * fhe_tfhe_bootstrap_many. */
+int  fhe_tfhe_circuit_create_many(const fhe_tfhe_node *nodes, size_t n_nodes, const fhe_tfhe_term *terms, size_t n_terms, size_t n_inputs,
+                                  size_t n_tables, const uint32_t *outputs, size_t n_outputs, fhe_tfhe_circuit **out);
+/* bootstrapping.rs:78-128, tglwe.rs:115-127: live outputs (rows of the wire table) and those of the level that has most (the widest
+ * batch of key-switch rows is max_rows * batch); fhe_tfhe_circuit_info's max_width stays in nodes.  Each pointer may be NULL. */
+int  fhe_tfhe_circuit_info_many(const fhe_tfhe_circuit *c, size_t *n_live_outputs, size_t *max_rows);
+
 #ifdef __cplusplus
 }
 #endif

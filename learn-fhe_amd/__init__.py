@@ -14,7 +14,7 @@ from .circuit import Circuit  # noqa: F401
 from . import tfhe_circuit  # noqa: F401
 from .ring import (BootstrapKey, CkksDiagMatrix, CkksEncoder, CkksKey, CkksLinearPlan, CkksLinearTransform, CkksShard, Fhew, GadgetKey, NttContext, RnsContext, TggswKey, TorusContext,  # noqa: F401
                    ak_t, automorphism, bsgs_split, decompose, lwe_key_switch, lwe_lincomb, lwe_mod_switch, monomial_mul, rlwe_sample_extract, rq_add, rq_from_i64, rq_neg, rq_scalar_mul, rq_sub,
-                   tglwe_sample_extract, tlwe_key_switch, tlwe_lincomb, torus_decompose, tglwe_rotate,
+                   tglwe_sample_extract, tglwe_sample_extract_many, tlwe_key_switch, tlwe_lincomb, torus_decompose, tglwe_rotate,
                    power_up, rgsw_encrypt, rlwe_ksk_gen, rlwe_sk_encrypt, sample_dg, sample_torus, sample_uniform,
                    lwe_ksk_gen, lwe_sk_encrypt, rq_sum,
                    sample_binary, sample_tdg, sample_zo, tggsw_encrypt, tglwe_sk_encrypt, tlwe_ksk_gen, tlwe_sk_encrypt,

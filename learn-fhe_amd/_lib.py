@@ -131,6 +131,12 @@ def lib():
         L.fhe_tfhe_circuit_info.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
         L.fhe_tfhe_circuit_levels.argtypes = [vp, u32p]
         L.fhe_tfhe_circuit_run.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, sz, ci, vp]
+        # many-LUT bootstrap: several tables from one blind rotation (torus_api.hip, tfhe_circuit_api.hip)
+        L.fhe_tfhe_mod_switch_many.argtypes = [vp, vp, sz, sz, ci, ci, vp]
+        L.fhe_tglwe_sample_extract_many.argtypes = [vp, vp, sz, ci, vp, vp, sz, ci, vp]
+        L.fhe_tfhe_bootstrap_many.argtypes = [vp, vp, ci, ci, vp, vp, vp, sz, vp, ci, vp, vp, vp, vp, sz, ci, vp]
+        L.fhe_tfhe_circuit_create_many.argtypes = [vp, sz, vp, sz, sz, sz, u32p, sz, C.POINTER(vp)]
+        L.fhe_tfhe_circuit_info_many.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
         L.fhe_torus_ctx_create.argtypes = [ci, C.POINTER(vp)]
         L.fhe_torus_ctx_destroy.argtypes = [vp]
         L.fhe_torus_ctx_destroy.restype = None

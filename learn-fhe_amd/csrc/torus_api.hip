@@ -1,6 +1,7 @@
 // extern "C" entry points for SURVEY.md section 8(a) row T: the TFHE torus path, k = 1.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -11,6 +12,7 @@
 #include "dispatch.hpp"
 #include "lwe_kernels.hpp"
 #include "keygen_kernels.hpp"
+#include "tfhe_circuit_kernels.hpp"
 
 namespace {
 
@@ -694,6 +696,105 @@ int fhe_tfhe_bootstrap_tables(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, 
     if ((!table_of || !lwe_a || !lwe_b || !out_a || !out_b) && batch) return FHE_ERR_INVALID;
     if (batch == 0) return FHE_OK;
     return bootstrap_any(t, brk, ks_log_b, ks_d, ksk_a, ksk_b, tables, n_tables, table_of, lwe_a, lwe_b, out_a, out_b, batch, mem, stream);
+}
+
+// ---- many-LUT bootstrap: 2^log_funcs tables from one blind rotation (bootstrapping.rs:78-128 and tglwe.rs:115-127 composed) ----
+
+// bootstrapping.rs:99-104 `mod_switch` to multiples of 2^log_funcs: the reference's mod_switch for big_n >> log_funcs, shifted left
+int fhe_tfhe_mod_switch_many(const uint64_t *in, uint64_t *out, size_t count, size_t big_n, int log_funcs, fhe_mem mem, void *stream) {
+    PtrDeviceGuard pguard(in, mem);
+    if (!pguard.ok) return FHE_ERR_HIP;
+    if (!is_pow2(big_n) || log_funcs < 0 || log_funcs > (int)fhe::TFHE_MAX_LOG_FUNCS || (big_n >> log_funcs) == 0 || ((!in || !out) && count))
+        return FHE_ERR_INVALID;
+    if (count == 0) return FHE_OK;
+    const int bits = 64 - (ilog2(big_n) + 1);  // bits + log_funcs <= 63: 2^log_funcs <= big_n
+    hipStream_t st = (hipStream_t)stream;
+    Mirror mi(in, count, mem, true, st), mo(out, count, mem, false, st);
+    if (mi.rc | mo.rc) return FHE_ERR_HIP;
+    FHE_TRY(fhe::launch<fhe::torus_rounding_shr_many_kernel>(grid_for(count), 256, 0, st, (const u64 *)mi.d, mo.d, count, bits, log_funcs));
+    return mo.sync_out(st);
+}
+
+}  // extern "C"
+namespace {
+// tglwe.rs:115-127 for the dense list of indices 0 .. funcs - 1 on device buffers: acc [batch][n] -> ea [batch][funcs][n], eb [batch][funcs]
+int sample_extract_dense_dev(const u64 *acc_a, const u64 *acc_b, size_t n, unsigned funcs, u64 *ea, u64 *eb, size_t batch, hipStream_t st) {
+    constexpr unsigned WAVES = 4;
+    const unsigned grid = (unsigned)std::min<size_t>((batch + WAVES - 1) / WAVES, 8192);
+    const size_t lds = WAVES * n * sizeof(u64);
+    const bool wide = ((reinterpret_cast<uintptr_t>(acc_a) | reinterpret_cast<uintptr_t>(ea)) & 15) == 0;
+    if (wide)
+        return fhe::launch<fhe::tglwe_sample_extract_many_kernel<true>>(grid, 64 * WAVES, lds, st, acc_a, acc_b, (unsigned)n, 1u, (unsigned)batch,
+                                                                        (const unsigned *)nullptr, (const fhe::TfheExtract *)nullptr, 0u, funcs, size_t(1),
+                                                                        size_t(funcs), ea, eb);
+    return fhe::launch<fhe::tglwe_sample_extract_many_kernel<false>>(grid, 64 * WAVES, lds, st, acc_a, acc_b, (unsigned)n, 1u, (unsigned)batch,
+                                                                     (const unsigned *)nullptr, (const fhe::TfheExtract *)nullptr, 0u, funcs, size_t(1),
+                                                                     size_t(funcs), ea, eb);
+}
+}  // namespace
+extern "C" {
+
+// tglwe.rs:115-127 `sample_extract(ct, i)` for every i < 2^log_funcs, each ciphertext read once: out_a [batch][2^log_funcs][n]
+int fhe_tglwe_sample_extract_many(const uint64_t *ct_a, const uint64_t *ct_b, size_t n, int log_funcs, uint64_t *out_a, uint64_t *out_b, size_t batch,
+                                  fhe_mem mem, void *stream) {
+    PtrDeviceGuard pguard(ct_a, mem);
+    if (!pguard.ok) return FHE_ERR_HIP;
+    if (!is_pow2(n) || n < 2 || n > (1u << 30) || log_funcs < 0 || log_funcs > (int)fhe::TFHE_MAX_LOG_FUNCS || (n >> log_funcs) == 0) return FHE_ERR_INVALID;
+    if ((!ct_a || !ct_b || !out_a || !out_b) && batch) return FHE_ERR_INVALID;
+    if (batch == 0) return FHE_OK;
+    const size_t funcs = size_t(1) << log_funcs;
+    if (batch > 0x7fffffffull / funcs) return FHE_ERR_UNSUPPORTED;
+    if (4 * n * sizeof(u64) > 64 * 1024) return FHE_ERR_UNSUPPORTED;  // a row per wave in LDS: n <= 2048
+    hipStream_t st = (hipStream_t)stream;
+    Mirror ma(ct_a, n * batch, mem, true, st), mb(ct_b, n * batch, mem, true, st), moa(out_a, n * funcs * batch, mem, false, st),
+        mob(out_b, funcs * batch, mem, false, st);
+    if (ma.rc | mb.rc | moa.rc | mob.rc) return FHE_ERR_HIP;
+    FHE_TRY(sample_extract_dense_dev(ma.d, mb.d, n, (unsigned)funcs, moa.d, mob.d, batch, st));
+    int rc = moa.sync_out(st);
+    return rc != FHE_OK ? rc : mob.sync_out(st);
+}
+
+// bootstrapping.rs:78-82 with 2^log_funcs outputs per ciphertext: mod switch to multiples of 2^log_funcs (99-104), blind rotation of the
+// interleaved table of the ciphertext (84-96), sample_extract(i) for i < 2^log_funcs (tglwe.rs:115-127), key switch (tlwe.rs:144-153) of
+// the batch * 2^log_funcs rows.  Bit-identical to the separate calls.
+int fhe_tfhe_bootstrap_many(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, int ks_log_b, int ks_d, const uint64_t *ksk_a, const uint64_t *ksk_b,
+                            const uint64_t *tables, size_t n_tables, const uint32_t *table_of, int log_funcs, const uint64_t *lwe_a,
+                            const uint64_t *lwe_b, uint64_t *out_a, uint64_t *out_b, size_t batch, fhe_mem mem, void *stream) {
+    fhe::TDecomp P;
+    int rc = make_tdecomp(ks_log_b, ks_d, &P);
+    if (rc != FHE_OK) return rc;
+    if (!t || !brk || brk->t != t || !ksk_a || !ksk_b || !tables || n_tables == 0 || n_tables > MAX_TABLES) return FHE_ERR_INVALID;
+    if (log_funcs < 0 || log_funcs > (int)fhe::TFHE_MAX_LOG_FUNCS) return FHE_ERR_INVALID;
+    if ((!table_of || !lwe_a || !lwe_b || !out_a || !out_b) && batch) return FHE_ERR_INVALID;
+    if (brk->log_n < 8 || brk->log_n > 11) return FHE_ERR_UNSUPPORTED;  // N = 256 .. 2048
+    if (batch == 0) return FHE_OK;
+    const size_t funcs = size_t(1) << log_funcs;
+    if (batch > 0x7fffffffull / funcs) return FHE_ERR_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    DeviceGuard guard(t->device);
+    if (!guard.ok) return FHE_ERR_HIP;
+    const size_t n = size_t(1) << brk->log_n, n_lwe = brk->count, rows = n * ks_d, outs = batch * funcs;
+    TableOf tof(table_of, batch, n_tables, mem, st);
+    if (tof.rc != FHE_OK) return tof.rc;
+    Mirror mka(ksk_a, rows * n_lwe, mem, true, st), mkb(ksk_b, rows, mem, true, st), mv(tables, n_tables * n, mem, true, st),
+        ma(lwe_a, n_lwe * batch, mem, true, st), mb(lwe_b, batch, mem, true, st), moa(out_a, n_lwe * outs, mem, false, st),
+        mob(out_b, outs, mem, false, st);
+    if (mka.rc | mkb.rc | mv.rc | ma.rc | mb.rc | moa.rc | mob.rc) return FHE_ERR_HIP;
+    // acc.a | acc.b | extracted a (the [..][n] arrays first: each starts on a 16-byte boundary) | a~ | b~ | extracted b
+    StreamWs ws((2 * batch * n + outs * n + batch * n_lwe + batch + outs) * sizeof(u64), st);
+    if (ws.rc != FHE_OK) return ws.rc;
+    u64 *ra = ws.as<u64>(), *rb = ra + batch * n, *ea = rb + batch * n, *at = ea + outs * n, *bt = at + batch * n_lwe, *eb = bt + batch;
+    typedef uint64_t U;
+    rc = fhe_tfhe_mod_switch_many((const U *)ma.d, (U *)at, batch * n_lwe, n, log_funcs, FHE_MEM_DEVICE, stream);
+    if (rc == FHE_OK) rc = fhe_tfhe_mod_switch_many((const U *)mb.d, (U *)bt, batch, n, log_funcs, FHE_MEM_DEVICE, stream);
+    if (rc == FHE_OK) rc = blind_rotate_dev(t, brk, at, bt, mv.d, tof.d, ra, rb, batch, st);
+    if (rc == FHE_OK) rc = sample_extract_dense_dev(ra, rb, n, (unsigned)funcs, ea, eb, batch, st);
+    if (rc == FHE_OK)
+        rc = fhe_tlwe_key_switch(ks_log_b, ks_d, (const U *)mka.d, (const U *)mkb.d, (const U *)ea, (const U *)eb, n, n_lwe, (U *)moa.d, (U *)mob.d, outs,
+                                 FHE_MEM_DEVICE, stream);
+    if (rc == FHE_OK) rc = moa.sync_out(st);
+    if (rc == FHE_OK) rc = mob.sync_out(st);
+    return rc;
 }
 
 // scheme/tfhe/src/tlwe.rs:22-75 (Add, Sub, Neg and scalar Mul on `TlweCiphertext`, composed): out = constant + sum_{j < k} weight[j] * ct_j

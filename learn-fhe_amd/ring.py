@@ -846,6 +846,14 @@ class TorusContext:
         L.check(L.lib().fhe_tfhe_mod_switch(p, po, cnt, big_n, mem, st), "fhe_tfhe_mod_switch")
         return out
 
+    @staticmethod
+    def mod_switch_many(v, big_n, log_funcs):
+        """bootstrapping.rs:99-104 to multiples of 2^log_funcs: mod_switch for big_n >> log_funcs, shifted left by log_funcs."""
+        p, cnt, mem, st = _buf(v)
+        out = _like(v, tuple(v.shape))
+        L.check(L.lib().fhe_tfhe_mod_switch_many(p, _buf(out)[0], cnt, big_n, log_funcs, mem, st), "fhe_tfhe_mod_switch_many")
+        return out
+
 
 class TggswKey:
     """Prepared TGGSW ciphertexts, k = 1 (scheme/tfhe/src/tggsw.rs:44-88)."""
@@ -928,6 +936,19 @@ class TggswKey:
         out_a, out_b = _like(lwe_a, (batch, self.count)), _like(lwe_a, (batch,))
         L.check(L.lib().fhe_tfhe_bootstrap_tables(self.t.handle, self._h, ks_log_b, ks_d, pka, _buf(ksk_b)[0], pt, cnt // self.n, pi, _buf(lwe_a)[0], pb,
                                                   _buf(out_a)[0], _buf(out_b)[0], batch, mem, st), "fhe_tfhe_bootstrap_tables")
+        return out_a, out_b
+
+    def bootstrap_many(self, ks_log_b, ks_d, ksk_a, ksk_b, tables, table_of, log_funcs, lwe_a, lwe_b):
+        """The many-LUT bootstrap: ONE blind rotation per ciphertext through the interleaved table tables[table_of[i]] (tfhe_circuit.lut_many)
+        serves 2^log_funcs functions -> (a [batch][2^log_funcs][n_lwe], b [batch][2^log_funcs])."""
+        pka, _, mem, st = _buf(ksk_a)
+        pt, cnt, _, _ = _buf(tables)
+        pi, n_idx, mem_i = _buf32(table_of)
+        pb, batch, _, _ = _buf(lwe_b)
+        assert n_idx == batch and mem_i == mem
+        out_a, out_b = _like(lwe_a, (batch, 1 << log_funcs, self.count)), _like(lwe_a, (batch, 1 << log_funcs))
+        L.check(L.lib().fhe_tfhe_bootstrap_many(self.t.handle, self._h, ks_log_b, ks_d, pka, _buf(ksk_b)[0], pt, cnt // self.n, pi, log_funcs,
+                                                _buf(lwe_a)[0], pb, _buf(out_a)[0], _buf(out_b)[0], batch, mem, st), "fhe_tfhe_bootstrap_many")
         return out_a, out_b
 
 
@@ -1040,6 +1061,16 @@ def tglwe_sample_extract(ct_a, ct_b, n, index):
     poa, _, _, _ = _buf(out_a)
     pob, _, _, _ = _buf(out_b)
     L.check(L.lib().fhe_tglwe_sample_extract(pa, pb, n, index, poa, pob, batch, mem, st), "fhe_tglwe_sample_extract")
+    return out_a, out_b
+
+
+def tglwe_sample_extract_many(ct_a, ct_b, n, log_funcs):
+    """tglwe.rs:115-127 for every index below 2^log_funcs, each ciphertext read once -> (a [batch][2^log_funcs][n], b [batch][2^log_funcs])"""
+    pa, cnt, mem, st = _buf(ct_a)
+    batch = cnt // n
+    out_a, out_b = _like(ct_a, (batch, 1 << log_funcs, n)), _like(ct_a, (batch, 1 << log_funcs))
+    L.check(L.lib().fhe_tglwe_sample_extract_many(pa, _buf(ct_b)[0], n, log_funcs, _buf(out_a)[0], _buf(out_b)[0], batch, mem, st),
+            "fhe_tglwe_sample_extract_many")
     return out_a, out_b
 
 

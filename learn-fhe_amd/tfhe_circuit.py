@@ -10,6 +10,11 @@ the whole batch at a time, every job through the table of its node.
 Messages live in Z_p, p = 2^log_p, under `padding` = 1 extra bit: a phase is a value x of Z_2p times 2^(64 - log_p - 1).  A node computes
 x = constant + sum weight * wire over Z_2p and bootstraps it: table[x] for x < p and, the test polynomial being negacyclic,
 -table[x - p] when the sum lands in the padding half.
+
+A many-LUT node (Builder.node_many, radix_add(..., many=True)) serves 2^v functions of the same sum from ONE blind rotation
+(PBSmanyLUT): the sum is mod-switched to multiples of 2^v, the node's table interleaves the functions' tables (lut_many) and outputs
+0 .. 2^v - 1 are extracted.  The mod-switch drift grows by 2^v: with a binary key of dimension n_lwe the worst case is
+2^v (n_lwe + 1) / 2 of 2n positions and must stay below the half-slot n / 2p -- the caller's condition.
 """
 from __future__ import annotations
 
@@ -48,15 +53,28 @@ def lut(f, log_p, padding, n):
     return np.array([(x << log_delta) % (1 << 64) for x in vals], dtype=np.uint64)
 
 
-class Wire:
-    """A reference to a wire of one Builder: an input or a node output."""
-    __slots__ = ("builder", "is_input", "index")
+def lut_many(fs, log_p, padding, n):
+    """The test polynomial of a many-LUT bootstrap (PBSmanyLUT): 2^v = len(fs) functions served by ONE blind rotation.  With L_i =
+    lut(fs[i], ...), coefficient c is L_{c mod 2^v}[c - (c mod 2^v)]: after a rotation by a multiple of 2^v (mod_switch_many), coefficient i
+    holds fs[i] of the message, negated on the torus through the negacyclic wrap exactly as lut does.  n / 2p must be a multiple of 2^v.
+    One function: lut itself.  -> [n] uint64"""
+    funcs = len(fs)
+    assert funcs >= 1 and funcs & (funcs - 1) == 0 and funcs <= 16, "1, 2, 4, 8 or 16 functions"
+    assert (n >> (log_p + 1)) % funcs == 0 and n >> (log_p + 1), "n / 2p must be a multiple of the number of functions"
+    luts = [lut(f, log_p, padding, n) for f in fs]
+    c = np.arange(n)
+    return np.stack(luts)[c % funcs, c - c % funcs]
 
-    def __init__(self, builder, is_input, index):
-        self.builder, self.is_input, self.index = builder, is_input, index
+
+class Wire:
+    """A reference to a wire of one Builder: an input or output `out` of a node (0 unless the node is a many-LUT node)."""
+    __slots__ = ("builder", "is_input", "index", "out")
+
+    def __init__(self, builder, is_input, index, out=0):
+        self.builder, self.is_input, self.index, self.out = builder, is_input, index, out
 
     def __repr__(self):
-        return "%s%d" % ("in" if self.is_input else "n", self.index)
+        return "%s%d%s" % ("in" if self.is_input else "n", self.index, ".%d" % self.out if self.out else "")
 
 
 class _Term(C.Structure):  # fhe_tfhe_term
@@ -98,8 +116,38 @@ class Builder:
         self.nodes.append((terms, int(table), int(constant)))
         return Wire(self, False, len(self.nodes) - 1)
 
-    def _ref(self, w):
-        return w.index if w.is_input else self.n_inputs + w.index
+    def table_many(self, fs):
+        """registers the functions of one many-LUT node as ONE table (a tuple; the same function objects in the same order: once)"""
+        fs = tuple(fs)
+        for i, g in enumerate(self.tables):
+            if isinstance(g, tuple) and len(g) == len(fs) and all(a is b for a, b in zip(g, fs)):
+                return i
+        self.tables.append(fs)
+        return len(self.tables) - 1
+
+    def node_many(self, terms, fs, constant=0):
+        """ONE bootstrap that yields fs[0](x), fs[1](x), ... of x = constant + sum weight * wire: a many-LUT node (len(fs) = 2^v <= 16
+        functions, one interleaved table, one blind rotation).  The mod-switch drift is 2^v times that of node().  -> list of wires"""
+        fs = tuple(fs)
+        assert len(fs) in (1, 2, 4, 8, 16)
+        w0 = self.node(terms, self.table_many(fs), constant)
+        return [Wire(self, False, w0.index, i) for i in range(len(fs))]
+
+    def log_funcs(self, g):
+        """v of node g: 0 for a node(), log2 of the number of functions of a node_many()"""
+        f = self.tables[self.nodes[g][1]]
+        return len(f).bit_length() - 1 if isinstance(f, tuple) else 0
+
+    def first_wires(self):
+        """[n_nodes + 1]: the netlist wire of every node's output 0 (node g owns 2^v_g consecutive wires); last = number of wires"""
+        out, w = [], self.n_inputs
+        for g in range(len(self.nodes)):
+            out.append(w)
+            w += 1 << self.log_funcs(g)
+        return out + [w]
+
+    def _ref(self, w, first=None):
+        return w.index if w.is_input else (first or self.first_wires())[w.index] + w.out
 
     def compile(self, outputs, log_p, padding, n):
         return CompiledTfheCircuit(self, list(outputs), log_p, padding, n)
@@ -107,24 +155,27 @@ class Builder:
     # ---- evaluation without the library -------------------------------------------------------------------------------------
     def evaluate(self, inputs, log_p, padding, outputs=None):
         """The plain-value model: inputs are integers or numpy integer arrays (one case per element), read mod 2p.  Every wire carries
-        an element of Z_2p (message + padding bit); a node yields table[x] for a sum x < p and (-table[x - p]) mod 2p for x >= p.
-        -> the values of `outputs` (default: every node), elements of Z_2p."""
+        an element of Z_2p (message + padding bit); a node yields table[x] for a sum x < p and (-table[x - p]) mod 2p for x >= p; output
+        i of a many-LUT node yields the same through the table of its function i.
+        -> the values of `outputs` (default: every output of every node, in wire order), elements of Z_2p."""
         assert padding == 1 and len(inputs) == self.n_inputs
         p = 1 << log_p
         ins = [np.asarray(v, dtype=np.int64) % (2 * p) for v in inputs]
-        tabs = [np.array(table_values(f, log_p), dtype=np.int64) for f in self.tables]
+        tabs = [[np.array(table_values(g, log_p), dtype=np.int64) for g in (f if isinstance(f, tuple) else (f,))] for f in self.tables]
         vals = []
 
         def get(w):
-            return ins[w.index] if w.is_input else vals[w.index]
+            return ins[w.index] if w.is_input else vals[w.index][w.out]
 
         for terms, table, constant in self.nodes:
             x = np.int64(constant)
             for w, k in terms:
                 x = x + k * get(w)
             x = x % (2 * p)
-            vals.append(np.where(x < p, tabs[table][x % p], (-tabs[table][x % p]) % (2 * p)))
-        return [get(w) for w in (outputs if outputs is not None else [Wire(self, False, i) for i in range(len(self.nodes))])]
+            vals.append([np.where(x < p, tab[x % p], (-tab[x % p]) % (2 * p)) for tab in tabs[table]])
+        if outputs is None:
+            outputs = [Wire(self, False, g, i) for g in range(len(self.nodes)) for i in range(1 << self.log_funcs(g))]
+        return [get(w) for w in outputs]
 
 
 class CompiledTfheCircuit:
@@ -133,23 +184,29 @@ class CompiledTfheCircuit:
     def __init__(self, builder: Builder, outputs, log_p, padding, n):
         self.builder, self.outputs, self.log_p, self.padding, self.n = builder, outputs, log_p, padding, n
         log_delta = 64 - (log_p + padding)
-        flat = [(builder._ref(w), k) for terms, _, _ in builder.nodes for w, k in terms]
+        fw = builder.first_wires()
+        flat = [(builder._ref(w, fw), k) for terms, _, _ in builder.nodes for w, k in terms]
         tarr = (_Term * max(1, len(flat)))()
         for i, (w, k) in enumerate(flat):
             tarr[i].wire, tarr[i].weight = w, k
         narr = (_Node * max(1, len(builder.nodes)))()
         first = 0
+        self.log_funcs = [builder.log_funcs(g) for g in range(len(builder.nodes))]
         for i, (terms, table, constant) in enumerate(builder.nodes):
             narr[i].first_term, narr[i].n_terms, narr[i].table = first, len(terms), table
             narr[i].constant = ((constant % (2 << log_p)) << log_delta) % (1 << 64)
+            narr[i].pad = self.log_funcs[i]            # fhe_tfhe_node_many's log_funcs
             first += len(terms)
-        outs = [builder._ref(w) for w in outputs]
+        outs = [builder._ref(w, fw) for w in outputs]
         oarr = (C.c_uint32 * max(1, len(outs)))(*outs)
         self.n_inputs, self.n_nodes, self.n_outputs, self.n_tables = builder.n_inputs, len(builder.nodes), len(outs), len(builder.tables)
-        self.tables = np.stack([lut(f, log_p, padding, n) for f in builder.tables]) if builder.tables else np.zeros((0, n), dtype=np.uint64)
+        self.tables = (np.stack([lut_many(f, log_p, padding, n) if isinstance(f, tuple) else lut(f, log_p, padding, n) for f in builder.tables])
+                       if builder.tables else np.zeros((0, n), dtype=np.uint64))
         self._h = C.c_void_p()
-        L.check(L.lib().fhe_tfhe_circuit_create(narr, len(builder.nodes), tarr, len(flat), builder.n_inputs, self.n_tables, oarr, len(outs),
-                                                C.byref(self._h)), "fhe_tfhe_circuit_create")
+        self.many = any(self.log_funcs)                # a many-LUT node anywhere: the create that reads log_funcs
+        create = L.lib().fhe_tfhe_circuit_create_many if self.many else L.lib().fhe_tfhe_circuit_create
+        L.check(create(narr, len(builder.nodes), tarr, len(flat), builder.n_inputs, self.n_tables, oarr, len(outs), C.byref(self._h)),
+                "fhe_tfhe_circuit_create_many" if self.many else "fhe_tfhe_circuit_create")
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -164,6 +221,13 @@ class CompiledTfheCircuit:
         lv, live, width = C.c_size_t(), C.c_size_t(), C.c_size_t()
         L.check(L.lib().fhe_tfhe_circuit_info(self._h, C.byref(lv), C.byref(live), C.byref(width)), "fhe_tfhe_circuit_info")
         return {"levels": lv.value, "live_nodes": live.value, "max_width": width.value}
+
+    def info_many(self):
+        """fhe_tfhe_circuit_info_many: live outputs (rows of the wire table) and those of the level that has most (key-switch rows per
+        ciphertext of the batch); equal to info()'s live_nodes and max_width without many-LUT nodes"""
+        live, rows = C.c_size_t(), C.c_size_t()
+        L.check(L.lib().fhe_tfhe_circuit_info_many(self._h, C.byref(live), C.byref(rows)), "fhe_tfhe_circuit_info_many")
+        return {"live_outputs": live.value, "max_rows": rows.value}
 
     def levels(self):
         """level of every node of the netlist, 0 = dropped"""
@@ -189,11 +253,19 @@ class CompiledTfheCircuit:
         vals = []
 
         def get(w):
-            return (in_a[w.index], in_b[w.index]) if w.is_input else vals[w.index]
+            return (in_a[w.index], in_b[w.index]) if w.is_input else vals[w.index][w.out]
 
-        for terms, table, constant in b.nodes:
+        for g, (terms, table, constant) in enumerate(b.nodes):
             s = tlwe_lincomb([k for _, k in terms], [get(w) for w, _ in terms], ((constant % (2 << self.log_p)) << log_delta) % (1 << 64))
-            vals.append(key.bootstrap(ks_log_b, ks_d, ksk_a, ksk_b, tables[table], s[0], s[1]))
+            if not self.log_funcs[g]:
+                vals.append([key.bootstrap(ks_log_b, ks_d, ksk_a, ksk_b, tables[table], s[0], s[1])])
+                continue
+            # a many-LUT node: one call, every ciphertext through the node's interleaved table
+            oa, ob = key.bootstrap_many(ks_log_b, ks_d, ksk_a, ksk_b, tables, _table_of(table, batch, in_a), self.log_funcs[g], s[0], s[1])
+            if isinstance(oa, np.ndarray):
+                vals.append([(np.ascontiguousarray(oa[:, i]), np.ascontiguousarray(ob[:, i])) for i in range(1 << self.log_funcs[g])])
+            else:
+                vals.append([(oa[:, i].contiguous(), ob[:, i].contiguous()) for i in range(1 << self.log_funcs[g])])
         outs = [get(w) for w in self.outputs]
         if isinstance(in_a, np.ndarray):
             return np.stack([o[0] for o in outs]), np.stack([o[1] for o in outs])
@@ -206,6 +278,14 @@ def _same_memory(tables, like):
         return tables
     import torch
     return torch.from_numpy(np.ascontiguousarray(tables).view(np.int64)).to(like.device)
+
+
+def _table_of(table, batch, like):
+    """[batch] copies of one table index in the memory of `like`"""
+    if isinstance(like, np.ndarray):
+        return np.full(batch, table, dtype=np.uint32)
+    import torch
+    return torch.full((batch,), table, dtype=torch.int32, device=like.device)
 
 
 def run_circuit(handle, n_inputs, n_outputs, tables, key, ks_log_b, ks_d, ksk_a, ksk_b, inputs, batch):
@@ -226,18 +306,25 @@ def run_circuit(handle, n_inputs, n_outputs, tables, key, ks_log_b, ks_d, ksk_a,
 
 # ---- arithmetic in the style of bootstrapping.rs:141-165: one table per function, message + carry blocks --------------------------
 
-def radix_add(blocks, msg_bits, carry_bits, b=None, x=None, y=None):
+def radix_add(blocks, msg_bits, carry_bits, b=None, x=None, y=None, many=False):
     """x + y over `blocks` blocks of msg_bits message bits under carry_bits of head room (log_p = msg_bits + carry_bits), least
     significant block first: per block one message table and one carry table of x_i + y_i + carry_{i-1}.  The last block's carry is
     emitted like the others (no output names it: create drops it).  b: the builder to extend (default: a new one); x, y: lists of
-    wires (default: fresh inputs, x first).  -> (builder, x, y, message wires)"""
+    wires (default: fresh inputs, x first).  many: ONE many-LUT node (message, carry) per block instead of two nodes -- `blocks` blind
+    rotations instead of 2 blocks - 1, at twice the mod-switch drift (node_many).  -> (builder, x, y, message wires)"""
     mask = (1 << msg_bits) - 1
     assert 2 * mask + 1 < (1 << (msg_bits + carry_bits)), "x_i + y_i + carry must stay below p"
     b = Builder() if b is None else b
     x = [b.input() for _ in range(blocks)] if x is None else x
     y = [b.input() for _ in range(blocks)] if y is None else y
-    t_msg, t_carry = b.table(_fn("msg%d" % msg_bits, lambda v: v & mask)), b.table(_fn("carry%d" % msg_bits, lambda v: v >> msg_bits))
+    f_msg, f_carry = _fn("msg%d" % msg_bits, lambda v: v & mask), _fn("carry%d" % msg_bits, lambda v: v >> msg_bits)
     outs, carry = [], None
+    if many:
+        for i in range(blocks):
+            msg, carry = b.node_many([(x[i], 1), (y[i], 1)] + ([(carry, 1)] if carry is not None else []), (f_msg, f_carry))
+            outs.append(msg)
+        return b, x, y, outs
+    t_msg, t_carry = b.table(f_msg), b.table(f_carry)
     for i in range(blocks):
         terms = [(x[i], 1), (y[i], 1)] + ([(carry, 1)] if carry is not None else [])
         outs.append(b.node(terms, t_msg))

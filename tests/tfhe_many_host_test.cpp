@@ -1,0 +1,329 @@
+// Stand-alone host program over learn-fhe_amd/csrc/tfhe_circuit.hpp (no HIP): tfhe_circuit_compile_many, the netlist compiler of
+// fhe_tfhe_circuit_create_many.  With every log_funcs == 0 its plan equals tfhe_circuit_compile's field by field (the hand-made netlist,
+// the radix adder, random netlists); with mixed log_funcs in {0, 1, 2} the wire numbering, the liveness per output, the levels through
+// many-LUT nodes, the slot order and the extraction descriptors against a restatement; the rejected cases.
+// Built with -fsanitize=address,undefined.
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <functional>
+#include <vector>
+
+#include "../learn-fhe_amd/csrc/tfhe_circuit.hpp"
+
+static uint64_t state = 0x243f6a8885a308d3ull;
+static uint32_t rnd(uint32_t m) {
+    state ^= state << 13; state ^= state >> 7; state ^= state << 17;
+    return (uint32_t)((state >> 11) % m);
+}
+
+#define REQUIRE(cond)                                                          \
+    do {                                                                       \
+        if (!(cond)) { std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); return 1; } \
+    } while (0)
+
+static bool same_nodes(const std::vector<fhe_tfhe_node> &a, const std::vector<fhe_tfhe_node> &b) {
+    if (a.size() != b.size()) return false;
+    for (size_t i = 0; i < a.size(); ++i)
+        if (a[i].first_term != b[i].first_term || a[i].n_terms != b[i].n_terms || a[i].constant != b[i].constant || a[i].table != b[i].table ||
+            a[i].pad != b[i].pad)
+            return false;
+    return true;
+}
+static bool same_terms(const std::vector<fhe_tfhe_term> &a, const std::vector<fhe_tfhe_term> &b) {
+    if (a.size() != b.size()) return false;
+    for (size_t i = 0; i < a.size(); ++i)
+        if (a[i].wire != b[i].wire || a[i].weight != b[i].weight) return false;
+    return true;
+}
+static bool same_extracts(const std::vector<fhe::TfheExtract> &a, const std::vector<fhe::TfheExtract> &b) {
+    if (a.size() != b.size()) return false;
+    for (size_t i = 0; i < a.size(); ++i)
+        if (a[i].node != b[i].node || a[i].index != b[i].index) return false;
+    return true;
+}
+
+// every field of the two plans
+static int same_plan(const fhe::TfheCircuitPlan &A, const fhe::TfheCircuitPlan &B) {
+    REQUIRE(A.n_inputs == B.n_inputs && A.n_nodes == B.n_nodes && A.n_outputs == B.n_outputs && A.n_tables == B.n_tables);
+    REQUIRE(A.n_levels == B.n_levels && A.n_live == B.n_live && A.max_width == B.max_width);
+    REQUIRE(A.level_of_node == B.level_of_node && A.level_start == B.level_start && A.outputs == B.outputs);
+    REQUIRE(same_nodes(A.nodes, B.nodes) && same_terms(A.terms, B.terms));
+    REQUIRE(A.many == B.many && A.n_slots == B.n_slots && A.max_rows == B.max_rows && A.out_start == B.out_start);
+    REQUIRE(same_extracts(A.extracts, B.extracts));
+    return 0;
+}
+
+struct Netlist {
+    std::vector<fhe_tfhe_node> nodes;
+    std::vector<fhe_tfhe_term> terms;
+    std::vector<uint32_t> outputs;
+    size_t n_inputs = 0, n_tables = 0;
+};
+
+static int compile_both_and_compare(const Netlist &N, fhe::TfheCircuitPlan *plan) {
+    fhe::TfheCircuitPlan A, B;
+    REQUIRE(fhe::tfhe_circuit_compile(N.nodes.data(), N.nodes.size(), N.terms.data(), N.terms.size(), N.n_inputs, N.n_tables, N.outputs.data(),
+                                      N.outputs.size(), &A) == FHE_OK);
+    REQUIRE(fhe::tfhe_circuit_compile_many(N.nodes.data(), N.nodes.size(), N.terms.data(), N.terms.size(), N.n_inputs, N.n_tables, N.outputs.data(),
+                                           N.outputs.size(), &B) == FHE_OK);
+    if (same_plan(A, B)) return 1;
+    // what a plan without many-LUT nodes says about its outputs: one per live node
+    REQUIRE(!B.many && B.n_slots == B.n_live && B.max_rows == B.max_width && B.out_start.size() == B.n_live + 1);
+    for (size_t i = 0; i < B.n_live; ++i) REQUIRE(B.out_start[i] == i && B.extracts[i].node == i && B.extracts[i].index == 0);
+    if (plan) *plan = B;
+    return 0;
+}
+
+static void add_node(Netlist &N, std::initializer_list<fhe_tfhe_term> terms, uint32_t table, uint64_t constant, uint32_t log_funcs) {
+    fhe_tfhe_node nd{};
+    nd.first_term = (uint32_t)N.terms.size();
+    nd.n_terms = (uint32_t)terms.size();
+    nd.constant = constant;
+    nd.table = table;
+    nd.pad = log_funcs;
+    N.terms.insert(N.terms.end(), terms.begin(), terms.end());
+    N.nodes.push_back(nd);
+}
+
+// the hand-made netlist of tests/test_tfhe_circuit_gpu.py and the two-table radix adder (4 blocks), every log_funcs == 0
+static int nu0_equals_the_existing_compiler() {
+    Netlist H;
+    H.n_inputs = 3; H.n_tables = 3;
+    add_node(H, {{0, 1}, {1, 1}}, 0, 0, 0);            // wire 3
+    add_node(H, {{1, 4}, {2, -1}}, 1, 5ull << 59, 0);  // 4
+    add_node(H, {{3, 1}, {4, -1}}, 2, 0, 0);           // 5
+    add_node(H, {{3, 1}, {2, 4}}, 0, 31ull << 59, 0);  // 6
+    add_node(H, {{5, 1}, {6, 1}, {0, -1}}, 1, 0, 0);   // 7
+    add_node(H, {{4, 1}, {6, 1}}, 2, 0, 0);            // 8: dead
+    H.outputs = {7, 1, 7, 5};
+    fhe::TfheCircuitPlan P;
+    if (compile_both_and_compare(H, &P)) return 1;
+    REQUIRE(P.n_levels == 3 && P.n_live == 5 && P.max_width == 2);
+    REQUIRE((P.level_of_node == std::vector<uint32_t>{1, 1, 2, 2, 3, 0}));
+    Netlist R;
+    R.n_inputs = 8; R.n_tables = 2;
+    uint32_t carry = 0;
+    for (uint32_t i = 0; i < 4; ++i) {
+        for (uint32_t which = 0; which < 2; ++which) {
+            if (i) add_node(R, {{i, 1}, {4 + i, 1}, {carry, 1}}, which, 0, 0);
+            else add_node(R, {{i, 1}, {4 + i, 1}}, which, 0, 0);
+        }
+        R.outputs.push_back(8 + 2 * i);
+        carry = 8 + 2 * i + 1;
+    }
+    if (compile_both_and_compare(R, &P)) return 1;
+    REQUIRE(P.n_levels == 4 && P.n_live == 7 && P.max_width == 2);
+    REQUIRE((P.level_of_node == std::vector<uint32_t>{1, 1, 2, 2, 3, 3, 4, 0}));
+    // random netlists with a pad of 0
+    for (int it = 0; it < 200; ++it) {
+        Netlist N;
+        N.n_inputs = 1 + rnd(6); N.n_tables = 1 + rnd(4);
+        const size_t n_nodes = rnd(50);
+        for (size_t g = 0; g < n_nodes; ++g) {
+            const uint32_t below = (uint32_t)(N.n_inputs + g);
+            fhe_tfhe_node nd{};
+            nd.first_term = (uint32_t)N.terms.size();
+            nd.n_terms = 1 + rnd(4);
+            nd.constant = ((uint64_t)rnd(1u << 31) << 33) | rnd(1u << 31);
+            nd.table = rnd((uint32_t)N.n_tables);
+            for (uint32_t k = 0; k < nd.n_terms; ++k) N.terms.push_back(fhe_tfhe_term{rnd(4) ? below - 1 - rnd(below < 5 ? below : 5) : rnd(below), (int32_t)rnd(4) + 1});
+            N.nodes.push_back(nd);
+        }
+        for (uint32_t o = 1 + rnd(4); o--;) N.outputs.push_back(rnd((uint32_t)(N.n_inputs + n_nodes)));
+        if (compile_both_and_compare(N, nullptr)) return 1;
+    }
+    return 0;
+}
+
+// random netlists with log_funcs in {0, 1, 2} against a restatement
+static int mixed(size_t n_inputs, size_t n_nodes, size_t n_outputs, size_t n_tables) {
+    std::vector<fhe_tfhe_node> nodes(n_nodes);
+    std::vector<fhe_tfhe_term> terms;
+    std::vector<uint32_t> first_wire(n_nodes + 1);
+    uint32_t n_wires = (uint32_t)n_inputs;
+    for (size_t g = 0; g < n_nodes; ++g) {
+        first_wire[g] = n_wires;
+        nodes[g] = fhe_tfhe_node{};
+        nodes[g].first_term = (uint32_t)terms.size();
+        nodes[g].n_terms = 1 + rnd(rnd(4) ? 3 : 16);
+        nodes[g].constant = ((uint64_t)rnd(1u << 31) << 33) | rnd(1u << 31);
+        nodes[g].table = rnd((uint32_t)n_tables);
+        nodes[g].pad = rnd(3);
+        for (uint32_t k = 0; k < nodes[g].n_terms; ++k) {
+            const uint32_t w = rnd(4) ? n_wires - 1 - rnd(n_wires < 9 ? n_wires : 9) : rnd(n_wires);
+            terms.push_back(fhe_tfhe_term{w, rnd(2) ? -1 : (int32_t)rnd(7) + 1});
+        }
+        if (rnd(5) == 0) terms.push_back(fhe_tfhe_term{0xffffffffu, 0});  // unused terms may hold anything
+        n_wires += 1u << nodes[g].pad;
+    }
+    first_wire[n_nodes] = n_wires;
+    std::vector<uint32_t> outputs(n_outputs);
+    for (auto &o : outputs) o = rnd(n_wires);
+    fhe::TfheCircuitPlan P;
+    REQUIRE(fhe::tfhe_circuit_compile_many(nodes.data(), n_nodes, terms.data(), terms.size(), n_inputs, n_tables, outputs.data(), n_outputs, &P) == FHE_OK);
+    // restatement: the node of a wire by search; a wire is live when an output or a live node's term names it (recursion)
+    auto node_of = [&](uint32_t w) { return (size_t)(std::upper_bound(first_wire.begin(), first_wire.end(), w) - first_wire.begin()) - 1; };
+    std::vector<int> live(n_wires, 0), node_live(n_nodes, 0), level(n_nodes, -1);
+    std::function<void(uint32_t)> mark = [&](uint32_t w) {
+        if (live[w]) return;
+        live[w] = 1;
+        if (w < n_inputs) return;
+        const size_t g = node_of(w);
+        if (node_live[g]) return;
+        node_live[g] = 1;
+        for (uint32_t k = 0; k < nodes[g].n_terms; ++k) mark(terms[nodes[g].first_term + k].wire);
+    };
+    for (uint32_t o : outputs) mark(o);
+    std::function<int(uint32_t)> lev = [&](uint32_t w) {
+        if (w < n_inputs) return 0;
+        const size_t g = node_of(w);
+        if (level[g] >= 0) return level[g];
+        int l = 0;
+        for (uint32_t k = 0; k < nodes[g].n_terms; ++k) l = std::max(l, lev(terms[nodes[g].first_term + k].wire));
+        return level[g] = l + 1;
+    };
+    size_t n_live = 0, n_levels = 0, any_many = 0;
+    std::vector<size_t> width, rows;
+    for (size_t g = 0; g < n_nodes; ++g) {
+        any_many |= nodes[g].pad != 0;
+        const uint32_t expect = node_live[g] ? (uint32_t)lev(first_wire[g]) : 0u;
+        REQUIRE(P.level_of_node[g] == expect);
+        if (!expect) continue;
+        ++n_live;
+        n_levels = std::max(n_levels, (size_t)expect);
+        if (width.size() < expect) { width.resize(expect, 0); rows.resize(expect, 0); }
+        ++width[expect - 1];
+        for (uint32_t w = first_wire[g]; w < first_wire[g + 1]; ++w) rows[expect - 1] += live[w];
+    }
+    REQUIRE(P.many == (any_many != 0));
+    REQUIRE(P.n_live == n_live && P.n_levels == n_levels && P.nodes.size() == n_live && P.level_start.size() == n_levels + 1);
+    REQUIRE(P.max_width == (width.empty() ? 0 : *std::max_element(width.begin(), width.end())));
+    REQUIRE(P.max_rows == (rows.empty() ? 0 : *std::max_element(rows.begin(), rows.end())));
+    REQUIRE(P.out_start.size() == n_live + 1 && P.extracts.size() == P.n_slots && P.out_start[n_live] == P.n_slots);
+    // slots: level by level, netlist order within a level, a node's live outputs by index; a dead output has none
+    std::vector<uint32_t> slot_of(n_wires, 0xffffffffu);
+    for (size_t w = 0; w < n_inputs; ++w) slot_of[w] = (uint32_t)w;
+    uint32_t s = 0, i = 0;
+    for (size_t l = 0; l < n_levels; ++l) {
+        REQUIRE(P.level_start[l] == i && P.level_start[l + 1] - P.level_start[l] == width[l]);
+        const uint32_t s_level = s;
+        for (size_t g = 0; g < n_nodes; ++g) {
+            if (P.level_of_node[g] != l + 1) continue;
+            REQUIRE(P.out_start[i] == s);
+            for (uint32_t w = first_wire[g]; w < first_wire[g + 1]; ++w) {
+                if (!live[w]) continue;
+                REQUIRE(s < P.n_slots && P.extracts[s].node == i && P.extracts[s].index == w - first_wire[g]);
+                slot_of[w] = (uint32_t)(n_inputs + s++);
+            }
+            REQUIRE(s > P.out_start[i]);  // a live node has a live output
+            const fhe_tfhe_node &nd = P.nodes[i];
+            REQUIRE(nd.n_terms == nodes[g].n_terms && nd.constant == nodes[g].constant && nd.table == nodes[g].table && nd.pad == nodes[g].pad);
+            REQUIRE((size_t)nd.first_term + nd.n_terms <= P.terms.size());
+            for (uint32_t k = 0; k < nd.n_terms; ++k) {
+                const fhe_tfhe_term &src = terms[nodes[g].first_term + k], &dst = P.terms[nd.first_term + k];
+                REQUIRE(dst.wire == slot_of[src.wire] && dst.weight == src.weight);
+                REQUIRE(dst.wire < n_inputs + s_level);  // produced by an earlier level: it has a slot below this level's
+            }
+            ++i;
+        }
+        REQUIRE(s - s_level == rows[l]);
+    }
+    REQUIRE(s == P.n_slots && i == n_live);
+    size_t t_at = 0;
+    for (size_t k = 0; k < n_live; ++k) {
+        REQUIRE(P.nodes[k].first_term == t_at);
+        t_at += P.nodes[k].n_terms;
+    }
+    REQUIRE(t_at == P.terms.size());
+    for (size_t o = 0; o < n_outputs; ++o) REQUIRE(P.outputs[o] == slot_of[outputs[o]] && P.outputs[o] != 0xffffffffu);
+    return 0;
+}
+
+// 2 inputs (wires 0, 1); node 0: v = 1 (wires 2, 3); node 1: v = 0 (wire 4) reads wire 3; node 2: v = 2 (wires 5 .. 8) reads wires 2, 4;
+// node 3: v = 1 (wires 9, 10) reads wire 8: nothing names its outputs
+static Netlist mixed_netlist() {
+    Netlist N;
+    N.n_inputs = 2; N.n_tables = 3;
+    add_node(N, {{0, 1}, {1, 1}}, 0, 0, 1);
+    add_node(N, {{3, 1}, {0, -1}}, 1, 7, 0);
+    add_node(N, {{2, 4}, {4, 1}}, 2, 0, 2);
+    add_node(N, {{8, 1}}, 0, 0, 1);
+    return N;
+}
+
+static int wires_and_liveness() {
+    Netlist N = mixed_netlist();
+    fhe::TfheCircuitPlan P;
+    auto compile = [&](const std::vector<uint32_t> &outs) {
+        return fhe::tfhe_circuit_compile_many(N.nodes.data(), N.nodes.size(), N.terms.data(), N.terms.size(), N.n_inputs, N.n_tables, outs.data(), outs.size(), &P);
+    };
+    // the last wire is 10; an output naming wire 8 = (node 2, output 3)
+    REQUIRE(compile({10}) == FHE_OK && compile({11}) == FHE_ERR_INVALID);
+    REQUIRE(compile({8, 1}) == FHE_OK);
+    REQUIRE(P.many && P.n_live == 3 && P.n_levels == 3 && P.max_width == 1);  // levels run through the many-LUT nodes: 0 -> 1 -> 2
+    REQUIRE((P.level_of_node == std::vector<uint32_t>{1, 2, 3, 0}));          // node 3: every output dead, dropped
+    // node 0: both outputs live (wire 2 feeds node 2, wire 3 node 1); node 2: output 3 alone
+    REQUIRE(P.n_slots == 4 && P.max_rows == 2 && (P.out_start == std::vector<uint32_t>{0, 2, 3, 4}));
+    REQUIRE(P.extracts[0].node == 0 && P.extracts[0].index == 0 && P.extracts[1].node == 0 && P.extracts[1].index == 1);
+    REQUIRE(P.extracts[2].node == 1 && P.extracts[2].index == 0 && P.extracts[3].node == 2 && P.extracts[3].index == 3);
+    REQUIRE((P.outputs == std::vector<uint32_t>{2 + 3, 1}));
+    REQUIRE(P.nodes[0].pad == 1 && P.nodes[1].pad == 0 && P.nodes[2].pad == 2);
+    REQUIRE(P.terms[2].wire == 2 + 1 && P.terms[4].wire == 2 + 0 && P.terms[5].wire == 2 + 2);  // wire 3 -> slot 3, 2 -> 2, 4 -> 4
+    // only output 1 of node 0 live: the node stays, ONE extraction row (index 1), output 0 has no slot
+    REQUIRE(compile({3}) == FHE_OK);
+    REQUIRE(P.n_live == 1 && P.n_levels == 1 && P.n_slots == 1 && P.max_rows == 1 && (P.out_start == std::vector<uint32_t>{0, 1}));
+    REQUIRE(P.extracts[0].node == 0 && P.extracts[0].index == 1 && P.outputs[0] == 2);
+    REQUIRE((P.level_of_node == std::vector<uint32_t>{1, 0, 0, 0}));
+    // outputs that name inputs only: every node dropped
+    REQUIRE(compile({0, 1}) == FHE_OK);
+    REQUIRE(P.n_live == 0 && P.n_slots == 0 && P.n_levels == 0 && P.max_rows == 0 && P.many);
+    return 0;
+}
+
+static int rejected() {
+    Netlist N = mixed_netlist();
+    fhe::TfheCircuitPlan P;
+    const uint32_t out[1] = {8};
+    auto compile = [&](const Netlist &M) {
+        return fhe::tfhe_circuit_compile_many(M.nodes.data(), M.nodes.size(), M.terms.data(), M.terms.size(), M.n_inputs, M.n_tables, out, 1, &P);
+    };
+    REQUIRE(compile(N) == FHE_OK);
+    Netlist M = N;
+    M.nodes[2].pad = 5;                                     // log_funcs = 5
+    REQUIRE(compile(M) == FHE_ERR_INVALID);
+    M.nodes[2].pad = 4;
+    REQUIRE(compile(M) == FHE_OK);
+    M = N; M.terms[2].wire = 4;                             // node 1 (first wire 4) naming its own wire
+    REQUIRE(compile(M) == FHE_ERR_INVALID);
+    M = N; M.terms[4].wire = 5;                             // node 2 (wires 5 .. 8) naming its own first wire
+    REQUIRE(compile(M) == FHE_ERR_INVALID);
+    M = N; M.terms[4].wire = 6;                             // ... and one of its further outputs
+    REQUIRE(compile(M) == FHE_ERR_INVALID);
+    M = N; M.terms[4].wire = 4;                             // the wire just below is fine
+    REQUIRE(compile(M) == FHE_OK);
+    M = N; M.terms[6].wire = 11;                            // node 3 naming a wire past the last
+    REQUIRE(compile(M) == FHE_ERR_INVALID);
+    // fhe_tfhe_circuit_compile ignores the field and numbers one wire per node: wire 8 does not exist there
+    REQUIRE(fhe::tfhe_circuit_compile(N.nodes.data(), N.nodes.size(), N.terms.data(), N.terms.size(), N.n_inputs, N.n_tables, out, 1, &P) == FHE_ERR_INVALID);
+    // the cap of 2^24 wires counts OUTPUT wires: 2^20 nodes of 16 outputs over one input
+    const size_t big = size_t(1) << 20;
+    std::vector<fhe_tfhe_node> nodes(big);
+    const fhe_tfhe_term one[1] = {{0, 1}};
+    for (auto &nd : nodes) { nd = fhe_tfhe_node{}; nd.n_terms = 1; nd.pad = 4; }
+    const uint32_t first[1] = {0};
+    REQUIRE(fhe::tfhe_circuit_compile_many(nodes.data(), big, one, 1, 1, 1, first, 1, &P) == FHE_ERR_INVALID);
+    REQUIRE(fhe::tfhe_circuit_compile_many(nodes.data(), big - 1, one, 1, 1, 1, first, 1, &P) == FHE_OK);   // 1 + 2^24 - 16 wires
+    nodes[big - 1].pad = 3;
+    REQUIRE(fhe::tfhe_circuit_compile_many(nodes.data(), big, one, 1, 1, 1, first, 1, &P) == FHE_OK);        // 1 + 2^24 - 8
+    return 0;
+}
+
+int main() {
+    if (nu0_equals_the_existing_compiler() || wires_and_liveness() || rejected()) return 1;
+    for (int it = 0; it < 300; ++it)
+        if (mixed(1 + rnd(6), rnd(60), 1 + rnd(5), 1 + rnd(4))) return 1;
+    if (mixed(3, 2000, 4, 9)) return 1;
+    std::printf("tfhe_many_host_test ok\n");
+    return 0;
+}
