@@ -58,7 +58,9 @@ int fhe_trim(void);
  * composed route at n = 128 .. 2048 too, instead of the fused kernels), "BR_SPLIT" (FHEW blind rotation: workgroups per ciphertext;
  * -1 = the library's rule, 0 = never split, 2 / 4 / 8 = that many wherever the call admits it -- fused route, n = 1024 or 2048,
  * batch x value <= compute units of the device -- and one workgroup per ciphertext elsewhere; any other value: FHE_ERR_INVALID;
- * fhe_blind_rotate_split tells what a call will run).  Unknown name: FHE_ERR_INVALID. */
+ * fhe_blind_rotate_split tells what a call will run), "PFKS_SPLIT" (fhe_tlwe_pfks: 0 = the library's rule, 1 = one block walks all
+ * input rows of its tile, k >= 2 = k blocks share them and add their partial sums), "PFKS_CHUNK" (fhe_tlwe_pfks: input coefficients whose digits a block
+ * keeps in LDS at a time; 0 = the library's rule).  Unknown name: FHE_ERR_INVALID. */
 int fhe_set_option(const char *name, long value);
 
 /* Entry points that take a modulus instead of a context (fhe_rq_*, fhe_decompose, fhe_automorphism, fhe_monomial_mul,
@@ -927,6 +929,51 @@ int  fhe_tfhe_circuit_create_many(const fhe_tfhe_node *nodes, size_t n_nodes, co
 /* bootstrapping.rs:78-128, tglwe.rs:115-127: live outputs (rows of the wire table) and those of the level that has most (the widest
  * batch of key-switch rows is max_rows * batch); fhe_tfhe_circuit_info's max_width stays in nodes.  Each pointer may be NULL. */
 int  fhe_tfhe_circuit_info_many(const fhe_tfhe_circuit *c, size_t *n_live_outputs, size_t *max_rows);
+
+/* ---- circuit bootstrap (k = 1): a computed TLWE bit becomes the TGGSW selector of fhe_tggsw_cmux (tggsw.rs:114-121) ----
+ * Gadget throughout: Base2Decomposor::<T64>::new(log_b, d) (decompose.rs:66-81, 114-135), g_j = 2^(64 - log_b d + j log_b), digits
+ * those of fhe_torus_decompose, least significant first; rows of a digit x key product are digit-major (row = j rows_in + i, as in
+ * fhe_tlwe_key_switch, tlwe.rs:144-153).
+ *
+ * Private functional key-switch key.  sk_in [n_in]: the binary key of the TLWE ciphertexts to switch (tlwe.rs:122-132); sk_out [n]: the
+ * TGLWE key (tglwe.rs:91-103); funcs [n_funcs][n], 1 <= n_funcs <= 4: plaintext polynomials F_u as integer words (the circuit
+ * bootstrap takes F_0 = -S, F_1 = 1).  pfksk [d (n_in + 1)][n_funcs][2][n]: at word offset ((j (n_in + 1) + i) n_funcs + u) 2 n stand
+ * a [n], then b [n], of a TGLWE encryption under sk_out (b = a s + e + pt, tglwe.rs:91-103) of pt = w_i g_j F_u mod 2^64, w_i =
+ * -sk_in[i] for i < n_in and w_{n_in} = 1 (the row of the ciphertext's b): b - a sk_out - pt is the drawn error of every row.  Draws
+ * come under a purpose tag of this entry's own: no keystream is shared with fhe_tglwe_sk_encrypt on the same (rng, stream_id).
+ * n: a ring the torus context serves; log_b d > 64, n_funcs outside 1 .. 4: FHE_ERR_INVALID. */
+int fhe_tlwe_pfksk_gen(const fhe_torus_ctx *t, int log_b, int d, const uint64_t *sk_in, size_t n_in, const uint64_t *sk_out, size_t n,
+                       const uint64_t *funcs, int n_funcs, double std_dev, const fhe_rng *rng, uint64_t stream_id, uint64_t *pfksk, fhe_mem mem,
+                       void *stream);
+/* The private functional key switch TLWE -> TGLWE (tlwe.rs:144-153's product against rows that are TGLWE ciphertexts, tglwe.rs:91-103).
+ * With c = (ct_a[r][0 .. n_in - 1], ct_b[r]) of input r: out(r, u) = sum_j sum_i digit_j(c_i) * pfksk[j (n_in + 1) + i][u] over Z/2^64
+ * on both halves, a TGLWE ciphertext whose phase is F_u times the phase of input r, plus the rounding of the digits.  ct_a
+ * [batch][n_in], ct_b [batch]; out_a, out_b [batch n_funcs][n]; the row of (r, u) is ((r / group) n_funcs + u) group + r % group:
+ * group = 1 is the plain [batch][n_funcs] order, group = d' with n_funcs = 2 the row order of a TGGSW ciphertext of d' levels
+ * (tggsw.rs:79-88).  batch must be a multiple of group.  The outputs must not overlap the inputs or the key: FHE_MEM_DEVICE calls whose
+ * out_a or out_b equals ct_a, ct_b or pfksk, and any call with out_a == out_b, return FHE_ERR_INVALID.  log_b > 31: FHE_ERR_UNSUPPORTED.
+ * Every schedule (tile, row split, lab switch "PFKS_SPLIT") gives the same bits. */
+int fhe_tlwe_pfks(int log_b, int d, const uint64_t *pfksk, int n_funcs, const uint64_t *ct_a, const uint64_t *ct_b, size_t n_in, size_t n,
+                  size_t group, uint64_t *out_a, uint64_t *out_b, size_t batch, fhe_mem mem, void *stream);
+/* The test polynomial of the circuit bootstrap, the pattern of bootstrapping.rs:118-128 on raw torus values f_j(0) = 0, f_j(1) = g_j:
+ * out[c] = T_{c mod 2^nu}[c - c mod 2^nu], nu = ceil(log2 cb_d), T_j[c] = g_j of (cb_log_b, cb_d) for n/4 <= c < 3n/4 and j < cb_d,
+ * 0 elsewhere.  out [n], host memory.  cb_d outside 1 .. 16 or n/4 no multiple of 2^nu: FHE_ERR_INVALID; n outside 256 .. 2048:
+ * FHE_ERR_UNSUPPORTED. */
+int fhe_tfhe_cbs_table(int cb_log_b, int cb_d, size_t n, uint64_t *out);
+/* Stream-ordered scratch of fhe_tfhe_circuit_bootstrap in 64-bit words (plus the n words of the table).  n no power of two, n_lwe = 0,
+ * cb_d outside 1 .. 16: FHE_ERR_INVALID; n outside 256 .. 2048: FHE_ERR_UNSUPPORTED. */
+int fhe_tfhe_cbs_workspace(size_t n, size_t n_lwe, int cb_d, size_t batch, size_t *words);
+/* Circuit bootstrap in one call.  lwe_a [batch][n_lwe], lwe_b [batch]: TLWE encryptions (tlwe.rs:122-132) of a bit, pt = bit << 62.
+ * Steps, all on `stream`: fhe_tfhe_mod_switch_many with nu = ceil(log2 cb_d) (bootstrapping.rs:99-104) -> fhe_tfhe_blind_rotate of
+ * fhe_tfhe_cbs_table (84-96) -> sample_extract(j), j < cb_d (tglwe.rs:115-127; no TLWE key switch) -> fhe_tlwe_pfks with group =
+ * cb_d under the two-function key pfksk (F_0 = -S, F_1 = 1; n_in = n; gadget (pf_log_b, pf_d)).  rows_a, rows_b [batch][2 cb_d][n]:
+ * the rows of `batch` TGGSW ciphertexts of the bits in Tggsw::sk_encrypt's order (tggsw.rs:79-88), ready for fhe_tggsw_prepare /
+ * fhe_tggsw_prepare_fft64 with count = batch.  Bit-identical to the four entries chained, in every exact key form (fft64: on the same
+ * device).  The rows must not overlap an input: rows_a == rows_b, and FHE_MEM_DEVICE calls whose rows_a or rows_b equals lwe_a, lwe_b
+ * or pfksk, return FHE_ERR_INVALID. */
+int fhe_tfhe_circuit_bootstrap(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, int cb_log_b, int cb_d, int pf_log_b, int pf_d,
+                               const uint64_t *pfksk, const uint64_t *lwe_a, const uint64_t *lwe_b, uint64_t *rows_a, uint64_t *rows_b,
+                               size_t batch, fhe_mem mem, void *stream);
 
 #ifdef __cplusplus
 }

@@ -137,6 +137,12 @@ def lib():
         L.fhe_tfhe_bootstrap_many.argtypes = [vp, vp, ci, ci, vp, vp, vp, sz, vp, ci, vp, vp, vp, vp, sz, ci, vp]
         L.fhe_tfhe_circuit_create_many.argtypes = [vp, sz, vp, sz, sz, sz, u32p, sz, C.POINTER(vp)]
         L.fhe_tfhe_circuit_info_many.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
+        # circuit bootstrap: TLWE bit -> TGGSW selector (tfhe_cbs_api.hip, torus_api.hip)
+        L.fhe_tlwe_pfksk_gen.argtypes = [vp, ci, ci, vp, sz, vp, sz, vp, ci, C.c_double, vp, C.c_uint64, vp, ci, vp]
+        L.fhe_tlwe_pfks.argtypes = [ci, ci, vp, ci, vp, vp, sz, sz, sz, vp, vp, sz, ci, vp]
+        L.fhe_tfhe_cbs_table.argtypes = [ci, ci, sz, u64p]
+        L.fhe_tfhe_cbs_workspace.argtypes = [sz, sz, ci, sz, C.POINTER(sz)]
+        L.fhe_tfhe_circuit_bootstrap.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, sz, ci, vp]
         L.fhe_torus_ctx_create.argtypes = [ci, C.POINTER(vp)]
         L.fhe_torus_ctx_destroy.argtypes = [vp]
         L.fhe_torus_ctx_destroy.restype = None

@@ -13,6 +13,8 @@
 #include "lwe_kernels.hpp"
 #include "keygen_kernels.hpp"
 #include "tfhe_circuit_kernels.hpp"
+#include "pfks_kernels.hpp"
+#include "tfhe_cbs.hpp"
 
 namespace {
 
@@ -970,6 +972,37 @@ int fhe_tggsw_encrypt(const fhe_torus_ctx *t, int log_b, int d, const uint64_t *
         rc = fhe::launch<fhe::tggsw_add_gadget_kernel>(grid_for(count * d * n), 256, 0, st, ma.d, mb.d, (const u64 *)mpt.d, n, count, d, 64 - log_b * d, log_b);
     if (rc == FHE_OK) rc = ma.sync_out(st);
     if (rc == FHE_OK) rc = mb.sync_out(st);
+    return rc;
+}
+
+// include/fhe_ring.h: the key of fhe_tlwe_pfks.  Row (j (n_in + 1) + i, u) is tglwe.rs:91-103 of w_i g_j F_u: the plaintext rows are
+// built on the device, encrypted by the kernels of fhe_tglwe_sk_encrypt under this entry's own purpose tag, and laid side by side.
+int fhe_tlwe_pfksk_gen(const fhe_torus_ctx *t, int log_b, int d, const uint64_t *sk_in, size_t n_in, const uint64_t *sk_out, size_t n,
+                       const uint64_t *funcs, int n_funcs, double std_dev, const fhe_rng *rng, uint64_t stream_id, uint64_t *pfksk, fhe_mem mem,
+                       void *stream) {
+    if (!rng) return FHE_ERR_INVALID;
+    int rc = torus_ring_ok(t, n);
+    if (rc != FHE_OK) return rc;
+    if (!fhe::cbs_gadget_ok(log_b, d) || n_funcs < 1 || n_funcs > fhe::PFKS_MAX_FUNCS || n_in == 0 || !sk_in || !sk_out || !funcs || !pfksk ||
+        !(std_dev >= 0))
+        return FHE_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    DeviceGuard guard(t->device);
+    if (!guard.ok) return FHE_ERR_HIP;
+    const size_t rows = size_t(d) * (n_in + 1) * n_funcs, words = rows * n;
+    Mirror mi(sk_in, n_in, mem, true, st), mo(sk_out, n, mem, true, st), mf(funcs, size_t(n_funcs) * n, mem, true, st), mk(pfksk, 2 * words, mem, false, st);
+    if (mi.rc | mo.rc | mf.rc | mk.rc) return FHE_ERR_HIP;
+    StreamWs ws(3 * words * sizeof(u64), st);  // plaintexts | a | b, [rows][n] each
+    if (ws.rc != FHE_OK) return ws.rc;
+    u64 *pt = ws.as<u64>(), *ca = pt + words, *cb = ca + words;
+    rc = fhe::launch<fhe::pfksk_plain_kernel>(grid_for(words), 256, 0, st, (const u64 *)mi.d, (const u64 *)mf.d, pt, n_in, n, (size_t)n_funcs, d,
+                                              64 - log_b * d, log_b);
+    unsigned long long cursor = 0;
+    if (rc == FHE_OK)
+        rc = tglwe_sk_encrypt_dev(t, mo.d, pt, rows, ca, cb, ilog2(n), rows, std_dev, fhe::call_key(rng, stream_id, fhe::RNG_TLWE_PFKSK), &cursor, st);
+    // [rows][n] a and b -> [rows][2][n]
+    if (rc == FHE_OK) rc = fhe::launch<fhe::pfksk_pack_kernel>(grid_for(2 * words), 256, 0, st, (const u64 *)ca, (const u64 *)cb, mk.d, rows, n);
+    if (rc == FHE_OK) rc = mk.sync_out(st);
     return rc;
 }
 
