@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <new>
 
 #include "../../include/fhe_ring.h"
 #include "dev_arith.hpp"
@@ -253,4 +254,67 @@ struct Mirror {
     Mirror(const Mirror &) = delete;
     Mirror &operator=(const Mirror &) = delete;
 };
+
+// What a prepared handle's kernels read (a compiled circuit's descriptors), uploaded to a device when the handle first runs there and
+// freed with the handle.  The image is the parts laid end to end, each padded to a multiple of 8 bytes (an empty part takes 8).
+struct ImagePart {
+    const void *p;
+    size_t bytes;
+};
+struct DeviceImage {
+    std::mutex mu;
+    void *d[fhe::MAX_DEVICES] = {};
+    static size_t padded(size_t bytes) { return bytes ? (bytes + 7) & ~size_t(7) : 8; }
+    // at[i]: part i on device `dev`; the parts must be the same on every call
+    template <size_t N>
+    int get(int dev, const ImagePart (&parts)[N], const unsigned char *(&at)[N]) {
+        if (dev < 0 || dev >= fhe::MAX_DEVICES) return FHE_ERR_INVALID;
+        std::lock_guard<std::mutex> lock(mu);
+        size_t total = 0;
+        for (const ImagePart &pt : parts) total += padded(pt.bytes);
+        if (!d[dev]) {
+            void *p = nullptr;
+            HIP_TRY(hipMalloc(&p, total));
+            hipError_t e = hipSuccess;
+            size_t off = 0;
+            for (const ImagePart &pt : parts) {
+                if (e == hipSuccess && pt.bytes) e = hipMemcpy((unsigned char *)p + off, pt.p, pt.bytes, hipMemcpyHostToDevice);
+                off += padded(pt.bytes);
+            }
+            if (e != hipSuccess) { fhe::g_last_hip = (int)e; (void)hipFree(p); return FHE_ERR_HIP; }
+            d[dev] = p;
+        }
+        size_t off = 0;
+        for (size_t i = 0; i < N; ++i) {
+            at[i] = (const unsigned char *)d[dev] + off;
+            off += padded(parts[i].bytes);
+        }
+        return FHE_OK;
+    }
+    ~DeviceImage() {
+        for (int dev = 0; dev < fhe::MAX_DEVICES; ++dev) {
+            if (!d[dev]) continue;
+            DeviceGuard guard(dev);
+            (void)hipFree(d[dev]);
+        }
+    }
+};
+
+// The body of a handle's create entry: a new H, compile(h) -> FHE_* with an allocation failure caught, no handle unless FHE_OK
+template <class H, class F>
+int create_handle(H **out, F &&compile) {
+    if (!out) return FHE_ERR_INVALID;
+    *out = nullptr;
+    H *h = new (std::nothrow) H();
+    if (!h) return FHE_ERR_INVALID;
+    int rc;
+    try {
+        rc = compile(h);
+    } catch (const std::bad_alloc &) {
+        rc = FHE_ERR_INVALID;
+    }
+    if (rc != FHE_OK) { delete h; return rc; }
+    *out = h;
+    return FHE_OK;
+}
 }  // namespace

@@ -1,14 +1,16 @@
 // The netlist compiler behind fhe_fhew_circuit_create: plain host C++ (no HIP), so that it also builds into a stand-alone program.
 // A netlist of `Fhew` gates (scheme/fhew/src/fhew.rs:59-67) with free inversions (fhew.rs:27-29) is validated, pruned to the gates an
-// output depends on, levelled (level = 1 + max level of the inputs, inputs at level 0) and renumbered into SLOTS: slot s < n_inputs is
-// input s, slot n_inputs + i the i-th live gate in level order (ties keep the netlist's order), so the gates of one level write one
-// contiguous run of the wire table.
+// output depends on and levelled (netlist_levels.hpp: level = 1 + max level of the inputs, inputs at level 0), then renumbered into
+// SLOTS: slot s < n_inputs is input s, slot n_inputs + i the i-th live gate in level order (ties keep the netlist's order), so the gates
+// of one level write one contiguous run of the wire table.
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <utility>
 #include <vector>
 
 #include "../../include/fhe_ring.h"
+#include "netlist_levels.hpp"
 
 namespace fhe {
 
@@ -45,53 +47,32 @@ inline int circuit_compile(const fhe_fhew_gate *gates, size_t n_gates, size_t n_
     }
     for (size_t o = 0; o < n_outputs; ++o)
         if ((outputs[o] & WIRE_INDEX_MASK) >= n_wires) return FHE_ERR_INVALID;
-    // liveness: backwards from the outputs (a gate only reads lower wires)
-    std::vector<unsigned char> live(n_wires, 0);
-    for (size_t o = 0; o < n_outputs; ++o) live[outputs[o] & WIRE_INDEX_MASK] = 1;
-    for (size_t g = n_gates; g-- > 0;) {
-        if (!live[n_inputs + g]) continue;
-        for (int k = 0; k < gate_arity(gates[g].op); ++k) live[gates[g].in[k] & WIRE_INDEX_MASK] = 1;
-    }
-    // levels: forwards
-    std::vector<uint32_t> level(n_wires, 0);
-    plan->level_of_gate.assign(n_gates, 0);
-    uint32_t n_levels = 0;
-    for (size_t g = 0; g < n_gates; ++g) {
-        if (!live[n_inputs + g]) continue;
-        uint32_t lv = 0;
-        for (int k = 0; k < gate_arity(gates[g].op); ++k) {
-            const uint32_t l = level[gates[g].in[k] & WIRE_INDEX_MASK];
-            if (l > lv) lv = l;
-        }
-        level[n_inputs + g] = plan->level_of_gate[g] = lv + 1;
-        if (lv + 1 > n_levels) n_levels = lv + 1;
-    }
-    // slots: a counting sort of the live gates by level
-    plan->level_start.assign(size_t(n_levels) + 1, 0);
-    for (size_t g = 0; g < n_gates; ++g)
-        if (plan->level_of_gate[g]) ++plan->level_start[plan->level_of_gate[g]];
-    size_t max_width = 0;
-    for (uint32_t l = 1; l <= n_levels; ++l) {
-        if (plan->level_start[l] > max_width) max_width = plan->level_start[l];
-        plan->level_start[l] += plan->level_start[l - 1];
-    }
-    const size_t n_live = plan->level_start[n_levels];
-    std::vector<uint32_t> slot(n_wires, 0), next(plan->level_start.begin(), plan->level_start.end());
+    // pruning and levels (netlist_levels.hpp): a gate owns one wire
+    std::vector<uint32_t> first_wire(n_gates + 1), out_wires(n_outputs);
+    for (size_t g = 0; g <= n_gates; ++g) first_wire[g] = (uint32_t)(n_inputs + g);
+    for (size_t o = 0; o < n_outputs; ++o) out_wires[o] = outputs[o] & WIRE_INDEX_MASK;
+    NetlistLevels L;
+    netlist_levels(first_wire.data(), n_gates, out_wires.data(), n_outputs, [&](size_t g, auto &&f) {
+        for (int k = 0; k < gate_arity(gates[g].op); ++k) f(gates[g].in[k] & WIRE_INDEX_MASK);
+    }, &L);
+    // slots: the live gates in level order
+    const size_t n_live = L.source.size();
+    std::vector<uint32_t> slot(n_wires, 0);
     for (size_t w = 0; w < n_inputs; ++w) slot[w] = (uint32_t)w;
-    for (size_t g = 0; g < n_gates; ++g)
-        if (plan->level_of_gate[g]) slot[n_inputs + g] = (uint32_t)(n_inputs + next[plan->level_of_gate[g] - 1]++);
+    for (size_t i = 0; i < n_live; ++i) slot[n_inputs + L.source[i]] = (uint32_t)(n_inputs + i);
     auto to_slot = [&](uint32_t ref) { return slot[ref & WIRE_INDEX_MASK] | (ref & FHE_WIRE_NOT); };
     plan->gates.assign(n_live, CircuitGate{});
-    for (size_t g = 0; g < n_gates; ++g) {
-        if (!plan->level_of_gate[g]) continue;
-        CircuitGate &cg = plan->gates[slot[n_inputs + g] - n_inputs];
-        cg.op = gates[g].op;
-        for (int k = 0; k < 3; ++k) cg.in[k] = k < gate_arity(gates[g].op) ? to_slot(gates[g].in[k]) : 0u;
+    for (size_t i = 0; i < n_live; ++i) {
+        const fhe_fhew_gate &gt = gates[L.source[i]];
+        plan->gates[i].op = gt.op;
+        for (int k = 0; k < 3; ++k) plan->gates[i].in[k] = k < gate_arity(gt.op) ? to_slot(gt.in[k]) : 0u;
     }
     plan->outputs.resize(n_outputs);
     for (size_t o = 0; o < n_outputs; ++o) plan->outputs[o] = to_slot(outputs[o]);
     plan->n_inputs = n_inputs; plan->n_gates = n_gates; plan->n_outputs = n_outputs;
-    plan->n_levels = n_levels; plan->n_live = n_live; plan->max_width = max_width;
+    plan->n_levels = L.n_levels; plan->n_live = n_live; plan->max_width = L.max_width;
+    plan->level_of_gate = std::move(L.level_of_node);
+    plan->level_start = std::move(L.level_start);
     return FHE_OK;
 }
 

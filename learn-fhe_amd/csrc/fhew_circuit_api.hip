@@ -3,8 +3,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <mutex>
-#include <new>
 #include <vector>
 
 #include "api_common.hpp"
@@ -14,35 +12,13 @@
 
 struct fhe_fhew_circuit {
     fhe::CircuitPlan plan;
-    // the plan as the kernels read it, uploaded to a device when the circuit first runs there: gates [n_live] | outputs [n_outputs]
-    mutable std::mutex mu;
-    mutable void *d_image[fhe::MAX_DEVICES] = {};
+    mutable DeviceImage image;  // the plan as the kernels read it: gates [n_live] | outputs [n_outputs]
 };
 
 namespace {
 
 // BootstrappingParam::big_q_by_8 / big_q_by_4 (scheme/fhew/src/bootstrapping.rs:62-68): Zq::from_f64(q, q as f64 / k as f64)
 uint64_t round_div(uint64_t q, double k) { return (uint64_t)std::round((double)q / k) % q; }
-
-size_t image_gate_bytes(const fhe::CircuitPlan &P) { return (P.n_live ? P.n_live : 1) * sizeof(fhe::CircuitGate); }
-
-int device_image(const fhe_fhew_circuit *c, int dev, const fhe::CircuitGate **gates, const unsigned **outputs) {
-    if (dev < 0 || dev >= fhe::MAX_DEVICES) return FHE_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(c->mu);
-    const fhe::CircuitPlan &P = c->plan;
-    const size_t gb = image_gate_bytes(P), ob = P.n_outputs * sizeof(unsigned);
-    if (!c->d_image[dev]) {
-        void *p = nullptr;
-        HIP_TRY(hipMalloc(&p, gb + ob));
-        hipError_t e = P.n_live ? hipMemcpy(p, P.gates.data(), P.n_live * sizeof(fhe::CircuitGate), hipMemcpyHostToDevice) : hipSuccess;
-        if (e == hipSuccess) e = hipMemcpy((unsigned char *)p + gb, P.outputs.data(), ob, hipMemcpyHostToDevice);
-        if (e != hipSuccess) { g_last_hip = (int)e; (void)hipFree(p); return FHE_ERR_HIP; }
-        c->d_image[dev] = p;
-    }
-    *gates = (const fhe::CircuitGate *)c->d_image[dev];
-    *outputs = (const unsigned *)((const unsigned char *)c->d_image[dev] + gb);
-    return FHE_OK;
-}
 
 inline bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 
@@ -52,30 +28,10 @@ extern "C" {
 
 int fhe_fhew_circuit_create(const fhe_fhew_gate *gates, size_t n_gates, size_t n_inputs, const uint32_t *outputs, size_t n_outputs,
                             fhe_fhew_circuit **out) {
-    if (!out) return FHE_ERR_INVALID;
-    *out = nullptr;
-    fhe_fhew_circuit *c = new (std::nothrow) fhe_fhew_circuit();
-    if (!c) return FHE_ERR_INVALID;
-    int rc;
-    try {
-        rc = fhe::circuit_compile(gates, n_gates, n_inputs, outputs, n_outputs, &c->plan);
-    } catch (const std::bad_alloc &) {
-        rc = FHE_ERR_INVALID;
-    }
-    if (rc != FHE_OK) { delete c; return rc; }
-    *out = c;
-    return FHE_OK;
+    return create_handle(out, [&](fhe_fhew_circuit *c) { return fhe::circuit_compile(gates, n_gates, n_inputs, outputs, n_outputs, &c->plan); });
 }
 
-void fhe_fhew_circuit_destroy(fhe_fhew_circuit *c) {
-    if (!c) return;
-    for (int dev = 0; dev < fhe::MAX_DEVICES; ++dev) {
-        if (!c->d_image[dev]) continue;
-        DeviceGuard guard(dev);
-        (void)hipFree(c->d_image[dev]);
-    }
-    delete c;
-}
+void fhe_fhew_circuit_destroy(fhe_fhew_circuit *c) { delete c; }
 
 int fhe_fhew_circuit_info(const fhe_fhew_circuit *c, size_t *n_levels, size_t *n_live_gates, size_t *max_width) {
     if (!c) return FHE_ERR_INVALID;
@@ -110,9 +66,11 @@ int fhe_fhew_circuit_run(const fhe_fhew_circuit *c, const fhe_bootstrap_key *bk,
     hipStream_t st = (hipStream_t)stream;
     DeviceGuard guard(ctx->device);
     if (!guard.ok) return FHE_ERR_HIP;
-    const fhe::CircuitGate *d_gates = nullptr;
-    const unsigned *d_outputs = nullptr;
-    FHE_TRY(device_image(c, ctx->device, &d_gates, &d_outputs));
+    const ImagePart parts[] = {{P.gates.data(), P.n_live * sizeof(fhe::CircuitGate)}, {P.outputs.data(), P.n_outputs * sizeof(unsigned)}};
+    const unsigned char *img[2];
+    FHE_TRY(c->image.get(ctx->device, parts, img));
+    const fhe::CircuitGate *d_gates = (const fhe::CircuitGate *)img[0];
+    const unsigned *d_outputs = (const unsigned *)img[1];
     const size_t ks_rows = n * ks_d;
     Mirror mka(lwe_ksk_a, ks_rows * n_lwe, mem, true, st), mkb(lwe_ksk_b, ks_rows, mem, true, st);
     Mirror mia(in_a, P.n_inputs * batch * n, mem, true, st), mib(in_b, P.n_inputs * batch, mem, true, st);

@@ -12,6 +12,7 @@
 #include <cstdint>
 
 #include "../../include/fhe_ring.h"
+#include "tfhe_circuit.hpp"  // TfheScratch
 
 namespace fhe {
 
@@ -83,11 +84,9 @@ inline int pfks_check(int log_b, int d, int n_funcs, size_t n_in, size_t n, size
     return FHE_OK;
 }
 
-// Stream-ordered scratch of fhe_tfhe_circuit_bootstrap in 64-bit words: the accumulators a and b [batch][n], the extracted TLWEs
-// a [batch cb_d][n], then a~ [batch][n_lwe], b~ [batch] and the extracted b [batch cb_d] (the [..][n] arrays first: each starts on
-// a 16-byte boundary).  The key switch adds none: it reads the extracted rows and writes the caller's output.
-inline size_t cbs_workspace(size_t n, size_t n_lwe, int cb_d, size_t batch) {
-    return 2 * batch * n + batch * size_t(cb_d) * n + batch * n_lwe + batch + batch * size_t(cb_d);
-}
+// Stream-ordered scratch of fhe_tfhe_circuit_bootstrap in 64-bit words (tfhe_circuit.hpp: TfheScratch): batch blind rotations, batch cb_d
+// extracted TLWEs, no wire table.  The key switch adds none: it reads the extracted rows and writes the caller's output.
+inline TfheScratch cbs_scratch(size_t n, size_t n_lwe, int cb_d, size_t batch) { return TfheScratch(batch, batch * size_t(cb_d), n, n_lwe, 0, false); }
+inline size_t cbs_workspace(size_t n, size_t n_lwe, int cb_d, size_t batch) { return cbs_scratch(n, n_lwe, cb_d, batch).total; }
 
 }  // namespace fhe

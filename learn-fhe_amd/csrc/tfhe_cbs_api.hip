@@ -119,22 +119,18 @@ int fhe_tfhe_circuit_bootstrap(const fhe_torus_ctx *t, const fhe_tggsw_key *brk,
     Mirror mk(pfksk, fhe::pfksk_words(pf_d, n, 2, n), mem, true, st), ma(lwe_a, n_lwe * batch, mem, true, st), mb(lwe_b, batch, mem, true, st),
         moa(rows_a, outs, mem, false, st), mob(rows_b, outs, mem, false, st);
     if (mk.rc | ma.rc | mb.rc | moa.rc | mob.rc) return FHE_ERR_HIP;
-    // acc.a | acc.b | extracted a | a~ | b~ | extracted b (tfhe_cbs.hpp: cbs_workspace), then the table
-    StreamWs ws((fhe::cbs_workspace(n, n_lwe, cb_d, batch) + n) * sizeof(u64), st);
-    if (ws.rc != FHE_OK) return ws.rc;
-    u64 *ra = ws.as<u64>(), *rb = ra + batch * n, *ea = rb + batch * n, *at = ea + levels * n, *bt = at + batch * n_lwe, *eb = bt + batch, *tab = eb + levels;
+    const fhe::TfheScratch L = fhe::cbs_scratch(n, n_lwe, cb_d, batch);  // then the table [n]
+    StreamWs wsp((L.total + n) * sizeof(u64), st);
+    if (wsp.rc != FHE_OK) return wsp.rc;
+    u64 *ws = wsp.as<u64>(), *ra = ws + L.acc_a, *rb = ws + L.acc_b, *ea = ws + L.ext_a, *eb = ws + L.ext_b, *at = ws + L.at, *bt = ws + L.bt;
+    u64 *tab = ws + L.total;
     typedef uint64_t U;
     rc = fhe::launch<fhe::cbs_table_kernel>(grid_for(n), 256, 0, st, tab, (unsigned)n, nu, cb_log_b, cb_d);
     if (rc == FHE_OK) rc = fhe_tfhe_mod_switch_many((const U *)ma.d, (U *)at, batch * n_lwe, n, nu, FHE_MEM_DEVICE, stream);
     if (rc == FHE_OK) rc = fhe_tfhe_mod_switch_many((const U *)mb.d, (U *)bt, batch, n, nu, FHE_MEM_DEVICE, stream);
     if (rc == FHE_OK) rc = fhe_tfhe_blind_rotate(t, brk, (const U *)at, (const U *)bt, (const U *)tab, (U *)ra, (U *)rb, batch, FHE_MEM_DEVICE, stream);
-    if (rc == FHE_OK) {  // tglwe.rs:115-127 for the indices 0 .. cb_d - 1 alone: [batch][cb_d][n], the key switch's input order
-        constexpr unsigned WAVES = 4;
-        const unsigned grid = (unsigned)std::min<size_t>((batch + WAVES - 1) / WAVES, 8192);
-        rc = fhe::launch<fhe::tglwe_sample_extract_many_kernel<true>>(grid, 64 * WAVES, WAVES * n * sizeof(u64), st, (const u64 *)ra, (const u64 *)rb,
-                                                                      (unsigned)n, 1u, (unsigned)batch, (const unsigned *)nullptr,
-                                                                      (const fhe::TfheExtract *)nullptr, 0u, (unsigned)cb_d, size_t(1), size_t(cb_d), ea, eb);
-    }
+    // tglwe.rs:115-127 for the indices 0 .. cb_d - 1 alone: [batch][cb_d][n], the key switch's input order
+    if (rc == FHE_OK) rc = fhe::launch_sample_extract_many(ra, rb, n, 1, batch, nullptr, nullptr, 0, (size_t)cb_d, 1, (size_t)cb_d, ea, eb, st);
     if (rc == FHE_OK) rc = pfks_dev(P, mk.d, 2, ea, eb, n, n, (size_t)cb_d, moa.d, mob.d, levels, st);
     if (rc == FHE_OK) rc = moa.sync_out(st);
     if (rc == FHE_OK) rc = mob.sync_out(st);

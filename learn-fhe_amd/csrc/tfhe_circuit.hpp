@@ -2,9 +2,9 @@
 // into a stand-alone program.
 // A netlist of look-up-table nodes -- node g = bootstrap(tables[table], constant + sum weight * wire), the pattern of
 // scheme/tfhe/src/bootstrapping.rs:118-165 over the free TLWE arithmetic of tlwe.rs:22-75 -- is validated, pruned to the nodes an output
-// depends on, levelled (level = 1 + max level of the inputs, inputs at level 0) and renumbered into SLOTS: slot s < n_inputs is input s,
-// slot n_inputs + i the i-th live node in level order (ties keep the netlist's order), so the nodes of one level write one contiguous
-// run of the wire table.  The terms of the live nodes are repacked in the same order.
+// depends on and levelled (netlist_levels.hpp: level = 1 + max level of the inputs, inputs at level 0), then renumbered into SLOTS:
+// slot s < n_inputs is input s, slot n_inputs + i the i-th live node in level order (ties keep the netlist's order), so the nodes of
+// one level write one contiguous run of the wire table.  The terms of the live nodes are repacked in the same order.
 //
 // Many-LUT nodes (tfhe_circuit_compile_many): a node with log_funcs = v > 0 is ONE blind rotation of a test polynomial that interleaves
 // 2^v tables and owns 2^v consecutive wires, output i = sample_extract(acc, i) (tglwe.rs:115-127).  Liveness is per OUTPUT: a node is
@@ -14,9 +14,11 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <utility>
 #include <vector>
 
 #include "../../include/fhe_ring.h"
+#include "netlist_levels.hpp"
 
 namespace fhe {
 
@@ -43,6 +45,29 @@ struct TfheCircuitPlan {
     size_t n_slots = 0, max_rows = 0;     // live outputs; those of the level that has most
     std::vector<uint32_t> out_start;      // [n_live + 1]: live node i owns slots n_inputs + out_start[i] .. n_inputs + out_start[i + 1] - 1
     std::vector<TfheExtract> extracts;    // [n_slots], slot order: the level's extraction descriptors are those of its nodes' slots
+};
+
+// The stream-ordered scratch of every composition "mod switch (or level front) -> blind rotation -> sample extraction -> key switch":
+// fhe_tfhe_bootstrap, _tables and _many, fhe_tfhe_circuit_run and fhe_tfhe_circuit_bootstrap.  Offsets in 64-bit words from a base that
+// is 16-byte aligned.  THE LAYOUT RULE: the [..][n] arrays come first, so that each starts on an even word (n is even) and the kernels
+// may use 16-byte accesses on them; the rest follows in the order the steps touch it.
+//   acc.a, acc.b [jobs][n] | extracted a [rows][n] | wire table a [wt_rows][n_lwe] | a~ [jobs][n_lwe] | wire table b [wt_rows] |
+//   b~ [jobs] | extracted b [rows] | table_of [jobs] (32-bit, two to a word; only with `table`)
+// jobs: blind rotations of the widest step; rows: extracted TLWEs of the widest step; wt_rows: rows of a circuit's wire table (else 0).
+struct TfheScratch {
+    size_t acc_a, acc_b, ext_a, wt_a, at, wt_b, bt, ext_b, table_of, total;
+    TfheScratch(size_t jobs, size_t rows, size_t n, size_t n_lwe, size_t wt_rows, bool table) {
+        acc_a = 0;
+        acc_b = acc_a + jobs * n;
+        ext_a = acc_b + jobs * n;
+        wt_a = ext_a + rows * n;
+        at = wt_a + wt_rows * n_lwe;
+        wt_b = at + jobs * n_lwe;
+        bt = wt_b + wt_rows;
+        ext_b = bt + jobs;
+        table_of = ext_b + rows;
+        total = table_of + (table ? (jobs + 1) / 2 : 0);
+    }
 };
 
 namespace detail {
@@ -77,48 +102,13 @@ inline int tfhe_circuit_compile_any(const fhe_tfhe_node *nodes, size_t n_nodes, 
     first_wire[n_nodes] = (uint32_t)n_wires;
     for (size_t o = 0; o < n_outputs; ++o)
         if (outputs[o] >= n_wires) return FHE_ERR_INVALID;
-    // liveness: backwards from the outputs (a node only reads lower wires); a node is live when any of its outputs is
-    std::vector<unsigned char> live(n_wires, 0);
-    for (size_t o = 0; o < n_outputs; ++o) live[outputs[o]] = 1;
-    std::vector<unsigned char> node_live(n_nodes, 0);
-    for (size_t g = n_nodes; g-- > 0;) {
-        for (uint32_t w = first_wire[g]; w < first_wire[g + 1]; ++w) node_live[g] |= live[w];
-        if (!node_live[g]) continue;
-        for (uint32_t k = 0; k < nodes[g].n_terms; ++k) live[terms[nodes[g].first_term + k].wire] = 1;
-    }
-    // levels: forwards; every output of a node carries the node's level
-    std::vector<uint32_t> level(n_wires, 0);
-    plan->level_of_node.assign(n_nodes, 0);
-    uint32_t n_levels = 0;
-    size_t live_terms = 0;
-    for (size_t g = 0; g < n_nodes; ++g) {
-        if (!node_live[g]) continue;
-        uint32_t lv = 0;
-        for (uint32_t k = 0; k < nodes[g].n_terms; ++k) {
-            const uint32_t l = level[terms[nodes[g].first_term + k].wire];
-            if (l > lv) lv = l;
-        }
-        plan->level_of_node[g] = lv + 1;
-        for (uint32_t w = first_wire[g]; w < first_wire[g + 1]; ++w) level[w] = lv + 1;
-        if (lv + 1 > n_levels) n_levels = lv + 1;
-        live_terms += nodes[g].n_terms;
-    }
-    // live nodes in level order: a counting sort by level
-    plan->level_start.assign(size_t(n_levels) + 1, 0);
-    for (size_t g = 0; g < n_nodes; ++g)
-        if (plan->level_of_node[g]) ++plan->level_start[plan->level_of_node[g]];
-    size_t max_width = 0;
-    for (uint32_t l = 1; l <= n_levels; ++l) {
-        if (plan->level_start[l] > max_width) max_width = plan->level_start[l];
-        plan->level_start[l] += plan->level_start[l - 1];
-    }
-    const size_t n_live = plan->level_start[n_levels];
-    std::vector<uint32_t> next(plan->level_start.begin(), plan->level_start.end());
-    std::vector<uint32_t> source(n_live, 0);  // live node in level order -> netlist index
-    for (size_t g = 0; g < n_nodes; ++g) {
-        if (!plan->level_of_node[g]) continue;
-        source[next[plan->level_of_node[g] - 1]++] = (uint32_t)g;
-    }
+    // pruning and levels (netlist_levels.hpp): a node is live when any of its outputs is, every output carries the node's level
+    NetlistLevels L;
+    netlist_levels(first_wire.data(), n_nodes, outputs, n_outputs, [&](size_t g, auto &&f) {
+        for (uint32_t k = 0; k < nodes[g].n_terms; ++k) f(terms[nodes[g].first_term + k].wire);
+    }, &L);
+    const std::vector<uint32_t> &source = L.source;
+    const size_t n_live = source.size();
     // slots: the live outputs of the live nodes, in that order
     std::vector<uint32_t> slot(n_wires, 0xffffffffu);
     for (size_t w = 0; w < n_inputs; ++w) slot[w] = (uint32_t)w;
@@ -127,10 +117,10 @@ inline int tfhe_circuit_compile_any(const fhe_tfhe_node *nodes, size_t n_nodes, 
     size_t max_rows = 0, level_rows = 0;
     for (size_t i = 0, l = 0; i < n_live; ++i) {
         const uint32_t g = source[i];
-        while (i == plan->level_start[l + 1]) { ++l; level_rows = 0; }
+        while (i == L.level_start[l + 1]) { ++l; level_rows = 0; }
         plan->out_start[i] = (uint32_t)plan->extracts.size();
         for (uint32_t w = first_wire[g]; w < first_wire[g + 1]; ++w) {
-            if (!live[w]) continue;
+            if (!L.wire_live[w]) continue;
             slot[w] = (uint32_t)(n_inputs + plan->extracts.size());
             plan->extracts.push_back(TfheExtract{(uint32_t)i, w - first_wire[g]});
             ++level_rows;
@@ -140,7 +130,6 @@ inline int tfhe_circuit_compile_any(const fhe_tfhe_node *nodes, size_t n_nodes, 
     plan->out_start[n_live] = (uint32_t)plan->extracts.size();
     plan->nodes.assign(n_live, fhe_tfhe_node{});
     plan->terms.clear();
-    plan->terms.reserve(live_terms);
     for (size_t i = 0; i < n_live; ++i) {
         const fhe_tfhe_node &nd = nodes[source[i]];
         fhe_tfhe_node &out = plan->nodes[i];
@@ -157,8 +146,10 @@ inline int tfhe_circuit_compile_any(const fhe_tfhe_node *nodes, size_t n_nodes, 
     plan->outputs.resize(n_outputs);
     for (size_t o = 0; o < n_outputs; ++o) plan->outputs[o] = slot[outputs[o]];
     plan->n_inputs = n_inputs; plan->n_nodes = n_nodes; plan->n_outputs = n_outputs; plan->n_tables = n_tables;
-    plan->n_levels = n_levels; plan->n_live = n_live; plan->max_width = max_width;
+    plan->n_levels = L.n_levels; plan->n_live = n_live; plan->max_width = L.max_width;
     plan->many = any_many; plan->n_slots = plan->extracts.size(); plan->max_rows = max_rows;
+    plan->level_of_node = std::move(L.level_of_node);
+    plan->level_start = std::move(L.level_start);
     return FHE_OK;
 }
 

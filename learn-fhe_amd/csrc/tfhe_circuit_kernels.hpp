@@ -2,16 +2,21 @@
 // fhe_tlwe_lincomb launch and two mod-switch launches on, for every node of the level and every ciphertext of the batch in one launch --
 // and the copy of the outputs out of the wire table.
 //
-// Wire table: slot s < n_inputs is the caller's input s (read where it lies), slot n_inputs + i is live node i (level order) in the
-// call's workspace; a slot holds a [batch][n_lwe] and b [batch].  Job m = node * batch + batch index of a level is the unit every later
-// launch of the level (blind rotation .. key switch) sees, so the key switch writes the level's slots as one [width * batch][n_lwe].
+// Wire table: slot s < n_inputs is the caller's input s (read where it lies), slot n_inputs + i is live output i (level order; a node
+// without many-LUT outputs has one) in the call's workspace; a slot holds a [batch][n_lwe] and b [batch].  Job m = node * batch + batch
+// index of a level is the unit the front and the blind rotation see; the extraction turns jobs into rows, one per live output and batch
+// index, so the key switch writes the level's slots as one [rows][n_lwe].
 //
 // Both kernels are element-wise and memory bound.  ONE WAVE owns a job at a time: its node descriptor and term list are the same for all
 // 64 lanes (the job index goes through readfirstlane, so descriptors and terms are scalar loads and the term loop is uniform), and the
 // lanes walk the n_lwe + 1 words of the job (index n_lwe = the b word) with consecutive lanes on consecutive words of every term.
 #pragma once
+#include <algorithm>
+
 #include "arith.hpp"
+#include "dispatch.hpp"  // launch(), with_bool()
 #include "tfhe_circuit.hpp"
+#include "torus_kernels.hpp"  // tglwe_sample_extract_kernel
 
 namespace fhe {
 
@@ -30,21 +35,23 @@ __device__ __forceinline__ const u64 *tfhe_wire_b(const TfheWires &W, unsigned s
     return slot < W.n_inputs ? W.in_b + size_t(slot) * W.batch + bi : W.wt_b + size_t(slot - W.n_inputs) * W.batch + bi;
 }
 
-// Level front.  nodes: the level's descriptors [width] (first_term indexes `terms`, the circuit's whole term list; wire = slot);
-// jobs = width * batch.  Out, per job m: a1 [m][n_lwe], b1 [m] = `mod_switch` (bootstrapping.rs:99-104: rounding_shr by `bits`, the
-// sequence of torus_rounding_shr_kernel) of constant + sum weight * wire mod 2^64 (constant on b only), table_of [m] = the node's table.
+// Level front.  nodes: the level's descriptors [width] (first_term indexes `terms`, the circuit's whole term list; wire = slot;
+// pad = log_funcs of the node, scalar and uniform per wave); jobs = width * batch.  Out, per job m: a1 [m][n_lwe], b1 [m] = `mod_switch`
+// to multiples of 2^log_funcs (torus_rounding_shr_many_kernel below; log_funcs = 0: bootstrapping.rs:99-104, the sequence of
+// torus_rounding_shr_kernel) of constant + sum weight * wire mod 2^64 (constant on b only), table_of [m] = the node's table.
 FHE_HEADER_KERNEL __launch_bounds__(256) void tfhe_circuit_front_kernel(TfheWires W, const fhe_tfhe_node *__restrict__ nodes, const fhe_tfhe_term *__restrict__ terms,
                                                                  unsigned width, int bits, u64 *__restrict__ a1, u64 *__restrict__ b1,
                                                                  unsigned *__restrict__ table_of) {
     const size_t jobs = size_t(width) * W.batch;
     const unsigned lane = threadIdx.x & 63u, waves_per_block = blockDim.x >> 6;
     const size_t first = size_t(blockIdx.x) * waves_per_block + (threadIdx.x >> 6), step = size_t(gridDim.x) * waves_per_block;
-    const u64 half = (u64(1) << bits) >> 1;
     for (size_t job = first; job < jobs; job += step) {
         const unsigned m = __builtin_amdgcn_readfirstlane(unsigned(job));  // jobs < 2^31 (checked by the entry point)
         const unsigned node = m / W.batch, bi = m - node * W.batch;
         const fhe_tfhe_node nd = nodes[node];
         const fhe_tfhe_term *tm = terms + nd.first_term;
+        const int nu = int(nd.pad), sh = bits + nu;  // nu <= 4 (checked by create): sh <= 59
+        const u64 half = (u64(1) << sh) >> 1;
         for (unsigned j = lane; j <= W.n_lwe; j += 64) {
             const bool is_b = j == W.n_lwe;
             u64 acc = is_b ? nd.constant : 0;
@@ -53,7 +60,7 @@ FHE_HEADER_KERNEL __launch_bounds__(256) void tfhe_circuit_front_kernel(TfheWire
                 const u64 x = is_b ? *tfhe_wire_b(W, slot, bi) : tfhe_wire_a(W, slot, bi)[j];
                 acc += u64(int64_t(tm[k].weight)) * x;
             }
-            const u64 sw = (acc + half) >> bits;
+            const u64 sw = ((acc + half) >> sh) << nu;
             if (is_b) b1[m] = sw;
             else a1[size_t(m) * W.n_lwe + j] = sw;
         }
@@ -88,37 +95,6 @@ FHE_HEADER_KERNEL void torus_rounding_shr_many_kernel(const u64 *__restrict__ in
         out[idx] = ((in[idx] + half) >> sh) << nu;
 }
 
-// tfhe_circuit_front_kernel with a shift per node: nodes[].pad = log_funcs of the node (scalar, uniform per wave); the same bits at
-// log_funcs = 0.
-FHE_HEADER_KERNEL __launch_bounds__(256) void tfhe_circuit_front_many_kernel(TfheWires W, const fhe_tfhe_node *__restrict__ nodes,
-                                                                      const fhe_tfhe_term *__restrict__ terms, unsigned width, int bits,
-                                                                      u64 *__restrict__ a1, u64 *__restrict__ b1, unsigned *__restrict__ table_of) {
-    const size_t jobs = size_t(width) * W.batch;
-    const unsigned lane = threadIdx.x & 63u, waves_per_block = blockDim.x >> 6;
-    const size_t first = size_t(blockIdx.x) * waves_per_block + (threadIdx.x >> 6), step = size_t(gridDim.x) * waves_per_block;
-    for (size_t job = first; job < jobs; job += step) {
-        const unsigned m = __builtin_amdgcn_readfirstlane(unsigned(job));  // jobs < 2^31 (checked by the entry point)
-        const unsigned node = m / W.batch, bi = m - node * W.batch;
-        const fhe_tfhe_node nd = nodes[node];
-        const fhe_tfhe_term *tm = terms + nd.first_term;
-        const int nu = int(nd.pad), sh = bits + nu;  // nu <= 4 (checked by create): sh <= 59
-        const u64 half = (u64(1) << sh) >> 1;
-        for (unsigned j = lane; j <= W.n_lwe; j += 64) {
-            const bool is_b = j == W.n_lwe;
-            u64 acc = is_b ? nd.constant : 0;
-            for (unsigned k = 0; k < nd.n_terms; ++k) {
-                const unsigned slot = tm[k].wire;
-                const u64 x = is_b ? *tfhe_wire_b(W, slot, bi) : tfhe_wire_a(W, slot, bi)[j];
-                acc += u64(int64_t(tm[k].weight)) * x;
-            }
-            const u64 sw = ((acc + half) >> sh) << nu;
-            if (is_b) b1[m] = sw;
-            else a1[size_t(m) * W.n_lwe + j] = sw;
-        }
-        if (lane == 0) table_of[m] = nd.table;
-    }
-}
-
 // scheme/tfhe/src/tglwe.rs:115-127 `sample_extract(acc, i)` (k = 1) for SEVERAL i of one accumulator.  Job m = node * batch + bi reads
 // the accumulator acc_a [m][n], acc_b [m][n]; ONE WAVE owns a job: it stages the row a [n] in its own n words of LDS once (16-byte
 // loads) and writes every extraction e of the node from there -- out_a [r][n], out_b [r], r = (e - base) * stride_e + bi * stride_b,
@@ -128,7 +104,7 @@ FHE_HEADER_KERNEL __launch_bounds__(256) void tfhe_circuit_front_many_kernel(Tfh
 //   ext == null: the dense list of one node (width = 1): e = i = 0 .. dense - 1, base = 0
 // n a power of two >= 2; dynamic LDS = waves per block * n * 8 bytes.  The job loop is uniform per BLOCK (every wave of a block makes the
 // same number of trips; a wave past the last job only keeps the barriers).  WIDE: acc_a and out_a are 16-byte aligned (the executor's
-// workspace always is); otherwise the same words go as 8-byte accesses.
+// workspace always is: TfheScratch); otherwise the same words go as 8-byte accesses.
 template <bool WIDE>
 __global__ __launch_bounds__(256) void tglwe_sample_extract_many_kernel(const u64 *__restrict__ acc_a, const u64 *__restrict__ acc_b, unsigned n,
                                                                         unsigned width, unsigned batch, const unsigned *__restrict__ out_start,
@@ -172,6 +148,24 @@ __global__ __launch_bounds__(256) void tglwe_sample_extract_many_kernel(const u6
         }
         __syncthreads();
     }
+}
+
+// Every launch of the kernel above: WAVES rows of n words in LDS per block (n <= 2048, checked by the entry points), a block per WAVES
+// jobs up to a cap, WIDE where acc_a and out_a allow it.  index0: the caller states that every job has ONE extraction, of index 0, into
+// row = job (a circuit level of one-output nodes): the element-wise kernel of fhe_tglwe_sample_extract writes the same rows and is what
+// such levels ran before the executors became one; the measurement rule of DESIGN.md 9.1 kept it for them.
+inline int launch_sample_extract_many(const u64 *acc_a, const u64 *acc_b, size_t n, size_t width, size_t batch, const unsigned *out_start,
+                                      const TfheExtract *ext, size_t base, size_t dense, size_t stride_e, size_t stride_b, u64 *out_a, u64 *out_b,
+                                      hipStream_t st, bool index0 = false) {
+    if (index0) return launch<tglwe_sample_extract_kernel>(grid_for(n * width * batch), 256, 0, st, acc_a, acc_b, (unsigned)n, width * batch, 0u, out_a, out_b);
+    constexpr unsigned WAVES = 4;
+    const unsigned grid = (unsigned)std::min<size_t>((width * batch + WAVES - 1) / WAVES, 8192);
+    const bool wide = ((reinterpret_cast<uintptr_t>(acc_a) | reinterpret_cast<uintptr_t>(out_a)) & 15) == 0;
+    return with_bool(wide, [&](auto w) {
+        return launch<tglwe_sample_extract_many_kernel<decltype(w)::value>>(grid, 64 * WAVES, WAVES * n * sizeof(u64), st, acc_a, acc_b, (unsigned)n,
+                                                                            (unsigned)width, (unsigned)batch, out_start, ext, (unsigned)base,
+                                                                            (unsigned)dense, stride_e, stride_b, out_a, out_b);
+    });
 }
 
 }  // namespace fhe

@@ -640,30 +640,44 @@ int fhe_tlwe_key_switch(int log_b, int d, const uint64_t *ksk_a, const uint64_t 
 
 }  // extern "C"
 namespace {
-// fhe_tfhe_bootstrap (table_of null, n_tables = 1: v [n]) and fhe_tfhe_bootstrap_tables
+// tglwe.rs:115-127 for the dense list of indices 0 .. funcs - 1 on device buffers: acc [batch][n] -> ea [batch][funcs][n], eb [batch][funcs]
+int sample_extract_dense_dev(const u64 *acc_a, const u64 *acc_b, size_t n, size_t funcs, u64 *ea, u64 *eb, size_t batch, hipStream_t st) {
+    return fhe::launch_sample_extract_many(acc_a, acc_b, n, 1, batch, nullptr, nullptr, 0, funcs, 1, funcs, ea, eb, st);
+}
+
+// The body of fhe_tfhe_bootstrap (table_of null, n_tables = 1: v [n]), fhe_tfhe_bootstrap_tables and fhe_tfhe_bootstrap_many: mod switch
+// to multiples of 2^log_funcs, blind rotation, sample_extract(i) for i < 2^log_funcs, key switch of the batch * 2^log_funcs rows.
+// log_funcs = 0 goes through the one-output entries (fhe_tfhe_mod_switch, fhe_tglwe_sample_extract): the same bits, their kernels.
 int bootstrap_any(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, int ks_log_b, int ks_d, const uint64_t *ksk_a, const uint64_t *ksk_b,
-                  const uint64_t *v, size_t n_tables, const uint32_t *table_of, const uint64_t *lwe_a, const uint64_t *lwe_b, uint64_t *out_a,
-                  uint64_t *out_b, size_t batch, fhe_mem mem, void *stream) {
+                  const uint64_t *v, size_t n_tables, const uint32_t *table_of, int log_funcs, const uint64_t *lwe_a, const uint64_t *lwe_b,
+                  uint64_t *out_a, uint64_t *out_b, size_t batch, fhe_mem mem, void *stream) {
     hipStream_t st = (hipStream_t)stream;
     DeviceGuard guard(t->device);
     if (!guard.ok) return FHE_ERR_HIP;
-    const size_t n = size_t(1) << brk->log_n, n_lwe = brk->count, rows = n * ks_d;
+    const size_t n = size_t(1) << brk->log_n, n_lwe = brk->count, rows = n * ks_d, funcs = size_t(1) << log_funcs, outs = batch * funcs;
     TableOf tof(table_of, table_of ? batch : 0, n_tables, table_of ? mem : FHE_MEM_DEVICE, st);
     if (tof.rc != FHE_OK) return tof.rc;
     Mirror mka(ksk_a, rows * n_lwe, mem, true, st), mkb(ksk_b, rows, mem, true, st), mv(v, n_tables * n, mem, true, st),
-        ma(lwe_a, n_lwe * batch, mem, true, st), mb(lwe_b, batch, mem, true, st), moa(out_a, n_lwe * batch, mem, false, st),
-        mob(out_b, batch, mem, false, st);
+        ma(lwe_a, n_lwe * batch, mem, true, st), mb(lwe_b, batch, mem, true, st), moa(out_a, n_lwe * outs, mem, false, st),
+        mob(out_b, outs, mem, false, st);
     if (mka.rc | mkb.rc | mv.rc | ma.rc | mb.rc | moa.rc | mob.rc) return FHE_ERR_HIP;
-    StreamWs ws((batch * n_lwe + batch + 3 * batch * n + batch) * sizeof(u64), st);  // a~ | b~ | acc.a | acc.b | extracted a | b
-    if (ws.rc != FHE_OK) return ws.rc;
-    u64 *at = ws.as<u64>(), *bt = at + batch * n_lwe, *ra = bt + batch, *rb = ra + batch * n, *ea = rb + batch * n, *eb = ea + batch * n;
+    const fhe::TfheScratch L(batch, outs, n, n_lwe, 0, false);
+    StreamWs wsp(L.total * sizeof(u64), st);
+    if (wsp.rc != FHE_OK) return wsp.rc;
+    u64 *ws = wsp.as<u64>(), *ra = ws + L.acc_a, *rb = ws + L.acc_b, *ea = ws + L.ext_a, *eb = ws + L.ext_b, *at = ws + L.at, *bt = ws + L.bt;
     typedef uint64_t U;
-    int rc = fhe_tfhe_mod_switch((const U *)ma.d, (U *)at, batch * n_lwe, n, FHE_MEM_DEVICE, stream);
-    if (rc == FHE_OK) rc = fhe_tfhe_mod_switch((const U *)mb.d, (U *)bt, batch, n, FHE_MEM_DEVICE, stream);
+    auto mod_switch = [&](const u64 *in, u64 *out, size_t count) {
+        return log_funcs ? fhe_tfhe_mod_switch_many((const U *)in, (U *)out, count, n, log_funcs, FHE_MEM_DEVICE, stream)
+                         : fhe_tfhe_mod_switch((const U *)in, (U *)out, count, n, FHE_MEM_DEVICE, stream);
+    };
+    int rc = mod_switch(ma.d, at, batch * n_lwe);
+    if (rc == FHE_OK) rc = mod_switch(mb.d, bt, batch);
     if (rc == FHE_OK) rc = blind_rotate_dev(t, brk, at, bt, mv.d, tof.d, ra, rb, batch, st);
-    if (rc == FHE_OK) rc = fhe_tglwe_sample_extract((const U *)ra, (const U *)rb, n, 0, (U *)ea, (U *)eb, batch, FHE_MEM_DEVICE, stream);
     if (rc == FHE_OK)
-        rc = fhe_tlwe_key_switch(ks_log_b, ks_d, (const U *)mka.d, (const U *)mkb.d, (const U *)ea, (const U *)eb, n, n_lwe, (U *)moa.d, (U *)mob.d, batch,
+        rc = log_funcs ? sample_extract_dense_dev(ra, rb, n, funcs, ea, eb, batch, st)
+                       : fhe_tglwe_sample_extract((const U *)ra, (const U *)rb, n, 0, (U *)ea, (U *)eb, batch, FHE_MEM_DEVICE, stream);
+    if (rc == FHE_OK)
+        rc = fhe_tlwe_key_switch(ks_log_b, ks_d, (const U *)mka.d, (const U *)mkb.d, (const U *)ea, (const U *)eb, n, n_lwe, (U *)moa.d, (U *)mob.d, outs,
                                  FHE_MEM_DEVICE, stream);
     if (rc == FHE_OK) rc = moa.sync_out(st);
     if (rc == FHE_OK) rc = mob.sync_out(st);
@@ -683,7 +697,7 @@ int fhe_tfhe_bootstrap(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, int ks_
     if (rc != FHE_OK) return rc;
     if (!t || !brk || brk->t != t || !ksk_a || !ksk_b || !v || ((!lwe_a || !lwe_b || !out_a || !out_b) && batch)) return FHE_ERR_INVALID;
     if (batch == 0) return FHE_OK;
-    return bootstrap_any(t, brk, ks_log_b, ks_d, ksk_a, ksk_b, v, 1, nullptr, lwe_a, lwe_b, out_a, out_b, batch, mem, stream);
+    return bootstrap_any(t, brk, ks_log_b, ks_d, ksk_a, ksk_b, v, 1, nullptr, 0, lwe_a, lwe_b, out_a, out_b, batch, mem, stream);
 }
 
 // The same through one table per ciphertext (bootstrapping.rs:118-165: a table per function): tables [n_tables][n] encoded, ciphertext i
@@ -697,7 +711,7 @@ int fhe_tfhe_bootstrap_tables(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, 
     if (!t || !brk || brk->t != t || !ksk_a || !ksk_b || !tables || n_tables == 0 || n_tables > MAX_TABLES) return FHE_ERR_INVALID;
     if ((!table_of || !lwe_a || !lwe_b || !out_a || !out_b) && batch) return FHE_ERR_INVALID;
     if (batch == 0) return FHE_OK;
-    return bootstrap_any(t, brk, ks_log_b, ks_d, ksk_a, ksk_b, tables, n_tables, table_of, lwe_a, lwe_b, out_a, out_b, batch, mem, stream);
+    return bootstrap_any(t, brk, ks_log_b, ks_d, ksk_a, ksk_b, tables, n_tables, table_of, 0, lwe_a, lwe_b, out_a, out_b, batch, mem, stream);
 }
 
 // ---- many-LUT bootstrap: 2^log_funcs tables from one blind rotation (bootstrapping.rs:78-128 and tglwe.rs:115-127 composed) ----
@@ -717,25 +731,6 @@ int fhe_tfhe_mod_switch_many(const uint64_t *in, uint64_t *out, size_t count, si
     return mo.sync_out(st);
 }
 
-}  // extern "C"
-namespace {
-// tglwe.rs:115-127 for the dense list of indices 0 .. funcs - 1 on device buffers: acc [batch][n] -> ea [batch][funcs][n], eb [batch][funcs]
-int sample_extract_dense_dev(const u64 *acc_a, const u64 *acc_b, size_t n, unsigned funcs, u64 *ea, u64 *eb, size_t batch, hipStream_t st) {
-    constexpr unsigned WAVES = 4;
-    const unsigned grid = (unsigned)std::min<size_t>((batch + WAVES - 1) / WAVES, 8192);
-    const size_t lds = WAVES * n * sizeof(u64);
-    const bool wide = ((reinterpret_cast<uintptr_t>(acc_a) | reinterpret_cast<uintptr_t>(ea)) & 15) == 0;
-    if (wide)
-        return fhe::launch<fhe::tglwe_sample_extract_many_kernel<true>>(grid, 64 * WAVES, lds, st, acc_a, acc_b, (unsigned)n, 1u, (unsigned)batch,
-                                                                        (const unsigned *)nullptr, (const fhe::TfheExtract *)nullptr, 0u, funcs, size_t(1),
-                                                                        size_t(funcs), ea, eb);
-    return fhe::launch<fhe::tglwe_sample_extract_many_kernel<false>>(grid, 64 * WAVES, lds, st, acc_a, acc_b, (unsigned)n, 1u, (unsigned)batch,
-                                                                     (const unsigned *)nullptr, (const fhe::TfheExtract *)nullptr, 0u, funcs, size_t(1),
-                                                                     size_t(funcs), ea, eb);
-}
-}  // namespace
-extern "C" {
-
 // tglwe.rs:115-127 `sample_extract(ct, i)` for every i < 2^log_funcs, each ciphertext read once: out_a [batch][2^log_funcs][n]
 int fhe_tglwe_sample_extract_many(const uint64_t *ct_a, const uint64_t *ct_b, size_t n, int log_funcs, uint64_t *out_a, uint64_t *out_b, size_t batch,
                                   fhe_mem mem, void *stream) {
@@ -751,7 +746,7 @@ int fhe_tglwe_sample_extract_many(const uint64_t *ct_a, const uint64_t *ct_b, si
     Mirror ma(ct_a, n * batch, mem, true, st), mb(ct_b, n * batch, mem, true, st), moa(out_a, n * funcs * batch, mem, false, st),
         mob(out_b, funcs * batch, mem, false, st);
     if (ma.rc | mb.rc | moa.rc | mob.rc) return FHE_ERR_HIP;
-    FHE_TRY(sample_extract_dense_dev(ma.d, mb.d, n, (unsigned)funcs, moa.d, mob.d, batch, st));
+    FHE_TRY(sample_extract_dense_dev(ma.d, mb.d, n, funcs, moa.d, mob.d, batch, st));
     int rc = moa.sync_out(st);
     return rc != FHE_OK ? rc : mob.sync_out(st);
 }
@@ -770,33 +765,8 @@ int fhe_tfhe_bootstrap_many(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, in
     if ((!table_of || !lwe_a || !lwe_b || !out_a || !out_b) && batch) return FHE_ERR_INVALID;
     if (brk->log_n < 8 || brk->log_n > 11) return FHE_ERR_UNSUPPORTED;  // N = 256 .. 2048
     if (batch == 0) return FHE_OK;
-    const size_t funcs = size_t(1) << log_funcs;
-    if (batch > 0x7fffffffull / funcs) return FHE_ERR_UNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    DeviceGuard guard(t->device);
-    if (!guard.ok) return FHE_ERR_HIP;
-    const size_t n = size_t(1) << brk->log_n, n_lwe = brk->count, rows = n * ks_d, outs = batch * funcs;
-    TableOf tof(table_of, batch, n_tables, mem, st);
-    if (tof.rc != FHE_OK) return tof.rc;
-    Mirror mka(ksk_a, rows * n_lwe, mem, true, st), mkb(ksk_b, rows, mem, true, st), mv(tables, n_tables * n, mem, true, st),
-        ma(lwe_a, n_lwe * batch, mem, true, st), mb(lwe_b, batch, mem, true, st), moa(out_a, n_lwe * outs, mem, false, st),
-        mob(out_b, outs, mem, false, st);
-    if (mka.rc | mkb.rc | mv.rc | ma.rc | mb.rc | moa.rc | mob.rc) return FHE_ERR_HIP;
-    // acc.a | acc.b | extracted a (the [..][n] arrays first: each starts on a 16-byte boundary) | a~ | b~ | extracted b
-    StreamWs ws((2 * batch * n + outs * n + batch * n_lwe + batch + outs) * sizeof(u64), st);
-    if (ws.rc != FHE_OK) return ws.rc;
-    u64 *ra = ws.as<u64>(), *rb = ra + batch * n, *ea = rb + batch * n, *at = ea + outs * n, *bt = at + batch * n_lwe, *eb = bt + batch;
-    typedef uint64_t U;
-    rc = fhe_tfhe_mod_switch_many((const U *)ma.d, (U *)at, batch * n_lwe, n, log_funcs, FHE_MEM_DEVICE, stream);
-    if (rc == FHE_OK) rc = fhe_tfhe_mod_switch_many((const U *)mb.d, (U *)bt, batch, n, log_funcs, FHE_MEM_DEVICE, stream);
-    if (rc == FHE_OK) rc = blind_rotate_dev(t, brk, at, bt, mv.d, tof.d, ra, rb, batch, st);
-    if (rc == FHE_OK) rc = sample_extract_dense_dev(ra, rb, n, (unsigned)funcs, ea, eb, batch, st);
-    if (rc == FHE_OK)
-        rc = fhe_tlwe_key_switch(ks_log_b, ks_d, (const U *)mka.d, (const U *)mkb.d, (const U *)ea, (const U *)eb, n, n_lwe, (U *)moa.d, (U *)mob.d, outs,
-                                 FHE_MEM_DEVICE, stream);
-    if (rc == FHE_OK) rc = moa.sync_out(st);
-    if (rc == FHE_OK) rc = mob.sync_out(st);
-    return rc;
+    if (batch > (0x7fffffffull >> log_funcs)) return FHE_ERR_UNSUPPORTED;
+    return bootstrap_any(t, brk, ks_log_b, ks_d, ksk_a, ksk_b, tables, n_tables, table_of, log_funcs, lwe_a, lwe_b, out_a, out_b, batch, mem, stream);
 }
 
 // scheme/tfhe/src/tlwe.rs:22-75 (Add, Sub, Neg and scalar Mul on `TlweCiphertext`, composed): out = constant + sum_{j < k} weight[j] * ct_j

@@ -135,6 +135,31 @@ def test_bootstrap_many_equals_the_composition(fhe, torch_cuda, n, log_b, d, n_l
     assert e.value.code == 1
 
 
+@pytest.mark.parametrize("n,log_b,d,n_lwe", KEY_FORMS)
+def test_bootstrap_many_nu0_equals_bootstrap_tables(fhe, torch_cuda, n, log_b, d, n_lwe):
+    """log_funcs = 0 is the one-table bootstrap: batch 5, two tables assigned unevenly, random key rows: fhe_tfhe_bootstrap_many bit-equal
+    to fhe_tfhe_bootstrap_tables (one composition serves both entries); exact and fft64 on device memory, host memory for the first
+    key form"""
+    batch, ks_log_b, ks_d = 5, 4, 5
+    rng = np.random.Generator(np.random.PCG64(5250 + log_b + n))
+    bra, brb, tables = r64(rng, n_lwe, 2 * d, n), r64(rng, n_lwe, 2 * d, n), r64(rng, 2, n)
+    a_raw, b_raw = r64(rng, batch, n_lwe), r64(rng, batch)
+    ksa, ksb = r64(rng, n * ks_d, n_lwe), r64(rng, n * ks_d)
+    table_of = np.array([0, 1, 1, 0, 1], dtype=np.uint32)
+    t = fhe.TorusContext()
+    D = lambda x: dev(torch_cuda, x)  # noqa: E731
+    dksa, dksb, dtab, da, db, dtof = D(ksa), D(ksb), D(tables), D(a_raw), D(b_raw), dev32(torch_cuda, table_of)
+    for fft64 in (False, True):
+        key = fhe.TggswKey(t, log_b, d, D(bra), D(brb), n, fft64=fft64)
+        ga, gb = key.bootstrap_many(ks_log_b, ks_d, dksa, dksb, dtab, dtof, 0, da, db)
+        assert tuple(ga.shape) == (batch, 1, n_lwe) and tuple(gb.shape) == (batch, 1)
+        wa, wb = key.bootstrap_tables(ks_log_b, ks_d, dksa, dksb, dtab, dtof, da, db)
+        assert torch_cuda.equal(ga.reshape(batch, n_lwe), wa.reshape(batch, n_lwe)) and torch_cuda.equal(gb.reshape(batch), wb.reshape(batch)), fft64
+        if not fft64 and (n, log_b, d, n_lwe) == KEY_FORMS[0]:
+            ha, hb = key.bootstrap_many(ks_log_b, ks_d, ksa, ksb, tables, table_of, 0, a_raw, b_raw)
+            assert np.array_equal(ha.reshape(batch, n_lwe), host(wa).reshape(batch, n_lwe)) and np.array_equal(hb.reshape(batch), host(wb).reshape(batch))
+
+
 def test_bootstrap_many_equals_pyref_piece_by_piece(fhe, torch_cuda):
     """n = 256, n_lwe = 6, gadget (15, 1): oracle.pyref composed -- tfhe_mod_switch for n >> nu shifted left, tfhe_blind_rotate on the
     ciphertext's table, tglwe_sample_extract(i), tlwe_key_switch"""

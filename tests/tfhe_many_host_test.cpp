@@ -1,7 +1,9 @@
 // Stand-alone host program over learn-fhe_amd/csrc/tfhe_circuit.hpp (no HIP): tfhe_circuit_compile_many, the netlist compiler of
 // fhe_tfhe_circuit_create_many.  With every log_funcs == 0 its plan equals tfhe_circuit_compile's field by field (the hand-made netlist,
 // the radix adder, random netlists); with mixed log_funcs in {0, 1, 2} the wire numbering, the liveness per output, the levels through
-// many-LUT nodes, the slot order and the extraction descriptors against a restatement; the rejected cases.
+// many-LUT nodes, the slot order and the extraction descriptors against a restatement; the rejected cases.  And TfheScratch, the one
+// layout of the bootstrap compositions' workspace: its arrays tile the total, the [..][n] arrays start on even words, the circuit
+// bootstrap's total is cbs_workspace's (learn-fhe_amd/csrc/tfhe_cbs.hpp).
 // Built with -fsanitize=address,undefined.
 #include <algorithm>
 #include <cstdio>
@@ -9,6 +11,7 @@
 #include <functional>
 #include <vector>
 
+#include "../learn-fhe_amd/csrc/tfhe_cbs.hpp"
 #include "../learn-fhe_amd/csrc/tfhe_circuit.hpp"
 
 static uint64_t state = 0x243f6a8885a308d3ull;
@@ -319,8 +322,40 @@ static int rejected() {
     return 0;
 }
 
+// one layout: the arrays in the order of their offsets, each with the words it holds
+static int tiles(const fhe::TfheScratch &L, size_t jobs, size_t rows, size_t n, size_t n_lwe, size_t wt_rows, bool table) {
+    const size_t off[9] = {L.acc_a, L.acc_b, L.ext_a, L.wt_a, L.at, L.wt_b, L.bt, L.ext_b, L.table_of};
+    const size_t words[9] = {jobs * n, jobs * n, rows * n, wt_rows * n_lwe, jobs * n_lwe, wt_rows, jobs, rows, table ? (jobs + 1) / 2 : 0};
+    size_t at = 0;
+    for (int i = 0; i < 9; ++i) {
+        REQUIRE(off[i] == at);  // no gap, no overlap
+        at += words[i];
+    }
+    REQUIRE(L.total == at);
+    REQUIRE(L.acc_a % 2 == 0 && L.acc_b % 2 == 0 && L.ext_a % 2 == 0);  // 16-byte accesses on the [..][n] arrays
+    return 0;
+}
+
+static int scratch_layout() {
+    for (size_t n : {256, 2048})
+        for (size_t n_lwe : {1, 6, 630})
+            for (size_t batch : {1, 5}) {
+                for (int cb_d : {1, 3, 16}) {
+                    // the circuit bootstrap, and a many-LUT bootstrap of as many functions (they share the shape)
+                    const fhe::TfheScratch L = fhe::cbs_scratch(n, n_lwe, cb_d, batch);
+                    if (tiles(L, batch, batch * cb_d, n, n_lwe, 0, false)) return 1;
+                    const size_t stated = 2 * batch * n + batch * size_t(cb_d) * n + batch * n_lwe + batch + batch * size_t(cb_d);
+                    REQUIRE(L.total == stated && fhe::cbs_workspace(n, n_lwe, cb_d, batch) == stated);
+                }
+                // a circuit: width 3, 7 live outputs in its widest level, 11 in all; and the plain bootstrap
+                if (tiles(fhe::TfheScratch(3 * batch, 7 * batch, n, n_lwe, 11 * batch, true), 3 * batch, 7 * batch, n, n_lwe, 11 * batch, true)) return 1;
+                if (tiles(fhe::TfheScratch(batch, batch, n, n_lwe, 0, false), batch, batch, n, n_lwe, 0, false)) return 1;
+            }
+    return 0;
+}
+
 int main() {
-    if (nu0_equals_the_existing_compiler() || wires_and_liveness() || rejected()) return 1;
+    if (nu0_equals_the_existing_compiler() || wires_and_liveness() || rejected() || scratch_layout()) return 1;
     for (int it = 0; it < 300; ++it)
         if (mixed(1 + rnd(6), rnd(60), 1 + rnd(5), 1 + rnd(4))) return 1;
     if (mixed(3, 2000, 4, 9)) return 1;
