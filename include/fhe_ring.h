@@ -60,7 +60,8 @@ int fhe_trim(void);
  * batch x value <= compute units of the device -- and one workgroup per ciphertext elsewhere; any other value: FHE_ERR_INVALID;
  * fhe_blind_rotate_split tells what a call will run), "PFKS_SPLIT" (fhe_tlwe_pfks: 0 = the library's rule, 1 = one block walks all
  * input rows of its tile, k >= 2 = k blocks share them and add their partial sums), "PFKS_CHUNK" (fhe_tlwe_pfks: input coefficients whose digits a block
- * keeps in LDS at a time; 0 = the library's rule).  Unknown name: FHE_ERR_INVALID. */
+ * keeps in LDS at a time; 0 = the library's rule), "LUT_EXTRACT" (fhe_tfhe_lut_eval: 0 = the library's rule, 1 = the rotation ladder writes the
+ * extractions from its registers, 2 = a kernel of its own reads the stored accumulators).  Unknown name: FHE_ERR_INVALID. */
 int fhe_set_option(const char *name, long value);
 
 /* Entry points that take a modulus instead of a context (fhe_rq_*, fhe_decompose, fhe_automorphism, fhe_monomial_mul,
@@ -974,6 +975,35 @@ int fhe_tfhe_cbs_workspace(size_t n, size_t n_lwe, int cb_d, size_t batch, size_
 int fhe_tfhe_circuit_bootstrap(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, int cb_log_b, int cb_d, int pf_log_b, int pf_d,
                                const uint64_t *pfksk, const uint64_t *lwe_a, const uint64_t *lwe_b, uint64_t *rows_a, uint64_t *rows_b,
                                size_t batch, fhe_mem mem, void *stream);
+
+/* ---- Encrypted table look-up with vertical packing (k = 1), every ciphertext under its own selectors ---------------------------------
+ * A plaintext table T[o][x] of torus words, o < n_out outputs and x < 2^m addresses, shared by the batch, is read by ciphertext c under
+ * the m TGGSW selectors of a prepared key at index first_index + c m + l, l = 0 the least significant address bit: the layout that
+ * fhe_tfhe_circuit_bootstrap on bits ordered [c][l] followed by fhe_tggsw_prepare / _prepare_fft64 with count = batch m produces.
+ *
+ * Shape.  r = min(m, log2 n) address bits rotate a packed polynomial, h = m - r go to a CMUX tree; per_acc = max(1, n / 2^m) outputs
+ * share one accumulator, n_acc = ceil(n_out / per_acc) accumulators, n_polys = n_acc 2^h polynomials.  Any output pointer may be NULL.
+ * m < 1, n_out < 1, n no power of two: FHE_ERR_INVALID; n outside 256 .. 2048, h > 10, n_polys > 65536: FHE_ERR_UNSUPPORTED. */
+int fhe_tfhe_lut_shape(int m, size_t n_out, size_t n, int *r, size_t *per_acc, size_t *n_acc, size_t *n_polys);
+/* Packing, host memory only.  table [n_out][2^m] -> polys [n_acc][2^h][n]: polynomial (g, t) holds T[g per_acc + u][t 2^r + i] at
+ * coefficient u 2^m + i, every other coefficient is 0.  Status as fhe_tfhe_lut_shape; a NULL pointer: FHE_ERR_INVALID. */
+int fhe_tfhe_lut_pack(const uint64_t *table, int m, size_t n_out, size_t n, uint64_t *polys);
+/* Stream-ordered scratch of fhe_tfhe_lut_eval in 64-bit words; n_lwe_out = 0: no key switch.  Status as fhe_tfhe_lut_shape; a batch whose
+ * launches would pass 2^31 - 1 teams: FHE_ERR_UNSUPPORTED. */
+int fhe_tfhe_lut_workspace(size_t n, int m, size_t n_out, size_t n_lwe_out, size_t batch, size_t *words);
+/* The look-up in one call, all on `stream`.  Per ciphertext c and accumulator g: (1) tree level v = 0 .. h - 1 applies CMUX(selector r + v;
+ * even, odd) (tggsw.rs:114-121) to neighbouring polynomials, starting from the trivial ciphertexts (0, polys[g][t]); (2) for l = 0 ..
+ * r - 1, acc <- CMUX(selector l; acc, acc X^(-2^l)) (the rotation of fhe_tglwe_rotate with i = -2^l): coefficient u 2^m of the phase
+ * is then T[g per_acc + u][address]; (3) sample_extract at u 2^m (tglwe.rs:115-127) for every output; (4) when ksk_a is not NULL,
+ * fhe_tlwe_key_switch with (ks_log_b, ks_d, ksk_a, ksk_b) from n to n_lwe_out (tlwe.rs:144-153).  polys: fhe_tfhe_lut_pack's, where
+ * the outputs live.  out_a [batch][n_out][n_lwe_out] ([batch][n_out][n] without key switch), out_b [batch][n_out].  Bit-identical per
+ * ciphertext to fhe_tggsw_cmux with that ciphertext's index, fhe_tglwe_rotate, fhe_tglwe_sample_extract and fhe_tlwe_key_switch chained,
+ * in every exact key form (fft64: on the same device).  The depth is m CMUXes, as for a tree over all m bits.
+ * first_index + batch m > the key's count, a key of another context, ksk_b without ksk_a (or the reverse), out_a == out_b, and
+ * FHE_MEM_DEVICE calls whose out_a or out_b equals polys, ksk_a or ksk_b: FHE_ERR_INVALID; shapes as fhe_tfhe_lut_shape. */
+int fhe_tfhe_lut_eval(const fhe_torus_ctx *t, const fhe_tggsw_key *sel_key, size_t first_index, int m, const uint64_t *polys, size_t n_out,
+                      int ks_log_b, int ks_d, const uint64_t *ksk_a, const uint64_t *ksk_b, size_t n_lwe_out, uint64_t *out_a, uint64_t *out_b,
+                      size_t batch, fhe_mem mem, void *stream);
 
 #ifdef __cplusplus
 }

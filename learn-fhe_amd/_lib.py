@@ -143,6 +143,11 @@ def lib():
         L.fhe_tfhe_cbs_table.argtypes = [ci, ci, sz, u64p]
         L.fhe_tfhe_cbs_workspace.argtypes = [sz, sz, ci, sz, C.POINTER(sz)]
         L.fhe_tfhe_circuit_bootstrap.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, sz, ci, vp]
+        # encrypted table look-up with vertical packing (tfhe_lut_api.hip)
+        L.fhe_tfhe_lut_shape.argtypes = [ci, sz, sz, C.POINTER(ci), C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
+        L.fhe_tfhe_lut_pack.argtypes = [u64p, ci, sz, sz, u64p]
+        L.fhe_tfhe_lut_workspace.argtypes = [sz, ci, sz, sz, sz, C.POINTER(sz)]
+        L.fhe_tfhe_lut_eval.argtypes = [vp, vp, sz, ci, vp, sz, ci, ci, vp, vp, sz, vp, vp, sz, ci, vp]
         L.fhe_torus_ctx_create.argtypes = [ci, C.POINTER(vp)]
         L.fhe_torus_ctx_destroy.argtypes = [vp]
         L.fhe_torus_ctx_destroy.restype = None

@@ -111,10 +111,12 @@ namespace fhe {
 // PFKS_SPLIT: blocks that share the input rows of one output tile of fhe_tlwe_pfks (pfks_kernels.hpp): 0 the library's rule, 1 never split,
 // k >= 2: k blocks where the rows allow it.  PFKS_CHUNK: input coefficients whose digits a block keeps in LDS at a time: 0 the library's
 // rule, c >= 1: at most c.
+// LUT_EXTRACT: who writes the extractions of fhe_tfhe_lut_eval: 0 the library's rule, 1 the rotation ladder from its registers, 2 a kernel
+// of its own that reads the stored accumulators (tfhe_lut_kernels.hpp).
 enum Opt { OPT_NO_EDGE = 0, OPT_NO_LIMB_MAJOR, OPT_NO_W12, OPT_NO_FUSED_MUL, OPT_SMALL_BATCH, OPT_NO_PACKED_DIGITS, OPT_NO_F64_EXACT, OPT_FHEW_COMPOSED,
-           OPT_BR_SPLIT, OPT_PFKS_SPLIT, OPT_PFKS_CHUNK, OPT_COUNT };
+           OPT_BR_SPLIT, OPT_PFKS_SPLIT, OPT_PFKS_CHUNK, OPT_LUT_EXTRACT, OPT_COUNT };
 inline const char *const OPT_NAMES[OPT_COUNT] = {"NO_EDGE", "NO_LIMB_MAJOR", "NO_W12", "NO_FUSED_MUL", "SMALL_BATCH", "NO_PACKED_DIGITS", "NO_F64_EXACT",
-                                                 "FHEW_COMPOSED", "BR_SPLIT", "PFKS_SPLIT", "PFKS_CHUNK"};
+                                                 "FHEW_COMPOSED", "BR_SPLIT", "PFKS_SPLIT", "PFKS_CHUNK", "LUT_EXTRACT"};
 inline bool br_split_value_ok(long v) { return v == -1 || v == 0 || v == 2 || v == 4 || v == 8; }
 struct Options {
     std::atomic<long> v[OPT_COUNT];

@@ -7,6 +7,9 @@ fhe_tggsw_cmux (tggsw.rs:114-121), so that a table of 2^m plaintext entries is r
   circuit_bootstrap  TLWE bits -> TGGSW rows in one call (fhe_tfhe_circuit_bootstrap), and circuit_bootstrap_steps: the public entries
                      chained by hand
   lut_eval           the CMUX tree over trivial TGLWE ciphertexts, one fhe_tggsw_cmux call per level; lut_eval_plain: its plain values
+  lut_shape, lut_pack, lut_eval_batch
+                     vertical packing: a table of n_out x 2^m words as packed polynomials, read by a whole batch in one call
+                     (fhe_tfhe_lut_eval), every ciphertext under its own m selectors; lut_eval_batch_steps: the public entries chained
 """
 from __future__ import annotations
 
@@ -128,3 +131,84 @@ def lut_eval(table_polys, selector_key: TggswKey, first_index, m):
 def lut_eval_plain(table, bits):
     """the plain value of the tree: table[sum bits[l] << l]"""
     return table[sum(int(b) << l for l, b in enumerate(bits))]
+
+
+def lut_shape(m, n_out, n):
+    """fhe_tfhe_lut_shape -> (r, per_acc, n_acc, n_polys): r = min(m, log2 n) address bits rotate, m - r go to a tree; per_acc outputs
+    share one of n_acc accumulators; n_polys = n_acc 2^(m - r) packed polynomials"""
+    r, per_acc, n_acc, n_polys = C.c_int(), C.c_size_t(), C.c_size_t(), C.c_size_t()
+    L.check(L.lib().fhe_tfhe_lut_shape(m, n_out, n, C.byref(r), C.byref(per_acc), C.byref(n_acc), C.byref(n_polys)), "fhe_tfhe_lut_shape")
+    return r.value, per_acc.value, n_acc.value, n_polys.value
+
+
+def lut_pack(table, m, n):
+    """fhe_tfhe_lut_pack (host): table [n_out][2^m] uint64 torus words -> polys [n_acc][2^(m - r)][n]: polynomial (g, t) holds
+    table[g per_acc + u][t 2^r + i] at coefficient u 2^m + i"""
+    table = np.ascontiguousarray(table, dtype=np.uint64)
+    n_out = table.size >> m
+    assert table.size == n_out << m, "n_out rows of 2^m words"
+    r, _, n_acc, n_polys = lut_shape(m, n_out, n)
+    polys = np.empty((n_acc, 1 << (m - r), n), dtype=np.uint64)
+    L.check(L.lib().fhe_tfhe_lut_pack(table.ctypes.data_as(L.u64p), m, n_out, n, polys.ctypes.data_as(L.u64p)), "fhe_tfhe_lut_pack")
+    return polys
+
+
+def lut_workspace(n, m, n_out, n_lwe_out, batch):
+    words = C.c_size_t()
+    L.check(L.lib().fhe_tfhe_lut_workspace(n, m, n_out, n_lwe_out, batch, C.byref(words)), "fhe_tfhe_lut_workspace")
+    return words.value
+
+
+def lut_eval_batch(polys, selector_key: TggswKey, first_index, m, n_out, batch, ks=None):
+    """fhe_tfhe_lut_eval: ciphertext c reads the packed table `polys` (lut_pack, where the key lives) under the selectors
+    first_index + c m + l of selector_key.  ks = (log_b, d, ksk_a, ksk_b, n_lwe_out) adds the TLWE key switch.
+    -> (a [batch][n_out][n_lwe_out or n], b [batch][n_out])"""
+    pp, _, mem, st = _buf(polys)
+    n = selector_key.n
+    width = ks[4] if ks else n
+    out_a, out_b = _like(polys, (batch, n_out, width)), _like(polys, (batch, n_out))
+    log_b, d, pka, pkb = (ks[0], ks[1], _buf(ks[2])[0], _buf(ks[3])[0]) if ks else (0, 0, None, None)
+    L.check(L.lib().fhe_tfhe_lut_eval(selector_key.t.handle, selector_key._h, first_index, m, pp, n_out, log_b, d, pka, pkb, ks[4] if ks else 0,
+                                      _buf(out_a)[0], _buf(out_b)[0], batch, mem, st), "fhe_tfhe_lut_eval")
+    return out_a, out_b
+
+
+def lut_eval_batch_steps(polys, selector_key: TggswKey, first_index, m, n_out, batch, ks=None):
+    """The same through the public entries, ciphertext by ciphertext: fhe_tggsw_cmux with index first_index + c m + l on that
+    ciphertext's nodes (tree levels, then the rotation steps with fhe_tglwe_rotate by -2^l), fhe_tglwe_sample_extract at u 2^m,
+    fhe_tlwe_key_switch"""
+    from .ring import tglwe_rotate, tlwe_key_switch
+    n = selector_key.n
+    r, per_acc, n_acc, n_polys = lut_shape(m, n_out, n)
+    h = m - r
+    torch_like = _is_torch(polys)
+    cont = (lambda x: x.contiguous()) if torch_like else np.ascontiguousarray
+    if torch_like:
+        import torch
+        stack = torch.stack
+    else:
+        stack = np.stack
+    zeros = _like(polys, (n_polys, n))
+    if torch_like:
+        zeros.zero_()
+    else:
+        zeros[:] = 0
+    res_a, res_b = [], []
+    for c in range(batch):
+        base = first_index + c * m
+        cur_a, cur_b = zeros, polys.reshape(n_polys, n)
+        for v in range(h):
+            pa, pb = cur_a.reshape(-1, 2, n), cur_b.reshape(-1, 2, n)
+            cur_a, cur_b = selector_key.cmux(base + r + v, cont(pa[:, 0]), cont(pb[:, 0]), cont(pa[:, 1]), cont(pb[:, 1]))
+        cur_a, cur_b = cont(cur_a.reshape(n_acc, n)), cont(cur_b.reshape(n_acc, n))
+        for l in range(r):
+            ra, rb = tglwe_rotate(cur_a, cur_b, n, -(1 << l))
+            cur_a, cur_b = selector_key.cmux(base + l, cur_a, cur_b, ra, rb)
+        per_u = [tglwe_sample_extract(cur_a, cur_b, n, u << m) for u in range(min(per_acc, n_out))]
+        ea = stack([per_u[o % per_acc][0][o // per_acc] for o in range(n_out)])
+        eb = stack([per_u[o % per_acc][1][o // per_acc] for o in range(n_out)])
+        if ks:
+            ea, eb = tlwe_key_switch(ks[0], ks[1], ks[2], ks[3], cont(ea), cont(eb), n, ks[4])
+        res_a.append(ea)
+        res_b.append(eb)
+    return stack(res_a), stack(res_b)
