@@ -327,6 +327,18 @@ void fhe_tggsw_key_destroy(fhe_tggsw_key *key);
  * results agree.  The exact mode (fhe_tggsw_prepare) stays the default and the parity checker. */
 int fhe_tggsw_prepare_fft64(const fhe_torus_ctx *t, int log_b, int d, const uint64_t *rows_a, const uint64_t *rows_b, size_t n, size_t count,
                             fhe_mem mem, fhe_tggsw_key **out);
+/* A key of capacity `count` for ciphertexts that are fresh in every call (CMUX selectors out of a circuit bootstrap), where
+ * fhe_tggsw_prepare's allocation, copy, null stream and host wait per call would be in the way.  The form is the one fhe_tggsw_prepare
+ * chooses for (log_b, d, n), or with fft64 != 0 the one of fhe_tggsw_prepare_fft64; the contents are undefined until filled.  Status
+ * as those entries. */
+int fhe_tggsw_key_reserve(const fhe_torus_ctx *t, int log_b, int d, size_t n, size_t count, int fft64, fhe_tggsw_key **out);
+/* Transforms `count` ciphertexts, rows_a / rows_b [count][2d][n] of the key's ring and gadget, into the slots first_index ..
+ * first_index + count - 1 of `key`, on `stream`.  FHE_MEM_DEVICE calls neither allocate with hipMalloc nor wait on the host (scratch is
+ * stream ordered).  Afterwards every entry that takes the key gives, for the filled indices, the bits it gives under fhe_tggsw_prepare /
+ * _prepare_fft64 of the same rows.  The caller orders the fill against work on OTHER streams that still reads those slots.
+ * first_index + count beyond the key's capacity, a NULL key, NULL rows with count > 0: FHE_ERR_INVALID. */
+int fhe_tggsw_key_fill(fhe_tggsw_key *key, size_t first_index, const uint64_t *rows_a, const uint64_t *rows_b, size_t count, fhe_mem mem,
+                       void *stream);
 /* scheme/tfhe/src/tggsw.rs:100-112 `Tggsw::external_product(param, key[index], ct)`, in place on [batch][n] a / b. */
 int fhe_tggsw_external_product(const fhe_torus_ctx *t, const fhe_tggsw_key *key, size_t index, uint64_t *ct_a, uint64_t *ct_b,
                                size_t batch, fhe_mem mem, void *stream);
@@ -1004,6 +1016,59 @@ int fhe_tfhe_lut_workspace(size_t n, int m, size_t n_out, size_t n_lwe_out, size
 int fhe_tfhe_lut_eval(const fhe_torus_ctx *t, const fhe_tggsw_key *sel_key, size_t first_index, int m, const uint64_t *polys, size_t n_out,
                       int ks_log_b, int ks_d, const uint64_t *ksk_a, const uint64_t *ksk_b, size_t n_lwe_out, uint64_t *out_a, uint64_t *out_b,
                       size_t batch, fhe_mem mem, void *stream);
+
+/* ---- Look-up without a padding bit (k = 1): an m-bit TLWE message -> its bits as selectors -> T[message] ----------------------------------
+ * Input: TLWE ciphertexts under the key brk encrypts (dimension n_lwe) with phase x << (64 - m) + noise, 0 <= x < 2^m, NO padding bit;
+ * bit l of x stands at delta_l = 64 - m + l.  nu = ceil(log2(cb_d + 1)); h_j = g_j / 2 for j < cb_d (g_j of the circuit bootstrap's
+ * gadget), h_{cb_d} = 2^(delta_l - 1).  Steps l = 0 .. m - 1, all on `stream`, each after the one before:
+ *   (1) rem_l = rem_{l-1} - corr_{l-1} (rem_0 = the input);  (2) s = rem_l 2^(m-1-l) over Z/2^64, + 2^62 on b (fhe_tlwe_lincomb): phase
+ *   bit_l 2^63 + 2^62 + shifted noise;  (3) fhe_tfhe_mod_switch_many with nu;  (4) ONE fhe_tfhe_blind_rotate of fhe_tfhe_wop_table,
+ *   P[c] = -h_{c mod 2^nu}: extraction j has phase -h_j for bit 0, +h_j for bit 1;  (5) fhe_tglwe_sample_extract(j) for j <= cb_d
+ *   (j < cb_d in the last step) and h_j added to b: phase bit_l 2 h_j, that is bit_l g_j and bit_l 2^delta_l;  (6) except in the last
+ *   step, fhe_tlwe_key_switch (ks_log_b, ks_d, ksk: n -> n_lwe) of row cb_d gives corr_l.
+ * Then fhe_tlwe_pfks with group = cb_d over the batch m cb_d level rows in the order [c][l][j], under the circuit bootstrap's
+ * two-function key: the TGGSW rows of batch m selectors in the order [c][l], l = 0 the least significant bit, which fhe_tfhe_lut_eval reads.
+ * One blind rotation per bit serves every level of the selector AND the correction.
+ *
+ * The caller's conditions: the input noise times 2^(m-1) plus the mod-switch drift of 2^nu (n_lwe + 1) / 2 positions of the 2n stays
+ * inside a quarter of the ring (n / 2 positions); cb_log_b cb_d <= 63, so that g_0 / 2 exists; m <= 16.  For cb_d a power of two nu is one
+ * larger than fhe_tfhe_circuit_bootstrap's, and the drift twice as large.  (cb_d = 16 gives nu = 5, which fhe_tfhe_mod_switch_many itself does
+ * not admit; these entries compute its formula.)
+ *
+ * The test polynomial of the step whose bit stands at log_delta, 1 <= log_delta <= 63; log_delta < 0: the last step's, without the
+ * correction function.  out [n], host memory.  cb_d outside 1 .. 16, cb_log_b cb_d > 63, n/4 no multiple of 2^nu, log_delta = 0 or > 63:
+ * FHE_ERR_INVALID; n outside 256 .. 2048: FHE_ERR_UNSUPPORTED. */
+int fhe_tfhe_wop_table(int cb_log_b, int cb_d, size_t n, int log_delta, uint64_t *out);
+/* Stream-ordered scratch of fhe_tfhe_wop_selectors in 64-bit words (fhe_tfhe_wop_pbs adds the selectors' rows, 4 batch m cb_d n words, and
+ * then what fhe_tggsw_key_fill and fhe_tfhe_lut_eval take).  m < 1, n_lwe = 0, cb_d outside 1 .. 16, n/4 no multiple of 2^nu:
+ * FHE_ERR_INVALID; m > 16, n outside 256 .. 2048: FHE_ERR_UNSUPPORTED. */
+int fhe_tfhe_wop_workspace(size_t n, size_t n_lwe, int m, int cb_d, size_t batch, size_t *words);
+/* The front of one step on its own, one pass over the batch (n_lwe + 1) words: rem = src - cor (cor_a, cor_b both NULL: rem = src),
+ * s = rem 2^shift over Z/2^64 with 2^62 added to b, (at, bt) = fhe_tfhe_mod_switch_many(s) for the ring n with log_funcs = nu.  What
+ * fhe_tlwe_lincomb {1, -1}, fhe_tlwe_lincomb {2^shift} + 2^62 and two fhe_tfhe_mod_switch_many calls compute, the same bits.  src, cor,
+ * rem, at [batch][n_lwe] / [batch]; rem may be src (in place).  nu outside 0 .. 5 or above log2 n, shift outside 0 .. 63, cor_a without
+ * cor_b, outputs equal to each other: FHE_ERR_INVALID. */
+int fhe_tfhe_wop_front(const uint64_t *src_a, const uint64_t *src_b, const uint64_t *cor_a, const uint64_t *cor_b, size_t n_lwe, size_t batch,
+                       size_t n, int nu, int shift, uint64_t *rem_a, uint64_t *rem_b, uint64_t *at, uint64_t *bt, fhe_mem mem, void *stream);
+/* The bits as selectors.  lwe_a [batch][n_lwe], lwe_b [batch]; rows_a, rows_b [batch][m][2 cb_d][n]: the rows of batch m TGGSW
+ * ciphertexts, ready for fhe_tggsw_key_fill / fhe_tggsw_prepare with count = batch m.  rem_a [batch][n_lwe], rem_b [batch]: both NULL,
+ * or rem_{m-1}, the remainder after the last correction that exists, in which the top bit is still present.  ksk is read only for m > 1.
+ * Bit-identical to the public entries named above chained, in every exact key form (fft64: on the same device).  Rejections as
+ * fhe_tfhe_wop_table with m as fhe_tfhe_wop_workspace; outputs that are equal to each other, and FHE_MEM_DEVICE calls with an output
+ * equal to lwe_a, lwe_b, ksk_a, ksk_b or pfksk: FHE_ERR_INVALID. */
+int fhe_tfhe_wop_selectors(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, int ks_log_b, int ks_d, const uint64_t *ksk_a, const uint64_t *ksk_b,
+                           int cb_log_b, int cb_d, int pf_log_b, int pf_d, const uint64_t *pfksk, int m, const uint64_t *lwe_a, const uint64_t *lwe_b,
+                           uint64_t *rows_a, uint64_t *rows_b, uint64_t *rem_a, uint64_t *rem_b, size_t batch, fhe_mem mem, void *stream);
+/* T[message] in one call, all on `stream`: the selectors as above, fhe_tggsw_key_fill into sel_key at first_index (a key of
+ * fhe_tggsw_key_reserve with the gadget (cb_log_b, cb_d), brk's ring and a capacity >= first_index + batch m), then fhe_tfhe_lut_eval of
+ * polys (fhe_tfhe_lut_pack's) with its optional output key switch (out_ks_log_b, out_ks_d, out_ksk_a, out_ksk_b, n_lwe_out; both
+ * pointers NULL: none).  Table words T[x] << (64 - m') give an output of the input's format, so calls compose.  Bit-identical to
+ * fhe_tfhe_wop_selectors, fhe_tggsw_key_fill and fhe_tfhe_lut_eval chained.  Further rejections: a sel_key of another context, ring or
+ * gadget, or sel_key == brk; those of fhe_tfhe_lut_eval. */
+int fhe_tfhe_wop_pbs(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, int ks_log_b, int ks_d, const uint64_t *ksk_a, const uint64_t *ksk_b, int cb_log_b,
+                     int cb_d, int pf_log_b, int pf_d, const uint64_t *pfksk, int m, const uint64_t *lwe_a, const uint64_t *lwe_b, fhe_tggsw_key *sel_key,
+                     size_t first_index, const uint64_t *polys, size_t n_out, int out_ks_log_b, int out_ks_d, const uint64_t *out_ksk_a,
+                     const uint64_t *out_ksk_b, size_t n_lwe_out, uint64_t *out_a, uint64_t *out_b, size_t batch, fhe_mem mem, void *stream);
 
 #ifdef __cplusplus
 }

@@ -148,6 +148,14 @@ def lib():
         L.fhe_tfhe_lut_pack.argtypes = [u64p, ci, sz, sz, u64p]
         L.fhe_tfhe_lut_workspace.argtypes = [sz, ci, sz, sz, sz, C.POINTER(sz)]
         L.fhe_tfhe_lut_eval.argtypes = [vp, vp, sz, ci, vp, sz, ci, ci, vp, vp, sz, vp, vp, sz, ci, vp]
+        # look-up without a padding bit (tfhe_wop_api.hip) and reusable selector keys (torus_api.hip)
+        L.fhe_tfhe_wop_table.argtypes = [ci, ci, sz, ci, u64p]
+        L.fhe_tfhe_wop_workspace.argtypes = [sz, sz, ci, ci, sz, C.POINTER(sz)]
+        L.fhe_tfhe_wop_front.argtypes = [vp, vp, vp, vp, sz, sz, sz, ci, ci, vp, vp, vp, vp, ci, vp]
+        L.fhe_tfhe_wop_selectors.argtypes = [vp, vp, ci, ci, vp, vp, ci, ci, ci, ci, vp, ci, vp, vp, vp, vp, vp, vp, sz, ci, vp]
+        L.fhe_tfhe_wop_pbs.argtypes = [vp, vp, ci, ci, vp, vp, ci, ci, ci, ci, vp, ci, vp, vp, vp, sz, vp, sz, ci, ci, vp, vp, sz, vp, vp, sz, ci, vp]
+        L.fhe_tggsw_key_reserve.argtypes = [vp, ci, ci, sz, sz, ci, C.POINTER(vp)]
+        L.fhe_tggsw_key_fill.argtypes = [vp, sz, vp, vp, sz, ci, vp]
         L.fhe_torus_ctx_create.argtypes = [ci, C.POINTER(vp)]
         L.fhe_torus_ctx_destroy.argtypes = [vp]
         L.fhe_torus_ctx_destroy.restype = None

@@ -365,6 +365,100 @@ int fhe_tggsw_prepare_fft64(const fhe_torus_ctx *t, int log_b, int d, const uint
     return FHE_OK;
 }
 
+// A key of capacity `count` whose contents fhe_tggsw_key_fill writes later: selectors that are fresh in every call (the rows a circuit
+// bootstrap produces) instead of a bootstrapping key made once.  The form is chosen by fhe_tggsw_prepare's rule (restated here: that
+// entry stays as it is), or is the fft64 form.  This is the one device-wide allocation of a selector key's life.
+int fhe_tggsw_key_reserve(const fhe_torus_ctx *t, int log_b, int d, size_t n, size_t count, int fft64, fhe_tggsw_key **out) {
+    if (!out) return FHE_ERR_INVALID;
+    *out = nullptr;
+    if (!t || !is_pow2(n) || count == 0) return FHE_ERR_INVALID;
+    const int log_n = ilog2(n);
+    if (log_n < 8 || log_n > 11) return FHE_ERR_UNSUPPORTED;
+    fhe::TDecomp P;
+    int rc = make_tdecomp(log_b, d, &P);
+    if (rc != FHE_OK) return rc;
+    const int bound_bits = ilog2((size_t)2 * d) + 1 + log_n + 62 + log_b;
+    if (!fft64 && bound_bits > 118) return FHE_ERR_UNSUPPORTED;
+    const bool use30 = bound_bits <= 88 && log_b <= 28;
+    const bool usex3 = (size_t(2 * d) << (log_n + log_b)) <= (size_t(1) << 21) && log_b <= 7 && log_b * d <= 31 && 2 * d <= 16 && log_n <= 10 &&
+                       fhe::opt(fhe::OPT_NO_F64_EXACT) == 0;
+    DeviceGuard guard(t->device);
+    if (!guard.ok) return FHE_ERR_HIP;
+    const size_t words = count * 2 * d * n;  // of a or of b
+    fhe_tggsw_key *k = new (std::nothrow) fhe_tggsw_key();
+    if (!k) return FHE_ERR_INVALID;
+    k->t = t; k->device = t->device; k->log_n = log_n; k->log_b = log_b; k->d = d; k->count = count; k->P = P;
+    hipError_t e;
+    if (fft64) e = hipMalloc((void **)&k->d_rowsf, words * sizeof(double2));  // 2 rows (n / 2) complex values
+    else if (usex3) e = hipMalloc((void **)&k->d_rowsx3, 3 * words * sizeof(double2));
+    else if (use30) e = hipMalloc((void **)&k->d_rows30, 3 * 2 * words * sizeof(unsigned));
+    else {
+        e = hipMalloc((void **)&k->d_rows[0], 4 * words * sizeof(u64));  // both primes
+        if (e == hipSuccess) k->d_rows[1] = k->d_rows[0] + 2 * words;
+    }
+    if (e != hipSuccess) { g_last_hip = (int)e; delete k; return FHE_ERR_HIP; }
+    *out = k;
+    return FHE_OK;
+}
+
+// `count` ciphertexts into slots first_index .. of a reserved (or prepared) key, on `stream`: the prepare kernels of the key's form, each
+// writing where the whole-key prepare would (every form keeps the rows of one ciphertext together inside a prime's plane; the planes lie
+// the key's capacity apart).  Device memory: no hipMalloc, no host wait; the two 60-bit primes' transform scratch is stream ordered.
+int fhe_tggsw_key_fill(fhe_tggsw_key *key, size_t first_index, const uint64_t *rows_a, const uint64_t *rows_b, size_t count, fhe_mem mem, void *stream) {
+    if (!key || !key->t || first_index > key->count || count > key->count - first_index || ((!rows_a || !rows_b) && count)) return FHE_ERR_INVALID;
+    if (count == 0) return FHE_OK;
+    const fhe_torus_ctx *t = key->t;
+    hipStream_t st = (hipStream_t)stream;
+    DeviceGuard guard(key->device);
+    if (!guard.ok) return FHE_ERR_HIP;
+    const int log_n = key->log_n, d = key->d;
+    const size_t n = size_t(1) << log_n, rows = count * 2 * d, words = rows * n, per = size_t(2 * d) * 2 * n, cap_words = key->count * 2 * d * n;
+    Mirror ma(rows_a, words, mem, true, st), mb(rows_b, words, mem, true, st);
+    if (ma.rc | mb.rc) return FHE_ERR_HIP;
+    const u64 *sa = ma.d, *sb = mb.d;
+    if (key->d_rowsf) {
+        double2 *dst = key->d_rowsf + first_index * (per / 2);
+        return with_torus<TorusRingF>(log_n, [&](auto wr) {
+            using WR = typename decltype(wr)::type;
+            return fhe::launch_teams<fhe::torusf_key_prepare_kernel<WR>, WR>(2 * rows, fhe::TorusF<WR>::LDS_BYTES, st, sa, sb, rows, (const double2 *)t->d_twf, dst);
+        });
+    }
+    if (key->d_rowsx3) {
+        double2 *dst = key->d_rowsx3 + first_index * (per / 2) * 3;
+        return with_torus<TorusRingF>(log_n, [&](auto wr) {
+            using WR = typename decltype(wr)::type;
+            return fhe::launch_teams<fhe::torusx3_key_prepare_kernel<WR>, WR>(6 * rows, fhe::TorusF<WR>::LDS_BYTES, st, sa, sb, rows, (const double2 *)t->d_twf, dst);
+        });
+    }
+    int rc = FHE_OK;
+    if (key->d_rows30) {
+        for (int pi = 0; pi < 3 && rc == FHE_OK; ++pi) {
+            unsigned *dst = key->d_rows30 + size_t(pi) * 2 * cap_words + first_index * per;
+            rc = with_torus<TorusRing30>(log_n, [&](auto wr) {
+                using WR = typename decltype(wr)::type;
+                return fhe::launch_teams<fhe::torus30_key_prepare_kernel<WR>, WR>(2 * rows, WR::LDS_BYTES, st, sa, sb, rows, t->T30.descs + pi, dst);
+            });
+        }
+        return rc;
+    }
+    StreamWs wsp(2 * words * sizeof(u64), st);  // the residues of a and b of one prime, transformed in place
+    if (wsp.rc != FHE_OK) return wsp.rc;
+    u64 *tmp = wsp.as<u64>();
+    for (int pi = 0; pi < 2 && rc == FHE_OK; ++pi) {
+        const u64 p = pi ? t->T.p1 : t->T.p0;
+        rc = fhe::launch<fhe::torus_residue_kernel>(grid_for(words), 256, 0, st, sa, tmp, words, p);
+        if (rc == FHE_OK) rc = fhe::launch<fhe::torus_residue_kernel>(grid_for(words), 256, 0, st, sb, tmp + words, words, p);
+        if (rc == FHE_OK) rc = fhe::ntt_fwd_multi(t->d_descs + pi, 1, tmp, log_n, 2 * rows, st, 60);
+        if (rc != FHE_OK) break;
+        rc = with_torus<TorusRing>(log_n, [&](auto wr) {
+            using WR = typename decltype(wr)::type;
+            return fhe::launch<fhe::key_permute_kernel<WR>>(grid_for(words), 256, 0, st, (const u64 *)tmp, (const u64 *)(tmp + words),
+                                                            key->d_rows[pi] + first_index * per, rows, 60);
+        });
+    }
+    return rc;
+}
+
 // scheme/tfhe/src/tggsw.rs:100-112 `Tggsw::external_product(param, key[index], ct)`, in place on [batch][n] a / b
 int fhe_tggsw_external_product(const fhe_torus_ctx *t, const fhe_tggsw_key *key, size_t index, uint64_t *ct_a, uint64_t *ct_b, size_t batch,
                                fhe_mem mem, void *stream) {

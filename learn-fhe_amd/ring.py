@@ -869,6 +869,21 @@ class TggswKey:
         fn = L.lib().fhe_tggsw_prepare_fft64 if fft64 else L.lib().fhe_tggsw_prepare
         L.check(fn(t.handle, log_b, d, pa, pb, n, self.count, mem, C.byref(self._h)), "fhe_tggsw_prepare")
 
+    @classmethod
+    def reserve(cls, t: TorusContext, log_b, d, n, count, fft64=False):
+        """fhe_tggsw_key_reserve: a key of capacity `count` in the form the constructor would choose, contents undefined until fill()"""
+        self = cls.__new__(cls)
+        self.t, self.log_b, self.d, self.n, self.fft64, self.count = t, log_b, d, n, fft64, count
+        self._h = C.c_void_p()
+        L.check(L.lib().fhe_tggsw_key_reserve(t.handle, log_b, d, n, count, int(bool(fft64)), C.byref(self._h)), "fhe_tggsw_key_reserve")
+        return self
+
+    def fill(self, first_index, rows_a, rows_b):
+        """fhe_tggsw_key_fill: rows_a, rows_b [count][2d][n] into the slots first_index .., on the rows' stream (torch) without a host wait"""
+        pa, cnt, mem, st = _buf(rows_a)
+        L.check(L.lib().fhe_tggsw_key_fill(self._h, first_index, pa, _buf(rows_b)[0], cnt // (2 * self.d * self.n), mem, st), "fhe_tggsw_key_fill")
+        return self
+
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
         if h and L is not None and getattr(L, "lib", None):  # (module globals are gone at interpreter shutdown)
