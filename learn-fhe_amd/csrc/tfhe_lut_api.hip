@@ -16,92 +16,26 @@ namespace {
 // the library's rule for LUT_EXTRACT = 0: the ladder writes the extractions itself
 constexpr bool LUT_RULE_FUSED = true;
 
-// One tree level (polys or in_* -> out_*) under the key's form.  Every form offsets its rows to the call's first selector here; the
-// kernels add (c m + l) rows' worth.
+// One tree level (polys or in_* -> out_*) under the key's form.  The key argument starts at the call's first selector; the kernels add
+// (c m + l) entries.
 int launch_lut_level(const fhe_torus_ctx *t, const fhe_tggsw_key *key, size_t first_index, const u64 *polys, const u64 *in_a, const u64 *in_b, u64 *out_a,
                      u64 *out_b, const fhe::LutJobs &J, hipStream_t st) {
-    const size_t n = size_t(1) << key->log_n, per = size_t(2 * key->d) * 2 * n;
-    if (key->d_rowsf) {
-        const double2 *rows = key->d_rowsf + first_index * (per / 2);
-        return with_torus<TorusRingF>(key->log_n, [&](auto wr) {
-            using WR = typename decltype(wr)::type;
-            return fhe::launch_teams<fhe::torusf_lut_level_kernel<WR, TF_MIN_WAVES>, WR>(J.jobs, fhe::TorusF<WR>::LDS_BYTES, st, polys, in_a, in_b, out_a, out_b, J,
-                                                                                         rows, key->P, (const double2 *)t->d_twf);
-        });
-    }
-    if (key->d_rowsx3) {
-        const double2 *rows = key->d_rowsx3 + first_index * (per / 2) * 3;
-        return with_torus<TorusRingF>(key->log_n, [&](auto wr) {
-            using WR = typename decltype(wr)::type;
-            return fhe::launch_teams<fhe::torusx3_lut_level_kernel<WR, TF_MIN_WAVES>, WR>(J.jobs, fhe::TorusX3<WR>::lds_bytes(2 * key->d), st, polys, in_a, in_b,
-                                                                                          out_a, out_b, J, rows, key->P, (const double2 *)t->d_twf);
-        });
-    }
-    if (key->d_rows30) {
-        const size_t plane = key->count * per;
-        const unsigned *rows = key->d_rows30 + first_index * per;
-        return with_torus<TorusRing30>(key->log_n, [&](auto wr) {
-            using WR = typename decltype(wr)::type;
-            return fhe::launch_teams<fhe::torus30_lut_level_kernel<WR>, WR>(J.jobs, WR::TORUS_LDS_BYTES, st, polys, in_a, in_b, out_a, out_b, J, rows, plane,
-                                                                            key->P, t->T30);
-        });
-    }
-    const u64 *rows0 = key->d_rows[0] + first_index * per, *rows1 = key->d_rows[1] + first_index * per;
-    return with_torus<TorusRing>(key->log_n, [&](auto wr) {
-        using WR = typename decltype(wr)::type;
-        return fhe::launch_teams<fhe::torus_lut_level_kernel<WR>, WR>(J.jobs, WR::TORUS_LDS_BYTES, st, polys, in_a, in_b, out_a, out_b, J, rows0, rows1, key->P,
-                                                                      t->T);
+    return with_key_form<false>(t, key, first_index, [&](auto form, auto k, size_t lds) {
+        using Form = typename decltype(form)::type;
+        return fhe::launch_teams<fhe::tfhe_lut_level_kernel<Form>, typename Form::Ring>(J.jobs, lds, st, polys, in_a, in_b, out_a, out_b, J, k);
     });
 }
 
 // The rotation ladder on acc; ext_a != null: it writes the extractions (ext_a [batch n_out][n], ext_b [batch n_out]) instead of storing
-// the accumulators; FP: there was no tree, the accumulators start from the shared polynomials.  The two starts are
-// two instantiations: one kernel with both kept 28 registers more alive through the CMUX loop than either needs
-template <bool FP>
-int launch_lut_ladder_from(const fhe_torus_ctx *t, const fhe_tggsw_key *key, size_t first_index, const u64 *polys, u64 *acc_a, u64 *acc_b, u64 *ext_a, u64 *ext_b,
-                      const fhe::LutJobs &J, hipStream_t st) {
-    const size_t n = size_t(1) << key->log_n, per = size_t(2 * key->d) * 2 * n;
-    if (key->d_rowsf) {
-        const double2 *rows = key->d_rowsf + first_index * (per / 2);
-        return with_torus<TorusRingF>(key->log_n, [&](auto wr) {
-            using WR = typename decltype(wr)::type;
-            return fhe::launch_teams<fhe::torusf_lut_ladder_kernel<WR, TF_MIN_WAVES, FP>, WR>(J.jobs, fhe::TorusF<WR>::LDS_BYTES, st, polys, acc_a, acc_b, ext_a, ext_b, J, rows,
-                                                                                          key->P, (const double2 *)t->d_twf);
-        });
-    }
-    if (key->d_rowsx3) {
-        const double2 *rows = key->d_rowsx3 + first_index * (per / 2) * 3;
-        return with_torus<TorusRingF>(key->log_n, [&](auto wr) {
-            using WR = typename decltype(wr)::type;
-            return fhe::launch_teams<fhe::torusx3_lut_ladder_kernel<WR, TF_MIN_WAVES, FP>, WR>(J.jobs, fhe::TorusX3<WR>::lds_bytes(2 * key->d), st, polys, acc_a, acc_b,
-                                                                                           ext_a, ext_b, J, rows, key->P, (const double2 *)t->d_twf);
-        });
-    }
-    if (key->d_rows30) {
-        const size_t plane = key->count * per;
-        const unsigned *rows = key->d_rows30 + first_index * per;
-        // the rule of the blind rotation (torus_api.hip): digits computed once where they are bytes and at most 8 limbs
-        const bool packed = key->P.log_b <= 7 && 2 * key->d <= 8 && key->log_n >= 8 && fhe::opt(fhe::OPT_NO_PACKED_DIGITS) == 0;
-        return with_torus<TorusRing30>(key->log_n, [&](auto wr) {
-            using WR = typename decltype(wr)::type;
-            if (packed)
-                return fhe::launch_teams<fhe::torus30_lut_ladder_kernel<WR, true, FP>, WR>(J.jobs, WR::torus_pk_lds_bytes(2 * key->d), st, polys, acc_a, acc_b, ext_a, ext_b, J, rows,
-                                                                                       plane, key->P, t->T30);
-            return fhe::launch_teams<fhe::torus30_lut_ladder_kernel<WR, false, FP>, WR>(J.jobs, WR::TORUS_LDS_BYTES, st, polys, acc_a, acc_b, ext_a, ext_b, J, rows, plane, key->P,
-                                                                                    t->T30);
-        });
-    }
-    const u64 *rows0 = key->d_rows[0] + first_index * per, *rows1 = key->d_rows[1] + first_index * per;
-    return with_torus<TorusRing>(key->log_n, [&](auto wr) {
-        using WR = typename decltype(wr)::type;
-        return fhe::launch_teams<fhe::torus_lut_ladder_kernel<WR, FP>, WR>(J.jobs, WR::TORUS_LDS_BYTES, st, polys, acc_a, acc_b, ext_a, ext_b, J, rows0, rows1, key->P, t->T);
-    });
-}
-
+// the accumulators; polys != null: there was no tree, the accumulators start from the shared polynomials
 int launch_lut_ladder(const fhe_torus_ctx *t, const fhe_tggsw_key *key, size_t first_index, const u64 *polys, u64 *acc_a, u64 *acc_b, u64 *ext_a, u64 *ext_b,
                       const fhe::LutJobs &J, hipStream_t st) {
-    return fhe::with_bool(polys != nullptr, [&](auto fp) {
-        return launch_lut_ladder_from<decltype(fp)::value>(t, key, first_index, polys, acc_a, acc_b, ext_a, ext_b, J, st);
+    return with_key_form<true>(t, key, first_index, [&](auto form, auto k, size_t lds) {
+        using Form = typename decltype(form)::type;
+        return fhe::with_bool(polys != nullptr, [&](auto fp) {
+            return fhe::launch_teams<fhe::tfhe_lut_ladder_kernel<Form, decltype(fp)::value>, typename Form::Ring>(J.jobs, lds, st, polys, acc_a, acc_b, ext_a,
+                                                                                                                ext_b, J, k);
+        });
     });
 }
 

@@ -1,8 +1,7 @@
-// Kernels of the encrypted table look-up (tfhe_lut.hpp, fhe_tfhe_lut_eval; k = 1): a CMUX-tree level and the rotation ladder, in every
-// form a prepared fhe_tggsw_key can have.  They differ from the CMUX and blind-rotation kernels of those forms (torus_kernels.hpp,
-// torus30_kernels.hpp, torusf_kernels.hpp), whose team device functions they are built around, in where a team finds its key rows --
-// the selector index comes from the CIPHERTEXT, c m + l for address bit l of ciphertext c -- and in the rotation amounts, which are the
-// public constants 2N - 2^l.
+// Kernels of the encrypted table look-up (tfhe_lut.hpp, fhe_tfhe_lut_eval; k = 1): a CMUX-tree level and the rotation ladder, each ONE
+// template over the form of the prepared fhe_tggsw_key (torus_forms.hpp: the policy gives the registers, the LDS and the CMUX).  They
+// differ from the CMUX and blind-rotation kernels there in where a team finds its key rows -- the selector index comes from the
+// CIPHERTEXT, c m + l for address bit l of ciphertext c -- and in the rotation amounts, which are the public constants 2N - 2^l.
 //
 //   tree level v   job p = (c n_acc + g) half + t, half = 2^(h - 1 - v): out[p] = CMUX(selector c m + r + v; in[2 p], in[2 p + 1])
 //                  = in[2 p] + external_product(selector, in[2 p + 1] - in[2 p]) (tggsw.rs:114-121): the difference is formed in
@@ -18,9 +17,7 @@
 // Per ciphertext the arithmetic is that of fhe_tggsw_cmux, fhe_tglwe_rotate and fhe_tglwe_sample_extract chained: the same device
 // functions on the same operands, so the same bits in every exact form and, on one device, in the fft64 form.
 #pragma once
-#include "torus_kernels.hpp"
-#include "torus30_kernels.hpp"
-#include "torusf_kernels.hpp"
+#include "torus_forms.hpp"
 
 namespace fhe {
 
@@ -100,275 +97,95 @@ __device__ __forceinline__ LutPair lut_pair(unsigned p, const LutJobs &J, bool l
     return LutPair{c, level0 ? (size_t(g) << J.log_polys) + 2 * size_t(t) : 2 * size_t(p)};
 }
 
-// ---- fft64 and the exact three-piece form: a team over the N / 2 complex slots --------------------------------------------------
+// ---- one body per operation, in the key's form F (torus_forms.hpp) -----------------------------------------------------------------
 
-// CMUX(key; ct0, ct1) of one pair on a team of the f64 forms; X3: the three-piece device functions
-template <class W, bool X3>
-__device__ __forceinline__ void lutf_level(const u64 *__restrict__ polys, const u64 *__restrict__ in_a, const u64 *__restrict__ in_b, u64 *__restrict__ out_a,
-                                           u64 *__restrict__ out_b, unsigned p, const LutJobs &J, const double2 *__restrict__ rows, size_t per, const TDecomp &P,
-                                           const ArithC64::K &k, int lane, u64 *lds) {
-    constexpr int E = W::E, N = 2 * W::N;
-    const bool level0 = polys != nullptr;
-    const LutPair pr = lut_pair<W>(p, J, level0);
-    const u64 *s0b = (level0 ? polys : in_b) + pr.src * N, *s0a = in_a + pr.src * N;
-    u64 da[2 * E], db[2 * E], x[2 * E];
-    pairs_load<W>(db, s0b + N, lane);
-    pairs_load<W>(x, s0b, lane);
+// the pair's difference ct1 - ct0 into (da, db); level 0: da = 0
+template <class F>
+__device__ __forceinline__ void lut_pair_diff(const u64 *__restrict__ s0a, const u64 *__restrict__ s0b, bool level0, int lane, u64 (&da)[F::CNT], u64 (&db)[F::CNT]) {
+    constexpr int CNT = F::CNT, N = F::N;
+    u64 x[CNT];
+    F::load(db, s0b + N, lane);
+    F::load(x, s0b, lane);
 #pragma unroll
-    for (int e = 0; e < 2 * E; ++e) db[e] -= x[e];
+    for (int e = 0; e < CNT; ++e) db[e] -= x[e];
     if (level0) {
 #pragma unroll
-        for (int e = 0; e < 2 * E; ++e) da[e] = 0;
+        for (int e = 0; e < CNT; ++e) da[e] = 0;
     } else {
-        pairs_load<W>(da, s0a + N, lane);
-        pairs_load<W>(x, s0a, lane);
+        F::load(da, s0a + N, lane);
+        F::load(x, s0a, lane);
 #pragma unroll
-        for (int e = 0; e < 2 * E; ++e) da[e] -= x[e];
-    }
-    const double2 *row = rows + (size_t(pr.c) * J.m + J.first) * per;
-    if constexpr (X3) teamx3_cmux<W>(da, db, 0xffffffffu, row, P, k, lane, lds);
-    else teamf_cmux<W>(da, db, 0xffffffffu, row, P, k, lane, lds);
-    const int ln = lut_fresh_lane(lane);
-    pairs_load<W>(x, s0b, ln);
-#pragma unroll
-    for (int e = 0; e < 2 * E; ++e) db[e] += x[e];
-    if (!level0) {
-        pairs_load<W>(x, s0a, ln);
-#pragma unroll
-        for (int e = 0; e < 2 * E; ++e) da[e] += x[e];
-    }
-    pairs_store<W>(da, out_a + size_t(p) * N, ln);
-    pairs_store<W>(db, out_b + size_t(p) * N, ln);
-}
-
-template <class W, bool X3, bool FROM_POLYS>
-__device__ __forceinline__ void lutf_ladder(const u64 *__restrict__ polys, u64 *__restrict__ acc_a, u64 *__restrict__ acc_b, u64 *__restrict__ ext_a, u64 *__restrict__ ext_b,
-                                            unsigned job, const LutJobs &J,
-                                            const double2 *__restrict__ rows, size_t per, const TDecomp &P, const ArithC64::K &k, int lane, u64 *lds) {
-    constexpr int E = W::E, N = 2 * W::N;
-    const unsigned ju = lut_uniform<W>(job), c = ju / J.n_acc, g = ju - c * J.n_acc;
-    u64 ca[2 * E], cb[2 * E];
-    if constexpr (FROM_POLYS) {
-        pairs_load<W>(cb, polys + size_t(g) * N, lane);
-#pragma unroll
-        for (int e = 0; e < 2 * E; ++e) ca[e] = 0;
-    } else {
-        pairs_load<W>(cb, acc_b + size_t(ju) * N, lane);
-        pairs_load<W>(ca, acc_a + size_t(ju) * N, lane);
-    }
-    const double2 *row = rows + size_t(c) * J.m * per;
-#pragma unroll 1
-    for (unsigned l = 0; l < J.steps; ++l) {
-        const unsigned r = lut_step_rotation(2 * N, l);
-        if constexpr (X3) teamx3_cmux<W>(ca, cb, r, row + l * per, P, k, lane, lds);
-        else teamf_cmux<W>(ca, cb, r, row + l * per, P, k, lane, lds);
-    }
-    lut_ladder_finish<W, true>(ca, cb, acc_a, acc_b, ext_a, ext_b, ju, c, g, J, lane);
-}
-
-// rows: the key from the call's first selector on, [..][2d][2][M] complex
-template <class W, int MIN_WAVES>
-__global__ __launch_bounds__(W::THREADS, MIN_WAVES) void torusf_lut_level_kernel(const u64 *__restrict__ polys, const u64 *__restrict__ in_a,
-                                                                                 const u64 *__restrict__ in_b, u64 *__restrict__ out_a, u64 *__restrict__ out_b,
-                                                                                 LutJobs J, const double2 *__restrict__ rows, TDecomp P,
-                                                                                 const double2 *__restrict__ tw) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int lane = W::lane(), team = W::team();
-    const unsigned p = blockIdx.x * W::TEAMS + team;
-    const ArithC64::K k = ArithC64::make(stage_twiddles<W>(tw, smem_raw), W::LOG_N);
-    if (p >= J.jobs) return;
-    u64 *lds = reinterpret_cast<u64 *>(smem_raw) + team * TorusF<W>::LDS_WORDS;
-    lutf_level<W, false>(polys, in_a, in_b, out_a, out_b, p, J, rows, size_t(2 * P.d) * 2 * W::N, P, k, lane, lds);
-}
-
-template <class W, int MIN_WAVES, bool FROM_POLYS>
-__global__ __launch_bounds__(W::THREADS, MIN_WAVES) void torusf_lut_ladder_kernel(const u64 *__restrict__ polys, u64 *__restrict__ acc_a, u64 *__restrict__ acc_b,
-        u64 *__restrict__ ext_a, u64 *__restrict__ ext_b,
-                                                                                  LutJobs J, const double2 *__restrict__ rows, TDecomp P,
-                                                                                  const double2 *__restrict__ tw) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int lane = W::lane(), team = W::team();
-    const unsigned job = blockIdx.x * W::TEAMS + team;
-    const ArithC64::K k = ArithC64::make(stage_twiddles<W>(tw, smem_raw), W::LOG_N);
-    if (job >= J.jobs) return;
-    u64 *lds = reinterpret_cast<u64 *>(smem_raw) + team * TorusF<W>::LDS_WORDS;
-    lutf_ladder<W, false, FROM_POLYS>(polys, acc_a, acc_b, ext_a, ext_b, job, J, rows, size_t(2 * P.d) * 2 * W::N, P, k, lane, lds);
-}
-
-// rows: [..][2d][2][3][M] complex
-template <class W, int MIN_WAVES>
-__global__ __launch_bounds__(W::THREADS, MIN_WAVES) void torusx3_lut_level_kernel(const u64 *__restrict__ polys, const u64 *__restrict__ in_a,
-                                                                                  const u64 *__restrict__ in_b, u64 *__restrict__ out_a, u64 *__restrict__ out_b,
-                                                                                  LutJobs J, const double2 *__restrict__ rows, TDecomp P,
-                                                                                  const double2 *__restrict__ tw) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int lane = W::lane(), team = W::team();
-    const unsigned p = blockIdx.x * W::TEAMS + team;
-    const ArithC64::K k = ArithC64::make(stage_twiddles_x3<W>(tw, smem_raw, 2 * P.d), W::LOG_N);
-    if (p >= J.jobs) return;
-    u64 *lds = reinterpret_cast<u64 *>(smem_raw) + team * TorusX3<W>::lds_words(2 * P.d);
-    lutf_level<W, true>(polys, in_a, in_b, out_a, out_b, p, J, rows, size_t(2 * P.d) * 6 * W::N, P, k, lane, lds);
-}
-
-template <class W, int MIN_WAVES, bool FROM_POLYS>
-__global__ __launch_bounds__(W::THREADS, MIN_WAVES) void torusx3_lut_ladder_kernel(const u64 *__restrict__ polys, u64 *__restrict__ acc_a, u64 *__restrict__ acc_b,
-        u64 *__restrict__ ext_a, u64 *__restrict__ ext_b,
-                                                                                   LutJobs J, const double2 *__restrict__ rows, TDecomp P,
-                                                                                   const double2 *__restrict__ tw) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int lane = W::lane(), team = W::team();
-    const unsigned job = blockIdx.x * W::TEAMS + team;
-    const ArithC64::K k = ArithC64::make(stage_twiddles_x3<W>(tw, smem_raw, 2 * P.d), W::LOG_N);
-    if (job >= J.jobs) return;
-    u64 *lds = reinterpret_cast<u64 *>(smem_raw) + team * TorusX3<W>::lds_words(2 * P.d);
-    lutf_ladder<W, true, FROM_POLYS>(polys, acc_a, acc_b, ext_a, ext_b, job, J, rows, size_t(2 * P.d) * 6 * W::N, P, k, lane, lds);
-}
-
-// ---- the integer forms: a team over the N coefficients ---------------------------------------------------------------------------
-
-// the pair's difference into (da, db); level 0: da = 0
-template <class W>
-__device__ __forceinline__ void lut_pair_diff(const u64 *__restrict__ s0a, const u64 *__restrict__ s0b, bool level0, int lane, u64 (&da)[W::E], u64 (&db)[W::E]) {
-    constexpr int E = W::E, N = W::N;
-    u64 x[E];
-    wave_load<W>(db, s0b + N, lane);
-    wave_load<W>(x, s0b, lane);
-#pragma unroll
-    for (int e = 0; e < E; ++e) db[e] -= x[e];
-    if (level0) {
-#pragma unroll
-        for (int e = 0; e < E; ++e) da[e] = 0;
-    } else {
-        wave_load<W>(da, s0a + N, lane);
-        wave_load<W>(x, s0a, lane);
-#pragma unroll
-        for (int e = 0; e < E; ++e) da[e] -= x[e];
+        for (int e = 0; e < CNT; ++e) da[e] -= x[e];
     }
 }
-// out <- ct0 + (xa, xb)
-template <class W>
-__device__ __forceinline__ void lut_pair_finish(const u64 *__restrict__ s0a, const u64 *__restrict__ s0b, bool level0, int lane, u64 (&xa)[W::E], u64 (&xb)[W::E],
+// out <- ct0 + (xa, xb); ct0 is read again (from cache)
+template <class F>
+__device__ __forceinline__ void lut_pair_finish(const u64 *__restrict__ s0a, const u64 *__restrict__ s0b, bool level0, int lane, u64 (&xa)[F::CNT], u64 (&xb)[F::CNT],
                                                 u64 *__restrict__ oa, u64 *__restrict__ ob) {
-    constexpr int E = W::E;
-    u64 x[E];
+    constexpr int CNT = F::CNT;
+    u64 x[CNT];
     const int ln = lut_fresh_lane(lane);
-    wave_load<W>(x, s0b, ln);
+    F::load(x, s0b, ln);
 #pragma unroll
-    for (int e = 0; e < E; ++e) xb[e] += x[e];
+    for (int e = 0; e < CNT; ++e) xb[e] += x[e];
     if (!level0) {
-        wave_load<W>(x, s0a, ln);
+        F::load(x, s0a, ln);
 #pragma unroll
-        for (int e = 0; e < E; ++e) xa[e] += x[e];
+        for (int e = 0; e < CNT; ++e) xa[e] += x[e];
     }
-    wave_store<W>(xa, oa, ln);
-    wave_store<W>(xb, ob, ln);
+    F::store(xa, oa, ln);
+    F::store(xb, ob, ln);
 }
 
-// three 30-bit primes; rows: the first prime's rows from the call's first selector on, `plane` words to the next prime's.  The level
-// serves the packed-digit keys as well: fhe_tggsw_cmux runs this external product for them too (the packed form is bit-identical)
-template <class W>
-__global__ __launch_bounds__(W::THREADS, W::MIN_WAVES) void torus30_lut_level_kernel(const u64 *__restrict__ polys, const u64 *__restrict__ in_a,
-                                                                                     const u64 *__restrict__ in_b, u64 *__restrict__ out_a, u64 *__restrict__ out_b,
-                                                                                     LutJobs J, const unsigned *__restrict__ rows, size_t plane, TDecomp P,
-                                                                                     Torus30Consts T) {
-    constexpr int E = W::E, N = W::N;
+// out[p] = CMUX(selector; in[2 p], in[2 p + 1]) of one pair.  Both 30-bit forms run the unpacked external product, as fhe_tggsw_cmux does
+// (the packed form is bit-identical).
+template <class F>
+__global__ __launch_bounds__(F::Ring::THREADS, F::MIN_WAVES) void tfhe_lut_level_kernel(const u64 *__restrict__ polys, const u64 *__restrict__ in_a,
+                                                                                        const u64 *__restrict__ in_b, u64 *__restrict__ out_a,
+                                                                                        u64 *__restrict__ out_b, LutJobs J, typename F::Key key) {
+    using W = typename F::Ring;
+    constexpr int CNT = F::CNT, N = F::N;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int lane = W::lane(), team = W::team();
     const unsigned p = blockIdx.x * W::TEAMS + team;
+    const typename F::Team tm = F::team_setup(key, smem_raw, team);
     if (p >= J.jobs) return;
-    u64 *lds = reinterpret_cast<u64 *>(smem_raw) + team * W::TORUS_LDS_WORDS;
     const bool level0 = polys != nullptr;
     const LutPair pr = lut_pair<W>(p, J, level0);
     const u64 *s0b = (level0 ? polys : in_b) + pr.src * N, *s0a = in_a + pr.src * N;
-    u64 da[E], db[E], xa[E], xb[E];
-    lut_pair_diff<W>(s0a, s0b, level0, lane, da, db);
-    const unsigned *k0 = rows + (size_t(pr.c) * J.m + J.first) * (size_t(2 * P.d) * 2 * N);
-    team_torus_external_product30<W>(da, db, k0, k0 + plane, k0 + 2 * plane, P, T, lane, lds, xa, xb);
-    lut_pair_finish<W>(s0a, s0b, level0, lane, xa, xb, out_a + size_t(p) * N, out_b + size_t(p) * N);
+    u64 da[CNT], db[CNT];
+    lut_pair_diff<F>(s0a, s0b, level0, lane, da, db);
+    F::external_product(da, db, key, size_t(pr.c) * J.m + J.first, tm, lane);
+    lut_pair_finish<F>(s0a, s0b, level0, lane, da, db, out_a + size_t(p) * N, out_b + size_t(p) * N);
 }
 
-// PACKED: the CMUX whose digits are computed once (team_torus_cmux30_pk; its LDS carries the digit area)
-template <class W, bool PACKED, bool FROM_POLYS>
-__global__ __launch_bounds__(W::THREADS, W::MIN_WAVES) void torus30_lut_ladder_kernel(const u64 *__restrict__ polys, u64 *__restrict__ acc_a,
-                                                                                      u64 *__restrict__ acc_b, u64 *__restrict__ ext_a, u64 *__restrict__ ext_b, LutJobs J, const unsigned *__restrict__ rows,
-                                                                                      size_t plane, TDecomp P, Torus30Consts T) {
-    constexpr int E = W::E, N = W::N;
+// FROM_POLYS: there was no tree, the accumulator starts as (0, polys[g]).  The two starts are two instantiations: one kernel with both
+// kept 28 registers more alive through the CMUX loop than either needs
+template <class F, bool FROM_POLYS>
+__global__ __launch_bounds__(F::Ring::THREADS, F::MIN_WAVES) void tfhe_lut_ladder_kernel(const u64 *__restrict__ polys, u64 *__restrict__ acc_a,
+                                                                                         u64 *__restrict__ acc_b, u64 *__restrict__ ext_a,
+                                                                                         u64 *__restrict__ ext_b, LutJobs J, typename F::Key key) {
+    using W = typename F::Ring;
+    constexpr int CNT = F::CNT, N = F::N;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int lane = W::lane(), team = W::team();
     const unsigned job = blockIdx.x * W::TEAMS + team;
+    const typename F::Team tm = F::team_setup(key, smem_raw, team);
     if (job >= J.jobs) return;
-    u64 *lds = reinterpret_cast<u64 *>(smem_raw) + team * (W::TORUS_LDS_WORDS + (PACKED ? W::torus_dig_words(2 * P.d) : 0));
     const unsigned ju = lut_uniform<W>(job), c = ju / J.n_acc, g = ju - c * J.n_acc;
-    u64 ca[E], cb[E];
+    u64 ca[CNT], cb[CNT];
     if constexpr (FROM_POLYS) {
-        wave_load<W>(cb, polys + size_t(g) * N, lane);
+        F::load(cb, polys + size_t(g) * N, lane);
 #pragma unroll
-        for (int e = 0; e < E; ++e) ca[e] = 0;
+        for (int e = 0; e < CNT; ++e) ca[e] = 0;
     } else {
-        wave_load<W>(cb, acc_b + size_t(ju) * N, lane);
-        wave_load<W>(ca, acc_a + size_t(ju) * N, lane);
+        F::load(cb, acc_b + size_t(ju) * N, lane);
+        F::load(ca, acc_a + size_t(ju) * N, lane);
     }
-    const size_t per = size_t(2 * P.d) * 2 * N;
-    const unsigned *row = rows + size_t(c) * J.m * per;
+    const size_t first = size_t(c) * J.m;
 #pragma unroll 1
-    for (unsigned l = 0; l < J.steps; ++l) {
-        const unsigned *k0 = row + l * per;
-        const unsigned r = lut_step_rotation(2 * N, l);
-        if constexpr (PACKED) team_torus_cmux30_pk<W>(ca, cb, r, k0, k0 + plane, k0 + 2 * plane, P, T, lane, lds);
-        else team_torus_cmux30<W>(ca, cb, r, k0, k0 + plane, k0 + 2 * plane, P, T, lane, lds);
-    }
-    lut_ladder_finish<W, false>(ca, cb, acc_a, acc_b, ext_a, ext_b, ju, c, g, J, lane);
-}
-
-// two 60-bit primes; rows0, rows1: each prime's rows from the call's first selector on
-template <class W>
-__global__ __launch_bounds__(W::THREADS, W::MIN_WAVES) void torus_lut_level_kernel(const u64 *__restrict__ polys, const u64 *__restrict__ in_a,
-                                                                                   const u64 *__restrict__ in_b, u64 *__restrict__ out_a, u64 *__restrict__ out_b,
-                                                                                   LutJobs J, const u64 *__restrict__ rows0, const u64 *__restrict__ rows1, TDecomp P,
-                                                                                   TorusConsts T) {
-    constexpr int E = W::E, N = W::N;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int lane = W::lane(), team = W::team();
-    const unsigned p = blockIdx.x * W::TEAMS + team;
-    if (p >= J.jobs) return;
-    u64 *lds = reinterpret_cast<u64 *>(smem_raw) + team * W::TORUS_LDS_WORDS;
-    const bool level0 = polys != nullptr;
-    const LutPair pr = lut_pair<W>(p, J, level0);
-    const u64 *s0b = (level0 ? polys : in_b) + pr.src * N, *s0a = in_a + pr.src * N;
-    u64 da[E], db[E], xa[E], xb[E];
-    lut_pair_diff<W>(s0a, s0b, level0, lane, da, db);
-    const size_t off = (size_t(pr.c) * J.m + J.first) * (size_t(2 * P.d) * 2 * N);
-    team_torus_external_product<W>(da, db, rows0 + off, rows1 + off, P, T, lane, lds, xa, xb);
-    lut_pair_finish<W>(s0a, s0b, level0, lane, xa, xb, out_a + size_t(p) * N, out_b + size_t(p) * N);
-}
-
-template <class W, bool FROM_POLYS>
-__global__ __launch_bounds__(W::THREADS, W::MIN_WAVES) void torus_lut_ladder_kernel(const u64 *__restrict__ polys, u64 *__restrict__ acc_a, u64 *__restrict__ acc_b,
-        u64 *__restrict__ ext_a, u64 *__restrict__ ext_b,
-                                                                                    LutJobs J, const u64 *__restrict__ rows0, const u64 *__restrict__ rows1,
-                                                                                    TDecomp P, TorusConsts T) {
-    constexpr int E = W::E, N = W::N;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int lane = W::lane(), team = W::team();
-    const unsigned job = blockIdx.x * W::TEAMS + team;
-    if (job >= J.jobs) return;
-    u64 *lds = reinterpret_cast<u64 *>(smem_raw) + team * W::TORUS_LDS_WORDS;
-    const unsigned ju = lut_uniform<W>(job), c = ju / J.n_acc, g = ju - c * J.n_acc;
-    u64 ca[E], cb[E];
-    if constexpr (FROM_POLYS) {
-        wave_load<W>(cb, polys + size_t(g) * N, lane);
-#pragma unroll
-        for (int e = 0; e < E; ++e) ca[e] = 0;
-    } else {
-        wave_load<W>(cb, acc_b + size_t(ju) * N, lane);
-        wave_load<W>(ca, acc_a + size_t(ju) * N, lane);
-    }
-    const size_t per = size_t(2 * P.d) * 2 * N;
-    const size_t off = size_t(c) * J.m * per;
-#pragma unroll 1
-    for (unsigned l = 0; l < J.steps; ++l)
-        team_torus_cmux<W>(ca, cb, lut_step_rotation(2 * N, l), rows0 + off + l * per, rows1 + off + l * per, P, T, lane, lds);
-    lut_ladder_finish<W, false>(ca, cb, acc_a, acc_b, ext_a, ext_b, ju, c, g, J, lane);
+    for (unsigned l = 0; l < J.steps; ++l) F::cmux(ca, cb, lut_step_rotation(2 * N, l), key, first + l, tm, lane);
+    lut_ladder_finish<W, F::PAIRS>(ca, cb, acc_a, acc_b, ext_a, ext_b, ju, c, g, J, lane);
 }
 
 // ---- extraction ------------------------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
-// Row T on three 30-bit primes (arith30.hpp): the same team-per-ciphertext CMUX / blind-rotation kernels as torus_kernels.hpp,
-// with 32-bit transforms.  Used for keys whose exact products fit 2^88 (BASELINE config 5 does: ~2^82).
+// Row T on three 30-bit primes (arith30.hpp): the team device functions of torus_kernels.hpp with 32-bit transforms (the kernels
+// around them: torus_forms.hpp).  Used for keys whose exact products fit 2^88 (BASELINE config 5 does: ~2^82).
 #pragma once
 #include "arith30.hpp"
 #include "torus_kernels.hpp"
@@ -153,68 +153,13 @@ __device__ __forceinline__ void team_torus_cmux30(u64 (&ca)[W::E], u64 (&cb)[W::
     for (int e = 0; e < E; ++e) { ca[e] += xa[e]; cb[e] += xb[e]; }
 }
 
-// as torus_cmux_kernel; rows: [3 primes][count][2d][2][N] u32, `per` words per key entry, `plane` words per prime
-template <class W>
-__global__ __launch_bounds__(W::THREADS, W::MIN_WAVES) void torus30_cmux_kernel(u64 *__restrict__ acc_a, u64 *__restrict__ acc_b, unsigned batch,
-                                                                                const unsigned *__restrict__ rows, size_t plane, TDecomp P,
-                                                                                const u64 *__restrict__ rot, size_t rot_stride, Torus30Consts T) {
-    constexpr int E = W::E, N = W::N;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int lane = W::lane(), team = W::team();
-    const unsigned ct = blockIdx.x * W::TEAMS + team;
-    if (ct >= batch) return;
-    u64 *lds = reinterpret_cast<u64 *>(smem_raw) + team * W::TORUS_LDS_WORDS;
-    u64 *ga = acc_a + size_t(ct) * N, *gb = acc_b + size_t(ct) * N;
-    u64 ca[E], cb[E];
-    wave_load<W>(ca, ga, lane);
-    wave_load<W>(cb, gb, lane);
-    if (rot != nullptr) {
-        team_torus_cmux30<W>(ca, cb, unsigned(rot[size_t(ct) * rot_stride]) & (2 * N - 1), rows, rows + plane, rows + 2 * plane, P, T, lane, lds);
-    } else {
-        u64 xa[E], xb[E];
-        team_torus_external_product30<W>(ca, cb, rows, rows + plane, rows + 2 * plane, P, T, lane, lds, xa, xb);
-#pragma unroll
-        for (int e = 0; e < E; ++e) { ca[e] = xa[e]; cb[e] = xb[e]; }
-    }
-    wave_store<W>(ca, ga, lane);
-    wave_store<W>(cb, gb, lane);
-}
-
-template <class W>
-__global__ __launch_bounds__(W::THREADS, W::MIN_WAVES) void torus30_blind_rotate_kernel(
-    const u64 *__restrict__ v, const unsigned *__restrict__ table_of, const u64 *__restrict__ a_tilde, const u64 *__restrict__ b_tilde, unsigned n_lwe,
-    unsigned batch, const unsigned *__restrict__ rows, size_t plane, TDecomp P, Torus30Consts T, u64 *__restrict__ out_a, u64 *__restrict__ out_b) {
-    constexpr int E = W::E, N = W::N;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int lane = W::lane(), team = W::team();
-    const unsigned ct = blockIdx.x * W::TEAMS + team;
-    if (ct >= batch) return;
-    u64 *lds = reinterpret_cast<u64 *>(smem_raw) + team * W::TORUS_LDS_WORDS;
-    u64 ca[E], cb[E];
-    if (table_of != nullptr) v += size_t(__builtin_amdgcn_readfirstlane(table_of[ct])) * N;  // this ciphertext's own table
-    wave_load<W>(cb, v, lane);
-#pragma unroll
-    for (int e = 0; e < E; ++e) ca[e] = 0;
-    team_torus_rotate<W>(cb, (2 * N - (unsigned(b_tilde[ct]) & (2 * N - 1))) & (2 * N - 1), lane, lds);
-    const size_t per = size_t(2 * P.d) * 2 * N;
-    const u64 *a = a_tilde + size_t(ct) * n_lwe;
-#pragma unroll 1
-    for (unsigned i = 0; i < n_lwe; ++i) {
-        const unsigned r = __builtin_amdgcn_readfirstlane(unsigned(a[i]) & (2 * N - 1));
-        const unsigned *k0 = rows + i * per;
-        team_torus_cmux30<W>(ca, cb, r, k0, k0 + plane, k0 + 2 * plane, P, T, lane, lds);
-    }
-    wave_store<W>(ca, out_a + size_t(ct) * N, lane);
-    wave_store<W>(cb, out_b + size_t(ct) * N, lane);
-}
-
 // ---- the blind rotation with a CMUX's digits computed ONCE (log_b <= 8, 2d <= 8: BASELINE config 5's gadget) --------------------
-// The kernels above decompose (da, db) three times, once per prime, and keep (da, db) and the decomposition state in registers
+// The functions above decompose (da, db) three times, once per prime, and keep (da, db) and the decomposition state in registers
 // across all three passes: 48 registers, and a third of the decomposition work repeated twice.  A digit of a base <= 2^8 gadget
 // is a signed byte: here the 2d E digits of a lane are computed once, packed four to a dword and parked in a lane-private LDS
 // area ([limb][E / 4][TEAM] dwords: consecutive lanes on consecutive banks); each prime's pass unpacks them with one
 // v_bfe_i32 each.  The registers that frees hold the multiply-accumulate's sums UNREDUCED (Arith30::mac_close).  Same integers
-// mod every prime, same CRT: the outputs are bit-identical to the kernels above (tests/test_torus_gpu.py runs both).
+// mod every prime, same CRT: the outputs are bit-identical to theirs (tests/test_torus_gpu.py runs both).
 template <class W>
 __device__ __forceinline__ void park_digits30(const u64 (&da)[W::E], const u64 (&db)[W::E], const TDecomp &P, int lane, unsigned *dig) {
     constexpr int E = W::E;
@@ -334,40 +279,12 @@ __device__ __forceinline__ void team_torus_cmux30_pk(u64 (&ca)[W::E], u64 (&cb)[
     }
 }
 
-// Compiled for two waves per SIMD like the kernel above (204 registers at N = 2^10: FOUR teams per CU, a batch of 1024 is exactly one
-// generation of 256 CUs).  Measured and dropped: three waves per SIMD -- 159 registers once the lane index is made opaque per limb so
-// that the transforms' exchange addresses are recomputed instead of living across the loop, and with the digit area sized by the
-// gadget (31 232 bytes per team) FIVE teams per CU: 17.1 k gates/s at batch 1024 against 25.5 k (a fifth team per CU leaves 52 CUs of
-// that batch idle), 20.8 k against 21.8 k at 1280, 21.8 k against 26.4 k at 4096 -- recomputed addresses cost more than a fifth team hides.
-template <class W>
-__global__ __launch_bounds__(W::THREADS, W::MIN_WAVES) void torus30_blind_rotate_pk_kernel(
-    const u64 *__restrict__ v, const unsigned *__restrict__ table_of, const u64 *__restrict__ a_tilde, const u64 *__restrict__ b_tilde, unsigned n_lwe,
-    unsigned batch, const unsigned *__restrict__ rows, size_t plane, TDecomp P, Torus30Consts T, u64 *__restrict__ out_a, u64 *__restrict__ out_b) {
-    constexpr int E = W::E, N = W::N;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int lane = W::lane(), team = W::team();
-    const unsigned ct = blockIdx.x * W::TEAMS + team;
-    if (ct >= batch) return;
-    // a team's LDS: exchange image | parking area of two residue pairs | the digits of one CMUX, sized by the gadget (2d limbs): at
-    // cfg5 (N = 2^10, d = 3) 31 232 bytes -- FIVE teams per CU where the 8-limb maximum would leave room for four
-    u64 *lds = reinterpret_cast<u64 *>(smem_raw) + team * (W::TORUS_LDS_WORDS + W::torus_dig_words(2 * P.d));
-    u64 ca[E], cb[E];
-    if (table_of != nullptr) v += size_t(__builtin_amdgcn_readfirstlane(table_of[ct])) * N;  // this ciphertext's own table
-    wave_load<W>(cb, v, lane);
-#pragma unroll
-    for (int e = 0; e < E; ++e) ca[e] = 0;
-    team_torus_rotate<W>(cb, (2 * N - (unsigned(b_tilde[ct]) & (2 * N - 1))) & (2 * N - 1), lane, lds);
-    const size_t per = size_t(2 * P.d) * 2 * N;
-    const u64 *a = a_tilde + size_t(ct) * n_lwe;
-#pragma unroll 1
-    for (unsigned i = 0; i < n_lwe; ++i) {
-        const unsigned r = __builtin_amdgcn_readfirstlane(unsigned(a[i]) & (2 * N - 1));
-        const unsigned *k0 = rows + i * per;
-        team_torus_cmux30_pk<W>(ca, cb, r, k0, k0 + plane, k0 + 2 * plane, P, T, lane, lds);
-    }
-    wave_store<W>(ca, out_a + size_t(ct) * N, lane);
-    wave_store<W>(cb, out_b + size_t(ct) * N, lane);
-}
+// Where the packed-digit blind rotation stands (torus30_blind_rotate_pk_kernel, torus_forms.hpp): compiled for two waves per SIMD like
+// the unpacked kernel (204 registers at N = 2^10: FOUR teams per CU, a batch of 1024 is exactly one generation of 256 CUs).
+// Measured and dropped: three waves per SIMD -- 159 registers once the lane index is made opaque per limb so that the transforms'
+// exchange addresses are recomputed instead of living across the loop, and with the digit area sized by the gadget (31 232 bytes
+// per team) FIVE teams per CU: 17.1 k gates/s at batch 1024 against 25.5 k (a fifth team per CU leaves 52 CUs of that batch idle),
+// 20.8 k against 21.8 k at 1280, 21.8 k against 26.4 k at 4096 -- recomputed addresses cost more than a fifth team hides.
 
 // key preparation for one prime: signed torus rows [rows][2][N] (a | b) -> Montgomery-form evaluations in key_perm30 layout
 template <class W>

@@ -63,40 +63,51 @@ void build_host30(Host30 &H) {
 
 constexpr int TF_LOG_CAP = 11;  // fft64 mode: twiddles for rings up to N = 2^11
 
-int launch_cmux(const fhe_torus_ctx *t, const fhe_tggsw_key *key, size_t index, u64 *a, u64 *b, size_t batch, const u64 *rot,
-                size_t rot_stride, hipStream_t st) {
-    const size_t n = size_t(1) << key->log_n;
-    const size_t per = size_t(2 * key->d) * 2 * n;
-    if (key->d_rowsf) {  // fft64 mode
-        const double2 *frows = key->d_rowsf + index * (per / 2);
-        return with_torus<TorusRingF>(key->log_n, [&](auto wr) {
-            using WR = typename decltype(wr)::type;
-            return fhe::launch_teams<fhe::torusf_cmux_kernel<WR, TF_MIN_WAVES>, WR>(batch, fhe::TorusF<WR>::LDS_BYTES, st, a, b, (unsigned)batch, frows, key->P,
-                                                                                    rot, rot_stride, (const double2 *)t->d_twf);
-        });
-    }
-    if (key->d_rowsx3) {  // exact, three key pieces through f64 transforms
-        const double2 *xrows = key->d_rowsx3 + index * (per / 2) * 3;
-        return with_torus<TorusRingF>(key->log_n, [&](auto wr) {
-            using WR = typename decltype(wr)::type;
-            return fhe::launch_teams<fhe::torusx3_cmux_kernel<WR, TF_MIN_WAVES>, WR>(batch, fhe::TorusX3<WR>::lds_bytes(2 * key->d), st, a, b, (unsigned)batch,
-                                                                                     xrows, key->P, rot, rot_stride, (const double2 *)t->d_twf);
-        });
-    }
-    if (key->d_rows30) {  // three 30-bit primes
-        const size_t plane = key->count * per;
-        return with_torus<TorusRing30>(key->log_n, [&](auto wr) {
-            using WR = typename decltype(wr)::type;
-            return fhe::launch_teams<fhe::torus30_cmux_kernel<WR>, WR>(batch, WR::TORUS_LDS_BYTES, st, a, b, (unsigned)batch,
-                                                                       (const unsigned *)(key->d_rows30 + index * per), plane, key->P, rot, rot_stride, t->T30);
-        });
-    }
-    const u64 *rows0 = key->d_rows[0] + index * per, *rows1 = key->d_rows[1] + index * per;
-    return with_torus<TorusRing>(key->log_n, [&](auto wr) {
-        using WR = typename decltype(wr)::type;
-        return fhe::launch_teams<fhe::torus_cmux_kernel<WR>, WR>(batch, WR::TORUS_LDS_BYTES, st, a, b, (unsigned)batch, rows0, rows1, key->P, rot, rot_stride,
-                                                                 t->T);
+// (a, b) [batch][n] <- external_product(key[index], (a, b)) on device buffers
+int launch_external_product(const fhe_torus_ctx *t, const fhe_tggsw_key *key, size_t index, u64 *a, u64 *b, size_t batch, hipStream_t st) {
+    return with_key_form<false>(t, key, index, [&](auto form, auto k, size_t lds) {
+        using Form = typename decltype(form)::type;
+        return fhe::launch_teams<fhe::torus_external_product_kernel<Form>, typename Form::Ring>(batch, lds, st, a, b, (unsigned)batch, k);
     });
+}
+
+// fhe_tggsw_key_fill per form: `rows` TGLWE rows (sa, sb: [rows][N]) through the form's prepare kernels to where `k`, the key argument at
+// the first slot to fill, points.  The rows are the key's own and the key is the caller's to write: the const of Form::Key is the
+// kernels' view of them.
+template <class W, bool X3>
+int fill_rows(fhe::Type<fhe::FormF<W, X3>>, const typename fhe::FormF<W, X3>::Key &k, const fhe_torus_ctx *, const u64 *sa, const u64 *sb, size_t rows,
+              hipStream_t st) {
+    double2 *dst = const_cast<double2 *>(k.rows);
+    if constexpr (X3) return fhe::launch_teams<fhe::torusx3_key_prepare_kernel<W>, W>(6 * rows, fhe::TorusF<W>::LDS_BYTES, st, sa, sb, rows, k.tw, dst);
+    else return fhe::launch_teams<fhe::torusf_key_prepare_kernel<W>, W>(2 * rows, fhe::TorusF<W>::LDS_BYTES, st, sa, sb, rows, k.tw, dst);
+}
+template <class W>
+int fill_rows(fhe::Type<fhe::Form30<W, false>>, const typename fhe::Form30<W, false>::Key &k, const fhe_torus_ctx *, const u64 *sa, const u64 *sb, size_t rows,
+              hipStream_t st) {
+    int rc = FHE_OK;
+    for (int pi = 0; pi < 3 && rc == FHE_OK; ++pi)
+        rc = fhe::launch_teams<fhe::torus30_key_prepare_kernel<W>, W>(2 * rows, W::LDS_BYTES, st, sa, sb, rows, k.T.descs + pi,
+                                                                      const_cast<unsigned *>(k.rows) + pi * k.plane);
+    return rc;
+}
+template <class W>
+int fill_rows(fhe::Type<fhe::Form60<W>>, const typename fhe::Form60<W>::Key &k, const fhe_torus_ctx *t, const u64 *sa, const u64 *sb, size_t rows,
+              hipStream_t st) {
+    const size_t words = rows * W::N;
+    StreamWs wsp(2 * words * sizeof(u64), st);  // the residues of a and b of one prime, transformed in place
+    if (wsp.rc != FHE_OK) return wsp.rc;
+    u64 *tmp = wsp.as<u64>();
+    int rc = FHE_OK;
+    for (int pi = 0; pi < 2 && rc == FHE_OK; ++pi) {
+        const u64 p = pi ? t->T.p1 : t->T.p0;
+        rc = fhe::launch<fhe::torus_residue_kernel>(grid_for(words), 256, 0, st, sa, tmp, words, p);
+        if (rc == FHE_OK) rc = fhe::launch<fhe::torus_residue_kernel>(grid_for(words), 256, 0, st, sb, tmp + words, words, p);
+        if (rc == FHE_OK) rc = fhe::ntt_fwd_multi(t->d_descs + pi, 1, tmp, W::LOG_N, 2 * rows, st, 60);
+        if (rc == FHE_OK)
+            rc = fhe::launch<fhe::key_permute_kernel<W>>(grid_for(words), 256, 0, st, (const u64 *)tmp, (const u64 *)(tmp + words),
+                                                         const_cast<u64 *>(pi ? k.rows1 : k.rows0), rows, 60);
+    }
+    return rc;
 }
 
 }  // namespace
@@ -411,52 +422,10 @@ int fhe_tggsw_key_fill(fhe_tggsw_key *key, size_t first_index, const uint64_t *r
     hipStream_t st = (hipStream_t)stream;
     DeviceGuard guard(key->device);
     if (!guard.ok) return FHE_ERR_HIP;
-    const int log_n = key->log_n, d = key->d;
-    const size_t n = size_t(1) << log_n, rows = count * 2 * d, words = rows * n, per = size_t(2 * d) * 2 * n, cap_words = key->count * 2 * d * n;
+    const size_t rows = count * 2 * key->d, words = rows << key->log_n;
     Mirror ma(rows_a, words, mem, true, st), mb(rows_b, words, mem, true, st);
     if (ma.rc | mb.rc) return FHE_ERR_HIP;
-    const u64 *sa = ma.d, *sb = mb.d;
-    if (key->d_rowsf) {
-        double2 *dst = key->d_rowsf + first_index * (per / 2);
-        return with_torus<TorusRingF>(log_n, [&](auto wr) {
-            using WR = typename decltype(wr)::type;
-            return fhe::launch_teams<fhe::torusf_key_prepare_kernel<WR>, WR>(2 * rows, fhe::TorusF<WR>::LDS_BYTES, st, sa, sb, rows, (const double2 *)t->d_twf, dst);
-        });
-    }
-    if (key->d_rowsx3) {
-        double2 *dst = key->d_rowsx3 + first_index * (per / 2) * 3;
-        return with_torus<TorusRingF>(log_n, [&](auto wr) {
-            using WR = typename decltype(wr)::type;
-            return fhe::launch_teams<fhe::torusx3_key_prepare_kernel<WR>, WR>(6 * rows, fhe::TorusF<WR>::LDS_BYTES, st, sa, sb, rows, (const double2 *)t->d_twf, dst);
-        });
-    }
-    int rc = FHE_OK;
-    if (key->d_rows30) {
-        for (int pi = 0; pi < 3 && rc == FHE_OK; ++pi) {
-            unsigned *dst = key->d_rows30 + size_t(pi) * 2 * cap_words + first_index * per;
-            rc = with_torus<TorusRing30>(log_n, [&](auto wr) {
-                using WR = typename decltype(wr)::type;
-                return fhe::launch_teams<fhe::torus30_key_prepare_kernel<WR>, WR>(2 * rows, WR::LDS_BYTES, st, sa, sb, rows, t->T30.descs + pi, dst);
-            });
-        }
-        return rc;
-    }
-    StreamWs wsp(2 * words * sizeof(u64), st);  // the residues of a and b of one prime, transformed in place
-    if (wsp.rc != FHE_OK) return wsp.rc;
-    u64 *tmp = wsp.as<u64>();
-    for (int pi = 0; pi < 2 && rc == FHE_OK; ++pi) {
-        const u64 p = pi ? t->T.p1 : t->T.p0;
-        rc = fhe::launch<fhe::torus_residue_kernel>(grid_for(words), 256, 0, st, sa, tmp, words, p);
-        if (rc == FHE_OK) rc = fhe::launch<fhe::torus_residue_kernel>(grid_for(words), 256, 0, st, sb, tmp + words, words, p);
-        if (rc == FHE_OK) rc = fhe::ntt_fwd_multi(t->d_descs + pi, 1, tmp, log_n, 2 * rows, st, 60);
-        if (rc != FHE_OK) break;
-        rc = with_torus<TorusRing>(log_n, [&](auto wr) {
-            using WR = typename decltype(wr)::type;
-            return fhe::launch<fhe::key_permute_kernel<WR>>(grid_for(words), 256, 0, st, (const u64 *)tmp, (const u64 *)(tmp + words),
-                                                            key->d_rows[pi] + first_index * per, rows, 60);
-        });
-    }
-    return rc;
+    return with_key_form<false>(t, key, first_index, [&](auto form, auto k, size_t) { return fill_rows(form, k, t, (const u64 *)ma.d, (const u64 *)mb.d, rows, st); });
 }
 
 // scheme/tfhe/src/tggsw.rs:100-112 `Tggsw::external_product(param, key[index], ct)`, in place on [batch][n] a / b
@@ -470,7 +439,7 @@ int fhe_tggsw_external_product(const fhe_torus_ctx *t, const fhe_tggsw_key *key,
     const size_t n = size_t(1) << key->log_n;
     Mirror ma(ct_a, n * batch, mem, true, st), mb(ct_b, n * batch, mem, true, st);
     if (ma.rc | mb.rc) return FHE_ERR_HIP;
-    int rc = launch_cmux(t, key, index, ma.d, mb.d, batch, nullptr, 0, st);
+    int rc = launch_external_product(t, key, index, ma.d, mb.d, batch, st);
     if (rc == FHE_OK) rc = ma.sync_out(st);
     if (rc == FHE_OK) rc = mb.sync_out(st);
     return rc;
@@ -495,7 +464,7 @@ int fhe_tggsw_cmux(const fhe_torus_ctx *t, const fhe_tggsw_key *key, size_t inde
     const dim3 grid(grid_for(words));
     FHE_TRY(fhe::launch<fhe::torus_addsub_kernel>(grid, 256, 0, st, (const u64 *)m1a.d, (const u64 *)m0a.d, da, words, 1));
     FHE_TRY(fhe::launch<fhe::torus_addsub_kernel>(grid, 256, 0, st, (const u64 *)m1b.d, (const u64 *)m0b.d, db, words, 1));
-    FHE_TRY(launch_cmux(t, key, index, da, db, batch, nullptr, 0, st));
+    FHE_TRY(launch_external_product(t, key, index, da, db, batch, st));
     FHE_TRY(fhe::launch<fhe::torus_addsub_kernel>(grid, 256, 0, st, (const u64 *)m0a.d, (const u64 *)da, moa.d, words, 0));
     FHE_TRY(fhe::launch<fhe::torus_addsub_kernel>(grid, 256, 0, st, (const u64 *)m0b.d, (const u64 *)db, mob.d, words, 0));
     int rc = moa.sync_out(st);
@@ -541,49 +510,12 @@ namespace {
 // [n_tables][n] and ciphertext i starts from row table_of[i] (device array, in range: the kernels do not clamp).
 int blind_rotate_dev(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, const u64 *at, const u64 *bt, const u64 *v, const unsigned *table_of, u64 *oa,
                      u64 *ob, size_t batch, hipStream_t st) {
-    const size_t n = size_t(1) << brk->log_n, n_lwe = brk->count;
+    const size_t n_lwe = brk->count;
     if (batch > 0x7fffffffull || n_lwe > 0x7fffffffull) return FHE_ERR_UNSUPPORTED;
-    if (brk->d_rowsf) {  // fft64 mode
-        return with_torus<TorusRingF>(brk->log_n, [&](auto wr) {
-            using WR = typename decltype(wr)::type;
-            return fhe::launch_teams<fhe::torusf_blind_rotate_kernel<WR, TF_MIN_WAVES>, WR>(batch, fhe::TorusF<WR>::LDS_BYTES, st, v, table_of, at, bt,
-                                                                                            (unsigned)n_lwe, (unsigned)batch, (const double2 *)brk->d_rowsf,
-                                                                                            brk->P, (const double2 *)t->d_twf, oa, ob);
-        });
-    }
-    if (brk->d_rowsx3) {  // exact, three key pieces through f64 transforms
-        return with_torus<TorusRingF>(brk->log_n, [&](auto wr) {
-            using WR = typename decltype(wr)::type;
-            return fhe::launch_teams<fhe::torusx3_blind_rotate_kernel<WR, TF_MIN_WAVES>, WR>(batch, fhe::TorusX3<WR>::lds_bytes(2 * brk->d), st, v, table_of, at,
-                                                                                             bt, (unsigned)n_lwe, (unsigned)batch,
-                                                                                             (const double2 *)brk->d_rowsx3, brk->P,
-                                                                                             (const double2 *)t->d_twf, oa, ob);
-        });
-    }
-    if (brk->d_rows30) {  // three 30-bit primes
-        const size_t plane = brk->count * size_t(2 * brk->d) * 2 * n;
-        // base <= 2^8 and at most 8 limbs (cfg5: base 2^7, d = 3): the CMUX digits are computed once and parked as bytes, the
-        // multiply-accumulate runs unreduced (torus30_kernels.hpp); lab switch NO_PACKED_DIGITS keeps the older kernel (bit-identical)
-        // (a digit of base 2^8 ranges over [-128, 128]: one value too many for a byte)
-        const bool packed = brk->P.log_b <= 7 && 2 * brk->d <= 8 && brk->log_n >= 8 && fhe::opt(fhe::OPT_NO_PACKED_DIGITS) == 0;
-        if (packed) {
-            return with_torus<TorusRing30>(brk->log_n, [&](auto wr) {
-                using WR = typename decltype(wr)::type;
-                return fhe::launch_teams<fhe::torus30_blind_rotate_pk_kernel<WR>, WR>(batch, WR::torus_pk_lds_bytes(2 * brk->d), st, v, table_of, at, bt,
-                                                                                      (unsigned)n_lwe, (unsigned)batch, (const unsigned *)brk->d_rows30, plane,
-                                                                                      brk->P, t->T30, oa, ob);
-            });
-        }
-        return with_torus<TorusRing30>(brk->log_n, [&](auto wr) {
-            using WR = typename decltype(wr)::type;
-            return fhe::launch_teams<fhe::torus30_blind_rotate_kernel<WR>, WR>(batch, WR::TORUS_LDS_BYTES, st, v, table_of, at, bt, (unsigned)n_lwe,
-                                                                               (unsigned)batch, (const unsigned *)brk->d_rows30, plane, brk->P, t->T30, oa, ob);
-        });
-    }
-    return with_torus<TorusRing>(brk->log_n, [&](auto wr) {
-        using WR = typename decltype(wr)::type;
-        return fhe::launch_teams<fhe::torus_blind_rotate_kernel<WR>, WR>(batch, WR::TORUS_LDS_BYTES, st, v, table_of, at, bt, (unsigned)n_lwe, (unsigned)batch,
-                                                                         (const u64 *)brk->d_rows[0], (const u64 *)brk->d_rows[1], brk->P, t->T, oa, ob);
+    return with_key_form<true>(t, brk, 0, [&](auto form, auto k, size_t lds) {
+        using Form = typename decltype(form)::type;
+        return fhe::launch_teams<blind_rotate_kernel(decltype(form){}), typename Form::Ring>(batch, lds, st, v, table_of, at, bt, (unsigned)n_lwe,
+                                                                                             (unsigned)batch, k, oa, ob);
     });
 }
 

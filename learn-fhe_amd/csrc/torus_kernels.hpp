@@ -184,68 +184,6 @@ __device__ __forceinline__ void team_torus_cmux(u64 (&ca)[W::E], u64 (&cb)[W::E]
     for (int e = 0; e < E; ++e) { ca[e] += xa[e]; cb[e] += xb[e]; }
 }
 
-// scheme/tfhe/src/tggsw.rs:100-121 for k = 1, one team (fhew_kernels.hpp: WaveRing) per ciphertext.
-//   rot == nullptr: (a, b) <- external_product(key, (a, b))
-//   rot != nullptr: one CMUX step: (a, b) <- (a, b) + external_product(key, (a, b) X^r - (a, b)), r = rot[ct * rot_stride] mod 2N
-template <class W>
-__global__ __launch_bounds__(W::THREADS, W::MIN_WAVES) void torus_cmux_kernel(
-    u64 *__restrict__ acc_a, u64 *__restrict__ acc_b, unsigned batch, const u64 *__restrict__ rows0, const u64 *__restrict__ rows1,
-    TDecomp P, const u64 *__restrict__ rot, size_t rot_stride, TorusConsts T) {
-    constexpr int E = W::E, N = W::N;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int lane = W::lane(), team = W::team();
-    const unsigned ct = blockIdx.x * W::TEAMS + team;
-    if (ct >= batch) return;
-    u64 *lds = reinterpret_cast<u64 *>(smem_raw) + team * W::TORUS_LDS_WORDS;
-    u64 *ga = acc_a + size_t(ct) * N, *gb = acc_b + size_t(ct) * N;
-    u64 ca[E], cb[E];
-    wave_load<W>(ca, ga, lane);
-    wave_load<W>(cb, gb, lane);
-    if (rot != nullptr) {
-        team_torus_cmux<W>(ca, cb, unsigned(rot[size_t(ct) * rot_stride]) & (2 * N - 1), rows0, rows1, P, T, lane, lds);
-    } else {
-        u64 xa[E], xb[E];
-        team_torus_external_product<W>(ca, cb, rows0, rows1, P, T, lane, lds, xa, xb);
-#pragma unroll
-        for (int e = 0; e < E; ++e) { ca[e] = xa[e]; cb[e] = xb[e]; }
-    }
-    wave_store<W>(ca, ga, lane);
-    wave_store<W>(cb, gb, lane);
-}
-
-// scheme/tfhe/src/bootstrapping.rs:84-96 `blind_rotate` (k = 1), the whole fold in ONE launch: acc = (0, v X^-b), then
-// acc <- cmux(brk_i, acc, acc X^(a_i)) for i = 0 .. n_lwe-1, the accumulator in the team's registers throughout.
-// rows0 / rows1: the key set [n_lwe][2d][2][N] per prime (key_perm layout); a_tilde [batch][n_lwe], b_tilde [batch] mod 2N.
-// table_of (all five blind-rotation kernels): null = every ciphertext starts from v; else ciphertext ct starts from
-// v + table_of[ct] * N (v: [n_tables][N]).  The index is uniform across the team, read once and kept scalar; it is NOT range-checked
-// here: the entry points check host-memory indices, device-memory callers guarantee table_of[ct] < n_tables.
-template <class W>
-__global__ __launch_bounds__(W::THREADS, W::MIN_WAVES) void torus_blind_rotate_kernel(
-    const u64 *__restrict__ v, const unsigned *__restrict__ table_of, const u64 *__restrict__ a_tilde, const u64 *__restrict__ b_tilde, unsigned n_lwe,
-    unsigned batch, const u64 *__restrict__ rows0, const u64 *__restrict__ rows1, TDecomp P, TorusConsts T, u64 *__restrict__ out_a, u64 *__restrict__ out_b) {
-    constexpr int E = W::E, N = W::N;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int lane = W::lane(), team = W::team();
-    const unsigned ct = blockIdx.x * W::TEAMS + team;
-    if (ct >= batch) return;
-    u64 *lds = reinterpret_cast<u64 *>(smem_raw) + team * W::TORUS_LDS_WORDS;
-    u64 ca[E], cb[E];
-    if (table_of != nullptr) v += size_t(__builtin_amdgcn_readfirstlane(table_of[ct])) * N;  // this ciphertext's own table
-    wave_load<W>(cb, v, lane);
-#pragma unroll
-    for (int e = 0; e < E; ++e) ca[e] = 0;
-    team_torus_rotate<W>(cb, (2 * N - (unsigned(b_tilde[ct]) & (2 * N - 1))) & (2 * N - 1), lane, lds);  // (0, v).rotate(-b)
-    const size_t per = size_t(2 * P.d) * 2 * N;
-    const u64 *a = a_tilde + size_t(ct) * n_lwe;
-#pragma unroll 1
-    for (unsigned i = 0; i < n_lwe; ++i) {
-        const unsigned r = __builtin_amdgcn_readfirstlane(unsigned(a[i]) & (2 * N - 1));
-        team_torus_cmux<W>(ca, cb, r, rows0 + i * per, rows1 + i * per, P, T, lane, lds);
-    }
-    wave_store<W>(ca, out_a + size_t(ct) * N, lane);
-    wave_store<W>(cb, out_b + size_t(ct) * N, lane);
-}
-
 // exact torus product building blocks for fhe_torus_mul: c = a * b with |b| small (two-prime CRT)
 FHE_HEADER_KERNEL void torus_crt_kernel(const u64 *__restrict__ r /* [batch][2][n] */, u64 *__restrict__ out, size_t n, size_t batch, TorusConsts T) {
     const size_t total = n * batch;

@@ -237,57 +237,6 @@ __device__ __forceinline__ void teamf_cmux(u64 (&ca)[2 * W::E], u64 (&cb)[2 * W:
     }
 }
 
-template <class W, int MIN_WAVES>
-__global__ __launch_bounds__(W::THREADS, MIN_WAVES) void torusf_cmux_kernel(u64 *__restrict__ acc_a, u64 *__restrict__ acc_b, unsigned batch,
-                                                                            const double2 *__restrict__ rows, TDecomp P, const u64 *__restrict__ rot,
-                                                                            size_t rot_stride, const double2 *__restrict__ tw) {
-    constexpr int E = W::E, N = 2 * W::N;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int lane = W::lane(), team = W::team();
-    const unsigned ct = blockIdx.x * W::TEAMS + team;
-    const ArithC64::K k = ArithC64::make(stage_twiddles<W>(tw, smem_raw), W::LOG_N);
-    if (ct >= batch) return;
-    u64 *lds = reinterpret_cast<u64 *>(smem_raw) + team * TorusF<W>::LDS_WORDS;
-    u64 *ga = acc_a + size_t(ct) * N, *gb = acc_b + size_t(ct) * N;
-    u64 ca[2 * E], cb[2 * E];
-    pairs_load<W>(ca, ga, lane);
-    pairs_load<W>(cb, gb, lane);
-    teamf_cmux<W>(ca, cb, rot ? unsigned(rot[size_t(ct) * rot_stride]) & (2 * N - 1) : 0xffffffffu, rows, P, k, lane, lds);
-    pairs_store<W>(ca, ga, lane);
-    pairs_store<W>(cb, gb, lane);
-}
-
-// bootstrapping.rs:84-96 in one launch, as torus30_blind_rotate_kernel; rows: [n_lwe][2d][2][M] complex
-template <class W, int MIN_WAVES>
-__global__ __launch_bounds__(W::THREADS, MIN_WAVES) void torusf_blind_rotate_kernel(const u64 *__restrict__ v, const unsigned *__restrict__ table_of, const u64 *__restrict__ a_tilde,
-                                                                                    const u64 *__restrict__ b_tilde, unsigned n_lwe, unsigned batch,
-                                                                                    const double2 *__restrict__ rows, TDecomp P,
-                                                                                    const double2 *__restrict__ tw, u64 *__restrict__ out_a,
-                                                                                    u64 *__restrict__ out_b) {
-    constexpr int E = W::E, N = 2 * W::N;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int lane = W::lane(), team = W::team();
-    const unsigned ct = blockIdx.x * W::TEAMS + team;
-    const ArithC64::K k = ArithC64::make(stage_twiddles<W>(tw, smem_raw), W::LOG_N);
-    if (ct >= batch) return;
-    u64 *lds = reinterpret_cast<u64 *>(smem_raw) + team * TorusF<W>::LDS_WORDS;
-    u64 ca[2 * E], cb[2 * E];
-    if (table_of != nullptr) v += size_t(__builtin_amdgcn_readfirstlane(table_of[ct])) * N;  // this ciphertext's own table
-    pairs_load<W>(cb, v, lane);
-#pragma unroll
-    for (int e = 0; e < 2 * E; ++e) ca[e] = 0;
-    pairs_rotate<W>(cb, (2 * N - (unsigned(b_tilde[ct]) & (2 * N - 1))) & (2 * N - 1), lane, lds);
-    const size_t per = size_t(2 * P.d) * 2 * W::N;
-    const u64 *a = a_tilde + size_t(ct) * n_lwe;
-#pragma unroll 1
-    for (unsigned i = 0; i < n_lwe; ++i) {
-        const unsigned r = __builtin_amdgcn_readfirstlane(unsigned(a[i]) & (2 * N - 1));
-        teamf_cmux<W>(ca, cb, r, rows + i * per, P, k, lane, lds);
-    }
-    pairs_store<W>(ca, out_a + size_t(ct) * N, lane);
-    pairs_store<W>(cb, out_b + size_t(ct) * N, lane);
-}
-
 // Measured and dropped (round 3): PAIRED transforms -- an element type of two complex values (limb p of the a half with limb p of the b half,
 // the two outputs on the way back) shares every twiddle fetch, exchange and barrier between two transforms: four trips through the network
 // per CMUX instead of eight, 228 registers -- 72.8 k gates/s at cfg5 against 74.2-75.0 k unpaired: barriers are not what the kernel waits for.
@@ -470,57 +419,6 @@ __device__ __forceinline__ const double2 *stage_twiddles_x3(const double2 *__res
     for (int i = threadIdx.x; i < TorusX3<W>::N; i += W::THREADS) dst[i] = tw[i];
     __syncthreads();
     return dst;
-}
-
-template <class W, int MIN_WAVES>
-__global__ __launch_bounds__(W::THREADS, MIN_WAVES) void torusx3_cmux_kernel(u64 *__restrict__ acc_a, u64 *__restrict__ acc_b, unsigned batch,
-                                                                             const double2 *__restrict__ rows, TDecomp P, const u64 *__restrict__ rot,
-                                                                             size_t rot_stride, const double2 *__restrict__ tw) {
-    constexpr int E = W::E, N = 2 * W::N;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int lane = W::lane(), team = W::team();
-    const unsigned ct = blockIdx.x * W::TEAMS + team;
-    const ArithC64::K k = ArithC64::make(stage_twiddles_x3<W>(tw, smem_raw, 2 * P.d), W::LOG_N);
-    if (ct >= batch) return;
-    u64 *lds = reinterpret_cast<u64 *>(smem_raw) + team * TorusX3<W>::lds_words(2 * P.d);
-    u64 *ga = acc_a + size_t(ct) * N, *gb = acc_b + size_t(ct) * N;
-    u64 ca[2 * E], cb[2 * E];
-    pairs_load<W>(ca, ga, lane);
-    pairs_load<W>(cb, gb, lane);
-    teamx3_cmux<W>(ca, cb, rot ? unsigned(rot[size_t(ct) * rot_stride]) & (2 * N - 1) : 0xffffffffu, rows, P, k, lane, lds);
-    pairs_store<W>(ca, ga, lane);
-    pairs_store<W>(cb, gb, lane);
-}
-
-// bootstrapping.rs:84-96 in one launch; rows: [n_lwe][2d][2][3][M] complex
-template <class W, int MIN_WAVES>
-__global__ __launch_bounds__(W::THREADS, MIN_WAVES) void torusx3_blind_rotate_kernel(const u64 *__restrict__ v, const unsigned *__restrict__ table_of, const u64 *__restrict__ a_tilde,
-                                                                                     const u64 *__restrict__ b_tilde, unsigned n_lwe, unsigned batch,
-                                                                                     const double2 *__restrict__ rows, TDecomp P,
-                                                                                     const double2 *__restrict__ tw, u64 *__restrict__ out_a,
-                                                                                     u64 *__restrict__ out_b) {
-    constexpr int E = W::E, N = 2 * W::N;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int lane = W::lane(), team = W::team();
-    const unsigned ct = blockIdx.x * W::TEAMS + team;
-    const ArithC64::K k = ArithC64::make(stage_twiddles_x3<W>(tw, smem_raw, 2 * P.d), W::LOG_N);
-    if (ct >= batch) return;
-    u64 *lds = reinterpret_cast<u64 *>(smem_raw) + team * TorusX3<W>::lds_words(2 * P.d);
-    u64 ca[2 * E], cb[2 * E];
-    if (table_of != nullptr) v += size_t(__builtin_amdgcn_readfirstlane(table_of[ct])) * N;  // this ciphertext's own table
-    pairs_load<W>(cb, v, lane);
-#pragma unroll
-    for (int e = 0; e < 2 * E; ++e) ca[e] = 0;
-    pairs_rotate<W>(cb, (2 * N - (unsigned(b_tilde[ct]) & (2 * N - 1))) & (2 * N - 1), lane, lds);
-    const size_t per = size_t(2 * P.d) * 6 * W::N;
-    const u64 *a = a_tilde + size_t(ct) * n_lwe;
-#pragma unroll 1
-    for (unsigned i = 0; i < n_lwe; ++i) {
-        const unsigned r = __builtin_amdgcn_readfirstlane(unsigned(a[i]) & (2 * N - 1));
-        teamx3_cmux<W>(ca, cb, r, rows + i * per, P, k, lane, lds);
-    }
-    pairs_store<W>(ca, out_a + size_t(ct) * N, lane);
-    pairs_store<W>(cb, out_b + size_t(ct) * N, lane);
 }
 
 // key preparation for the three-piece form: job = (row, a | b, piece) -> [row][a | b][piece][M] complex evaluations
