@@ -339,6 +339,17 @@ int fhe_tggsw_key_reserve(const fhe_torus_ctx *t, int log_b, int d, size_t n, si
  * first_index + count beyond the key's capacity, a NULL key, NULL rows with count > 0: FHE_ERR_INVALID. */
 int fhe_tggsw_key_fill(fhe_tggsw_key *key, size_t first_index, const uint64_t *rows_a, const uint64_t *rows_b, size_t count, fhe_mem mem,
                        void *stream);
+/* Which form a prepared or reserved key is in (read-only; for tests and tools: every exact form gives the same bits). */
+enum {
+    FHE_TGGSW_FORM_60 = 0,     /* two 60-bit NTT primes */
+    FHE_TGGSW_FORM_30 = 1,     /* three 30-bit NTT primes */
+    FHE_TGGSW_FORM_FFT64 = 2,  /* the f64 FFT product of fhe_tggsw_prepare_fft64 (not exact) */
+    FHE_TGGSW_FORM_X3 = 3      /* three key pieces through f64 transforms, exact */
+};
+/* *form: one of FHE_TGGSW_FORM_*.  *packs_digits: 1 exactly when a blind rotation or a look-up ladder launched NOW on this key would run
+ * the 30-bit CMUX whose digits are computed once and parked as bytes (form 30, base <= 2^7, 2d <= 8, lab switch NO_PACKED_DIGITS off: the
+ * switch is read as the launch reads it), else 0.  A NULL key or a NULL output: FHE_ERR_INVALID.  Touches no device. */
+int fhe_tggsw_key_form(const fhe_tggsw_key *key, int *form, int *packs_digits);
 /* scheme/tfhe/src/tggsw.rs:100-112 `Tggsw::external_product(param, key[index], ct)`, in place on [batch][n] a / b. */
 int fhe_tggsw_external_product(const fhe_torus_ctx *t, const fhe_tggsw_key *key, size_t index, uint64_t *ct_a, uint64_t *ct_b,
                                size_t batch, fhe_mem mem, void *stream);

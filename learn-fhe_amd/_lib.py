@@ -156,6 +156,7 @@ def lib():
         L.fhe_tfhe_wop_pbs.argtypes = [vp, vp, ci, ci, vp, vp, ci, ci, ci, ci, vp, ci, vp, vp, vp, sz, vp, sz, ci, ci, vp, vp, sz, vp, vp, sz, ci, vp]
         L.fhe_tggsw_key_reserve.argtypes = [vp, ci, ci, sz, sz, ci, C.POINTER(vp)]
         L.fhe_tggsw_key_fill.argtypes = [vp, sz, vp, vp, sz, ci, vp]
+        L.fhe_tggsw_key_form.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]
         L.fhe_torus_ctx_create.argtypes = [ci, C.POINTER(vp)]
         L.fhe_torus_ctx_destroy.argtypes = [vp]
         L.fhe_torus_ctx_destroy.restype = None

@@ -428,6 +428,14 @@ int fhe_tggsw_key_fill(fhe_tggsw_key *key, size_t first_index, const uint64_t *r
     return with_key_form<false>(t, key, first_index, [&](auto form, auto k, size_t) { return fill_rows(form, k, t, (const u64 *)ma.d, (const u64 *)mb.d, rows, st); });
 }
 
+// What with_key_form would pick for `key` now (torus_dispatch.hpp: key_form, key_packs_digits); host only
+int fhe_tggsw_key_form(const fhe_tggsw_key *key, int *form, int *packs_digits) {
+    if (!key || !form || !packs_digits) return FHE_ERR_INVALID;
+    *form = key_form(key);
+    *packs_digits = key_packs_digits(key) ? 1 : 0;
+    return FHE_OK;
+}
+
 // scheme/tfhe/src/tggsw.rs:100-112 `Tggsw::external_product(param, key[index], ct)`, in place on [batch][n] a / b
 int fhe_tggsw_external_product(const fhe_torus_ctx *t, const fhe_tggsw_key *key, size_t index, uint64_t *ct_a, uint64_t *ct_b, size_t batch,
                                fhe_mem mem, void *stream) {

@@ -27,6 +27,23 @@ int with_torus(int log_n, F &&f) {
     return fhe::with_int<8, 9, 10, 11>(log_n, [&](auto ln) { return f(fhe::Type<Ring<decltype(ln)::value>>{}); });
 }
 
+// Whether a 30-bit key runs the CMUX whose digits are computed once, where the caller's kernels allow it (with_key_form<true>): base <= 2^7
+// and at most 8 limbs (cfg5: base 2^7, d = 3): the digits are parked as bytes, the multiply-accumulate runs unreduced
+// (torus30_kernels.hpp); a digit of base 2^8 ranges over [-128, 128]: one value too many for a byte.  The lab switch NO_PACKED_DIGITS
+// keeps the older kernel (bit-identical); it is read here, at the launch.  The ONE statement of the rule: with_key_form and
+// fhe_tggsw_key_form both ask it.
+inline bool key_packs_digits(const fhe_tggsw_key *key) {
+    return key->d_rows30 != nullptr && !key->d_rowsf && !key->d_rowsx3 && key->P.log_b <= 7 && 2 * key->d <= 8 && key->log_n >= 8 &&
+           fhe::opt(fhe::OPT_NO_PACKED_DIGITS) == 0;
+}
+
+// The form as fhe_tggsw_key_form reports it (FHE_TGGSW_FORM_*): the pointers with_key_form reads, in its order
+inline int key_form(const fhe_tggsw_key *key) {
+    if (key->d_rowsx3) return FHE_TGGSW_FORM_X3;
+    if (key->d_rowsf) return FHE_TGGSW_FORM_FFT64;
+    return key->d_rows30 ? FHE_TGGSW_FORM_30 : FHE_TGGSW_FORM_60;
+}
+
 // f(Type<Form>{}, key_arg, lds_bytes) for the form `key` is in: Form the policy over the key's ring, key_arg its Form::Key with the rows
 // offset to entry first_index, lds_bytes the dynamic LDS of a workgroup.  ALLOW_PACKED: a 30-bit key may run the CMUX whose digits are
 // computed once; the callers whose kernels run the plain external product (and the key fill) pass false.
@@ -43,10 +60,7 @@ int with_key_form(const fhe_torus_ctx *t, const fhe_tggsw_key *key, size_t first
         });
     }
     if (key->d_rows30) {  // three 30-bit primes
-        // base <= 2^7 and at most 8 limbs (cfg5: base 2^7, d = 3): the CMUX digits are computed once and parked as bytes, the
-        // multiply-accumulate runs unreduced (torus30_kernels.hpp); lab switch NO_PACKED_DIGITS keeps the older kernel (bit-identical)
-        // (a digit of base 2^8 ranges over [-128, 128]: one value too many for a byte)
-        const bool packed = ALLOW_PACKED && P.log_b <= 7 && 2 * key->d <= 8 && key->log_n >= 8 && fhe::opt(fhe::OPT_NO_PACKED_DIGITS) == 0;
+        const bool packed = ALLOW_PACKED && key_packs_digits(key);
         return with_torus<TorusRing30>(key->log_n, [&](auto wr) {
             auto run = [&](auto pk) {
                 using Form = fhe::Form30<typename decltype(wr)::type, decltype(pk)::value>;

@@ -889,6 +889,24 @@ class TggswKey:
         if h and L is not None and getattr(L, "lib", None):  # (module globals are gone at interpreter shutdown)
             L.lib().fhe_tggsw_key_destroy(h)
 
+    FORMS = {0: "60", 1: "30", 2: "fft64", 3: "x3"}  # FHE_TGGSW_FORM_* (include/fhe_ring.h)
+
+    def _key_form(self):
+        form, packs = C.c_int(), C.c_int()
+        L.check(L.lib().fhe_tggsw_key_form(self._h, C.byref(form), C.byref(packs)), "fhe_tggsw_key_form")
+        return form.value, packs.value
+
+    @property
+    def form(self):
+        """fhe_tggsw_key_form: "60" (two 60-bit primes), "30" (three 30-bit primes), "fft64", "x3" (three key pieces through f64 transforms)"""
+        return self.FORMS[self._key_form()[0]]
+
+    @property
+    def packs_digits(self):
+        """1 exactly when a blind rotation or look-up ladder launched now on this key would run the packed-digit 30-bit CMUX (reads the
+        lab switch NO_PACKED_DIGITS as the launch would), else 0"""
+        return self._key_form()[1]
+
     def external_product_(self, index, ct_a, ct_b):
         pa, cnt, mem, st = _buf(ct_a)
         pb, _, _, _ = _buf(ct_b)

@@ -148,9 +148,10 @@ def test_pfksk_gen_rows(fhe, torch_cuda):
     assert np.array_equal(ha.reshape(key0.shape), key0)             # host memory: the same key
 
 
-# exact key forms fhe_tggsw_prepare can be steered to: (15, 1) at n = 256 and (23, 1) at n = 1024: two 60-bit primes; (7, 3): three key pieces
-# through f64 transforms; (10, 2): three 30-bit primes
+# exact key forms fhe_tggsw_prepare can be steered to: (23, 1) at n = 1024: two 60-bit primes; (7, 3): three key pieces through f64
+# transforms; (10, 2), and (15, 1) at n = 256 (bound 2^87): three 30-bit primes.  FORM_OF: what fhe_tggsw_key_form must report for each
 KEY_FORMS = [(256, 15, 1), (256, 7, 3), (256, 10, 2), (1024, 7, 3), (1024, 10, 2), (1024, 23, 1)]
+FORM_OF = dict(zip(KEY_FORMS, ["30", "x3", "30", "x3", "30", "60"]))
 
 
 @pytest.mark.parametrize("n,log_b,d", KEY_FORMS)
@@ -166,6 +167,7 @@ def test_circuit_bootstrap_equals_the_chain_and_the_model(fhe, torch_cuda, n, lo
     D = lambda x: dev(torch_cuda, x)  # noqa: E731
     dk = D(pfksk)
     keys = {f: fhe.TggswKey(t, log_b, d, D(bra), D(brb), n, fft64=f) for f in (False, True)}
+    assert (keys[False].form, keys[True].form) == (FORM_OF[(n, log_b, d)], "fft64")
     for cb_log_b, cb_d in [(8, 2), (6, 3), (4, 4)]:
         table = D(C.cbs_table(cb_log_b, cb_d, n))
         for batch in (1, 5):

@@ -67,6 +67,42 @@ def test_model_reads_the_table_at_every_address(m):
         assert M.lookup(polys, m, n_out, address) == [int(table[o, address]) for o in range(n_out)], address
 
 
+@pytest.mark.parametrize("m,n_out", [(10, 2), (3, 5)])
+def test_ciphertext_model_reads_the_table_under_trivial_selectors(cref, m, n_out):
+    """A check of the CIPHERTEXT-level model (tfhe_lut_model.lut_eval_ciphertexts: the walk of lut_eval_batch_steps on the exact oracle's
+    external product, rotation, extraction and key switch) against the plain model: selectors that are TRIVIAL TGGSW ciphertexts -- every row
+    zero, plus bit x base_j on the gadget diagonal -- under the 64-bit gadget (16, 4), which rounds nothing away, make every CMUX exactly the
+    choice its bit encodes; the output phases b - <a, s> (under any key s: a stays 0) are then M.lookup's values.  n = 256; m = 10: a tree of
+    four leaves per accumulator, then 8 ladder steps; m = 3: no tree, five outputs share one accumulator; two unused selectors in front"""
+    n, log_b, d, first = 256, 16, 4, 2
+    rng = np.random.Generator(np.random.PCG64(7050 + m))
+    table = rng.integers(0, 1 << 63, size=(n_out, 1 << m), dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, size=(n_out, 1 << m), dtype=np.uint64)
+    polys = M.pack(table, m, n)
+    top = (1 << m) - 1
+    addresses = [0, top, top // 3, 2 * (top // 3), top - 2]                  # m = 10: leaves 0, 3, 1, 2, 3
+    batch = len(addresses)
+    bases = [1 << (64 - log_b * d + j * log_b) for j in range(d)]           # decompose.rs:66-81: least significant digit first
+    rows_a, rows_b = np.zeros((first + batch * m, 2 * d, n), dtype=np.uint64), np.zeros((first + batch * m, 2 * d, n), dtype=np.uint64)
+    bits = [1] * first + [(x >> l) & 1 for x in addresses for l in range(m)]  # noqa: E741
+    for i, bit in enumerate(bits):
+        for j, base in enumerate(bases):                                    # tggsw.rs:73-88: m g_j on a in rows 0 .. d, on b in rows d .. 2d
+            rows_a[i, j, 0] = rows_b[i, d + j, 0] = np.uint64(bit * base)
+    oa, ob = M.lut_eval_ciphertexts(cref, polys, log_b, d, rows_a, rows_b, first, m, n_out, batch, threads=4)
+    assert oa.shape == (batch, n_out, n) and ob.shape == (batch, n_out)
+    s = rng.integers(0, 2, size=n, dtype=np.uint64)
+    phases = ob - (oa * s).sum(axis=-1, dtype=np.uint64)
+    for c, x in enumerate(addresses):
+        want = M.lookup(polys, m, n_out, x)
+        assert want == [int(table[o, x]) for o in range(n_out)]
+        assert [int(v) for v in phases[c]] == want, hex(x)
+    # the key switch of the model is the oracle's, output by output
+    ks = (4, 3, rng.integers(0, 1 << 63, size=(n * 3, 6), dtype=np.uint64), rng.integers(0, 1 << 63, size=n * 3, dtype=np.uint64), 6)
+    ka, kb = M.lut_eval_ciphertexts(cref, polys, log_b, d, rows_a, rows_b, first, m, n_out, 2, ks=ks)
+    assert ka.shape == (2, n_out, 6) and kb.shape == (2, n_out)
+    wa, wb = cref.tlwe_key_switch(4, 3, ks[2], ks[3], oa[1, n_out - 1], int(ob[1, n_out - 1]))
+    assert np.array_equal(ka[1, n_out - 1], wa) and int(kb[1, n_out - 1]) == wb
+
+
 def test_model_rotation_is_negacyclic():
     p = np.arange(1, 9, dtype=np.uint64)
     assert list(M.rotate(p, -3)) == [4, 5, 6, 7, 8, M.M64 - 1, M.M64 - 2, M.M64 - 3]     # X^-k: coefficient j + k comes to j unsigned

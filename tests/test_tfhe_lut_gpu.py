@@ -96,12 +96,14 @@ def test_exact_plain_result(fhe, torch_cuda, exact_keys, m, n_out, batch):
         fhe.set_option("LUT_EXTRACT", 0)
 
 
-# exact key forms fhe_tggsw_prepare can be steered to (tests/test_tfhe_cbs_gpu.py): (15, 1) at n = 256 and (23, 1) at n = 1024: two 60-bit
-# primes; (7, 3): three key pieces through f64 transforms; (10, 2): three 30-bit primes.  The seventh entry prepares (7, 3) with the f64 route
-# switched off: three 30-bit primes with the digits computed once (the packed form), on a one-wave team (n = 256) and on a team of several
-# waves (n = 1024: the per-team LDS stride then carries the digit area)
+# exact key forms fhe_tggsw_prepare can be steered to: (23, 1) at n = 1024: two 60-bit primes; (7, 3): three key pieces through f64 transforms;
+# (10, 2), and (15, 1) at n = 256 (bound 2d N 2^(62 + log_b) = 2^87): three 30-bit primes, unpacked (base > 2^7).  The last two entries prepare
+# (7, 3) with the f64 route switched off: three 30-bit primes with the digits computed once (the packed form), on a one-wave team (n = 256)
+# and on a team of several waves (n = 1024: the per-team LDS stride then carries the digit area).  FORM_OF has what each entry must report
+# (fhe_tggsw_key_form): (form, packs_digits); tests/test_tfhe_forms_gpu.py runs every form at every ring size against the oracle
 KEY_FORMS = [(256, 15, 1, False), (256, 7, 3, False), (256, 10, 2, False), (1024, 7, 3, False), (1024, 10, 2, False), (1024, 23, 1, False),
              (256, 7, 3, True), (1024, 7, 3, True)]
+FORM_OF = dict(zip(KEY_FORMS, [("30", 0), ("x3", 0), ("30", 0), ("x3", 0), ("30", 0), ("60", 0), ("30", 1), ("30", 1)]))
 
 
 @pytest.mark.parametrize("n,log_b,d,no_f64", KEY_FORMS)
@@ -126,6 +128,7 @@ def test_bit_identity_with_the_chain(fhe, torch_cuda, n, log_b, d, no_f64):
         keys = {f: fhe.TggswKey(t, log_b, d, D(ra), D(rb), n, fft64=f) for f in (False, True)}
     finally:
         fhe.set_option("NO_F64_EXACT", 0)
+    assert (keys[False].form, keys[False].packs_digits) == FORM_OF[(n, log_b, d, no_f64)] and (keys[True].form, keys[True].packs_digits) == ("fft64", 0)
     polys = C.lut_pack(table, m, n)
     dp, dks = D(polys), (ks_log_b, ks_d, D(ksk_a), D(ksk_b), n_lwe_out)
     for fft64 in (False, True):
@@ -149,6 +152,7 @@ def test_bit_identity_with_the_chain(fhe, torch_cuda, n, log_b, d, no_f64):
     if no_f64:  # the older three-prime kernel: the same bits
         try:
             fhe.set_option("NO_PACKED_DIGITS", 1)
+            assert keys[False].packs_digits == 0
             pa, pb = C.lut_eval_batch(dp, keys[False], first, m, n_out, batch, dks)
         finally:
             fhe.set_option("NO_PACKED_DIGITS", 0)

@@ -83,6 +83,11 @@ def test_library_rejections_need_no_device(fhe):
     assert lib.fhe_tggsw_key_reserve(None, 7, 3, 256, 4, 0, C.byref(h)) == 1 and not h.value
     assert lib.fhe_tggsw_key_reserve(None, 7, 3, 256, 4, 0, None) == 1
     assert lib.fhe_tggsw_key_fill(None, 0, v, v, 1, 0, None) == 1
+    form, packs = C.c_int(-1), C.c_int(-1)
+    assert lib.fhe_tggsw_key_form(None, C.byref(form), C.byref(packs)) == 1 and (form.value, packs.value) == (-1, -1)
+    assert lib.fhe_tggsw_key_form(None, None, None) == 1
+    # (a key needs a device: NULL outputs beside a live key are rejected in tests/test_tfhe_forms_gpu.py)
+    assert hasattr(fhe.TggswKey, "form") and hasattr(fhe.TggswKey, "packs_digits")
 
 
 @pytest.mark.parametrize("m", [1, 2, 8, 16])

@@ -17,9 +17,12 @@ M64 = 1 << 64
 U = lambda x: np.array(x, dtype=np.uint64)  # noqa: E731
 r64 = M.r64
 
-# the key forms of tests/test_tfhe_lut_gpu.py: (n, log_b, d, NO_F64_EXACT while the key is made)
+# the key forms of tests/test_tfhe_lut_gpu.py: (n, log_b, d, NO_F64_EXACT while the key is made); FORM_OF: what fhe_tggsw_key_form must report
+# for each, (form, packs_digits): (15, 1) at n = 256 and (10, 2): three 30-bit primes, unpacked; (7, 3): three key pieces through f64
+# transforms, and with the switch three 30-bit primes with packed digits; (23, 1): two 60-bit primes
 KEY_FORMS = [(256, 15, 1, False), (256, 7, 3, False), (256, 10, 2, False), (1024, 7, 3, False), (1024, 10, 2, False), (1024, 23, 1, False),
              (256, 7, 3, True), (1024, 7, 3, True)]
+FORM_OF = dict(zip(KEY_FORMS, [("30", 0), ("x3", 0), ("30", 0), ("x3", 0), ("30", 0), ("60", 0), ("30", 1), ("30", 1)]))
 
 
 @pytest.fixture(scope="module")
@@ -67,6 +70,8 @@ def test_fill_equals_prepare(fhe, torch_cuda, n, log_b, d, no_f64, fft64):
     with steered(fhe, no_f64):
         prepared = fhe.TggswKey(t, log_b, d, ra, rb, n, fft64=fft64)
         reserved = fhe.TggswKey.reserve(t, log_b, d, n, 3, fft64=fft64)
+    want_form = ("fft64", 0) if fft64 else FORM_OF[(n, log_b, d, no_f64)]
+    assert (prepared.form, prepared.packs_digits) == want_form and (reserved.form, reserved.packs_digits) == want_form
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
@@ -195,6 +200,8 @@ def test_bit_identity_with_the_chain(fhe, torch_cuda, n, log_b, d, no_f64):
     with steered(fhe, no_f64):
         brk = {f: fhe.TggswKey(t, log_b, d, D(bra), D(brb), n, fft64=f) for f in (False, True)}
         sel = {f: fhe.TggswKey.reserve(t, cb_log_b, cb_d, n, cap, fft64=f) for f in (False, True)}
+    for k in (brk, sel):
+        assert (k[False].form, k[False].packs_digits) == FORM_OF[(n, log_b, d, no_f64)] and (k[True].form, k[True].packs_digits) == ("fft64", 0)
     for m in ms:
         polys = C.lut_pack(r64(rng, n_out, 1 << m), m, n)
         dp = D(polys)

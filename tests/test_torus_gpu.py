@@ -259,6 +259,7 @@ def test_external_product_at_the_path_boundary(fhe, torch_cuda, log_b, d):
     ra = [[[big] * n for _ in range(2 * d)]]
     rb = [[[big if (i + r) % 3 else (1 << 63) - 1 for i in range(n)] for r in range(2 * d)]]
     key = fhe.TggswKey(t, log_b, d, dev(torch_cuda, U(ra)), dev(torch_cuda, U(rb)), n)
+    assert (key.form, key.packs_digits) == ({15: "30", 16: "60"}[log_b], 0)  # the two sides of the boundary
     # torus values whose every digit is -2^(log_b-1) (the most negative balanced digit): sum_j (-B/2) B^j scaled to the top bits
     half = 1 << (log_b - 1)
     v = (-sum(half << (64 - log_b * (j + 1)) for j in range(d))) % (1 << 64)
@@ -292,6 +293,7 @@ def test_tggsw_external_product_n1024_vs_oracle(fhe, cref, torch_cuda, log_b, d,
     cb[1, :] = np.uint64((-sum(half << (64 - log_b * (j + 1)) for j in range(d))) % (1 << 64))  # every digit at its extreme
     t = fhe.TorusContext()
     key = fhe.TggswKey(t, log_b, d, dev(torch_cuda, ra), dev(torch_cuda, rb), n)
+    assert key.form == {"three key pieces": "x3", "three 30-bit primes": "30", "two 60-bit primes": "60"}[path.split(" through")[0]]  # the path named above
     for idx in range(count):
         a, b = dev(torch_cuda, ca), dev(torch_cuda, cb)
         key.external_product_(idx, a, b)
@@ -381,8 +383,9 @@ def test_exact_f64_path_whole_cfg5_blind_rotations_equal_the_integer_path(fhe, t
 @pytest.mark.parametrize("log_b,d,n_lwe,batch", [(7, 3, 10, 7), (23, 1, 8, 7), (7, 3, 4, 1100), (23, 1, 3, 600)])
 def test_blind_rotate_n1024_vs_oracle(fhe, cref, torch_cuda, log_b, d, n_lwe, batch):
     """scheme/tfhe/src/bootstrapping.rs:84-104 at N = 1024 (cfg5's ring): mod switch, the whole CMUX chain, sample extract and the
-    TLWE key switch, bit-equal to the exact oracle on both prime paths; small batches and batches that fill the GPU (every
-    ciphertext of the small ones, a spread sample of the large ones, their first and last included)"""
+    TLWE key switch, bit-equal to the exact oracle on the three-piece f64 form ((7, 3), cfg5's gadget) and on two 60-bit primes ((23, 1));
+    small batches and batches that fill the GPU (every ciphertext of the small ones, a spread sample of the large ones, their first and
+    last included).  The three 30-bit primes at this ring: tests/test_tfhe_forms_gpu.py"""
     n, ks_log_b, ks_d = 1024, 4, 5
     rng = np.random.Generator(np.random.PCG64(2000 + log_b + batch))
     r64 = lambda *shape: rng.integers(0, 1 << 63, size=shape, dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, size=shape, dtype=np.uint64)  # noqa: E731
@@ -392,6 +395,7 @@ def test_blind_rotate_n1024_vs_oracle(fhe, cref, torch_cuda, log_b, d, n_lwe, ba
     a_raw[0, 0] = np.uint64((1 << 64) - 1)                # rounds up to 2N = 0 (mod 2N)
     t = fhe.TorusContext()
     key = fhe.TggswKey(t, log_b, d, dev(torch_cuda, bra), dev(torch_cuda, brb), n)
+    assert (key.form, key.packs_digits) == ({7: "x3", 23: "60"}[log_b], 0)
     at = fhe.TorusContext.mod_switch(dev(torch_cuda, a_raw), n)
     bt = fhe.TorusContext.mod_switch(dev(torch_cuda, b_raw), n)
     assert np.array_equal(host(at).reshape(batch, n_lwe), cref.tfhe_mod_switch(a_raw, n)) and np.array_equal(host(bt), cref.tfhe_mod_switch(b_raw, n))
@@ -504,12 +508,17 @@ def test_cmux_and_rotate_entries(fhe, torch_cuda, log_n, log_b, d):
 
 @pytest.mark.parametrize("log_n,log_b,d,batch", [(10, 7, 3, 5), (10, 7, 4, 3), (10, 8, 3, 2), (9, 6, 2, 4), (8, 4, 4, 6), (11, 7, 2, 2)])
 def test_packed_digit_blind_rotation_equals_the_unpacked_one(fhe, torch_cuda, log_n, log_b, d, batch):
-    """Gadgets of base <= 2^7 (a digit of base 2^8 reaches +128: no byte) and at most 8 limbs run the blind rotation with each CMUX's digits computed once and parked as bytes, and
-    the multiply-accumulate unreduced (torus30_kernels.hpp, `_pk` kernels); the lab switch NO_PACKED_DIGITS keeps the kernel that
-    decomposes once per prime.  Same integers, same CRT: bit-identical accumulators -- incl. extreme inputs (digits at both ends of
-    their range, key words -2^63) -- and (cfg5's shape) equal to the exact oracle."""
+    """Three-prime keys (made under the lab switch NO_F64_EXACT: fhe_tggsw_prepare would otherwise take the three-piece f64 form for five of
+    these six shapes) with gadgets of base <= 2^7 and at most 8 limbs run the blind rotation with each CMUX's digits computed once and parked
+    as bytes, and the multiply-accumulate unreduced (torus30_kernels.hpp, `_pk` kernels); the lab switch NO_PACKED_DIGITS keeps the kernel
+    that decomposes once per prime: the key reports the change (packs_digits 1 -> 0).  (10, 8, 3) never packs -- a digit of base 2^8 reaches
+    +128: no byte -- and reports 0 in both runs.  Same integers, same CRT: bit-identical accumulators -- incl. extreme inputs (digits at both
+    ends of their range, key words -2^63) -- and (cfg5's shape) equal to the exact oracle.  tests/test_tfhe_forms_gpu.py pins the packed
+    kernel against the oracle at every ring size."""
     from oracle import cref
     n, n_lwe = 1 << log_n, 7
+    packs = int(log_b <= 7 and 2 * d <= 8)
+    assert packs == (0 if (log_n, log_b, d) == (10, 8, 3) else 1)
     rng = np.random.Generator(np.random.PCG64(100 + log_n + d))
     r64 = lambda *s: rng.integers(0, 1 << 63, size=s, dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, size=s, dtype=np.uint64)  # noqa: E731
     ra, rb, v = r64(n_lwe, 2 * d, n), r64(n_lwe, 2 * d, n), r64(n)
@@ -520,11 +529,17 @@ def test_packed_digit_blind_rotation_equals_the_unpacked_one(fhe, torch_cuda, lo
     a_t[0, 0] = 0                                          # a rotation by zero short-circuits
     b_t = rng.integers(0, 2 * n, size=batch, dtype=np.uint64)
     t = fhe.TorusContext()
-    key = fhe.TggswKey(t, log_b, d, dev(torch_cuda, ra), dev(torch_cuda, rb), n)
+    fhe.set_option("NO_F64_EXACT", 1)
+    try:
+        key = fhe.TggswKey(t, log_b, d, dev(torch_cuda, ra), dev(torch_cuda, rb), n)
+    finally:
+        fhe.set_option("NO_F64_EXACT", 0)
+    assert key.form == "30"
     outs = []
     for off in (0, 1):  # the packed kernel | the older one
         fhe.set_option("NO_PACKED_DIGITS", off)
         try:
+            assert key.packs_digits == (packs if off == 0 else 0)
             outs.append(key.blind_rotate(dev(torch_cuda, a_t), dev(torch_cuda, b_t), dev(torch_cuda, v)))
         finally:
             fhe.set_option("NO_PACKED_DIGITS", 0)

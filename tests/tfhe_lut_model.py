@@ -1,6 +1,9 @@
 """Plain model of the vertically packed table look-up (csrc/tfhe_lut.hpp, fhe_tfhe_lut_eval): the shape, the packing, and the values the
 packed polynomials take under an IDEAL tree and rotation -- every CMUX replaced by the choice its selector bit encrypts, on plaintext
-polynomials over Z / 2^64 [X] / (X^n + 1).  Python integers and numpy only; runs no library code."""
+polynomials over Z / 2^64 [X] / (X^n + 1).  Python integers and numpy only; runs no library code.
+
+The last section is the CIPHERTEXT-level model (lut_eval_ciphertexts): the same walk on TGLWE ciphertexts under arbitrary TGGSW rows, every
+step the exact oracle's (oracle/cref.py) -- what fhe_tfhe_lut_eval must give bit for bit in every exact key form."""
 import numpy as np
 
 M64 = 1 << 64
@@ -66,3 +69,65 @@ def lookup(polys, m, n_out, address):
     per_acc = max(1, n >> m)
     acc = accumulators(polys, m, address)
     return [int(acc[o // per_acc, (o % per_acc) << m]) for o in range(n_out)]
+
+
+# ---- ciphertext level: learn-fhe_amd/tfhe_cbs.py `lut_eval_batch_steps` step for step, the device entries replaced by the exact oracle ----
+
+def cmux(cref, log_b, d, rows_a, rows_b, c0a, c0b, c1a, c1b):
+    """tggsw.rs:114-121: ct0 + external_product(rows, ct1 - ct0); rows_* [2d][n], one ciphertext (uint64 arithmetic wraps)"""
+    ea, eb = cref.tggsw_external_product(log_b, d, rows_a, rows_b, c1a - c0a, c1b - c0b)
+    return c0a + ea, c0b + eb
+
+
+def lut_extractions(cref, polys, log_b, d, rows_a, rows_b, first_index, m, n_out, batch, threads=1):
+    """polys [n_acc][2^h][n] (pack), rows_a / rows_b [count][2d][n]: the selectors, ciphertext c reads first_index + c m + l.
+    -> (a [batch][n_out][n], b [batch][n_out]): the TLWE extractions in front of the key switch.  Ciphertexts are independent: `threads`
+    of them run at a time (the oracle's C calls release the interpreter lock)"""
+    from concurrent.futures import ThreadPoolExecutor
+    polys = np.asarray(polys, dtype=np.uint64)
+    n = polys.shape[-1]
+    r, h, per_acc, n_acc, n_polys = shape(m, n_out, n)
+    assert polys.size == n_polys * n and first_index + batch * m <= len(rows_a)
+
+    def one(c):
+        base = first_index + c * m
+        cur_a, cur_b = list(np.zeros((n_polys, n), dtype=np.uint64)), list(polys.reshape(n_polys, n))
+        for v in range(h):                                                   # tree level v: node p <- CMUX(bit r + v; node 2p, node 2p + 1)
+            ka, kb = rows_a[base + r + v], rows_b[base + r + v]
+            nxt = [cmux(cref, log_b, d, ka, kb, cur_a[2 * p], cur_b[2 * p], cur_a[2 * p + 1], cur_b[2 * p + 1]) for p in range(len(cur_a) // 2)]
+            cur_a, cur_b = [x[0] for x in nxt], [x[1] for x in nxt]
+        assert len(cur_a) == n_acc
+        for l in range(r):                                                   # noqa: E741  ladder step l: acc <- CMUX(bit l; acc, acc X^(-2^l))
+            ka, kb = rows_a[base + l], rows_b[base + l]
+            for g in range(n_acc):
+                ra, rb = cref.torus_monomial_mul(cur_a[g], -(1 << l)), cref.torus_monomial_mul(cur_b[g], -(1 << l))
+                cur_a[g], cur_b[g] = cmux(cref, log_b, d, ka, kb, cur_a[g], cur_b[g], ra, rb)
+        ea, eb = np.zeros((n_out, n), dtype=np.uint64), np.zeros(n_out, dtype=np.uint64)
+        for o in range(n_out):                                               # output o: coefficient u 2^m of accumulator g
+            g, u = divmod(o, per_acc)
+            ea[o], eb[o] = cref.tglwe_sample_extract(cur_a[g], cur_b[g], u << m)
+        return ea, eb
+
+    if threads > 1 and batch > 1:
+        with ThreadPoolExecutor(max_workers=min(threads, batch)) as pool:
+            res = list(pool.map(one, range(batch)))
+    else:
+        res = [one(c) for c in range(batch)]
+    return np.stack([x[0] for x in res]), np.stack([x[1] for x in res])
+
+
+def lut_key_switch(cref, ext_a, ext_b, ks):
+    """ks = (log_b, d, ksk_a [n d][n_lwe_out], ksk_b [n d], n_lwe_out): tlwe.rs:144-153 on every extraction -> (a [batch][n_out][n_lwe_out], b)"""
+    log_b, d, ksk_a, ksk_b, width = ks
+    batch, n_out = ext_b.shape
+    oa, ob = np.zeros((batch, n_out, width), dtype=np.uint64), np.zeros((batch, n_out), dtype=np.uint64)
+    for c in range(batch):
+        for o in range(n_out):
+            oa[c, o], ob[c, o] = cref.tlwe_key_switch(log_b, d, ksk_a, ksk_b, ext_a[c, o], int(ext_b[c, o]))
+    return oa, ob
+
+
+def lut_eval_ciphertexts(cref, polys, log_b, d, rows_a, rows_b, first_index, m, n_out, batch, ks=None, threads=1):
+    """fhe_tfhe_lut_eval on the CPU -> (a [batch][n_out][n_lwe_out or n], b [batch][n_out])"""
+    ea, eb = lut_extractions(cref, polys, log_b, d, rows_a, rows_b, first_index, m, n_out, batch, threads)
+    return lut_key_switch(cref, ea, eb, ks) if ks else (ea, eb)
