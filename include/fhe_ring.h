@@ -37,7 +37,7 @@ enum {
     FHE_ERR_HIP = 5,          /* a HIP runtime call failed; fhe_last_hip_error() has the code */
     FHE_ERR_UNSUPPORTED = 6,  /* valid in the reference, outside what this build implements (q >= 2^62, n > 2^17) */
     FHE_ERR_NO_DEVICE = 7,    /* compute call on a host-only context */
-    FHE_ERR_TIMEOUT = 8       /* a bounded wait between the workgroups of one launch ran out (split FHEW blind rotation): no output written */
+    FHE_ERR_TIMEOUT = 8       /* a bounded wait between the workgroups of one launch ran out (split FHEW or TFHE blind rotation): no output written */
 };
 
 typedef enum { FHE_MEM_HOST = 0, FHE_MEM_DEVICE = 1 } fhe_mem;
@@ -61,7 +61,10 @@ int fhe_trim(void);
  * fhe_blind_rotate_split tells what a call will run), "PFKS_SPLIT" (fhe_tlwe_pfks: 0 = the library's rule, 1 = one block walks all
  * input rows of its tile, k >= 2 = k blocks share them and add their partial sums), "PFKS_CHUNK" (fhe_tlwe_pfks: input coefficients whose digits a block
  * keeps in LDS at a time; 0 = the library's rule), "LUT_EXTRACT" (fhe_tfhe_lut_eval: 0 = the library's rule, 1 = the rotation ladder writes the
- * extractions from its registers, 2 = a kernel of its own reads the stored accumulators).  Unknown name: FHE_ERR_INVALID. */
+ * extractions from its registers, 2 = a kernel of its own reads the stored accumulators), "TFHE_SPLIT" (TFHE blind rotation: workgroups per
+ * ciphertext; -1 = the library's rule, 0 = never split, 2 / 6 = that many wherever the call is eligible -- a key in the x3 form at
+ * n = 1024, batch x value <= compute units of the device -- and one workgroup per ciphertext elsewhere; any other value:
+ * FHE_ERR_INVALID; fhe_tfhe_blind_rotate_split tells what a call will run).  Unknown name: FHE_ERR_INVALID. */
 int fhe_set_option(const char *name, long value);
 
 /* Entry points that take a modulus instead of a context (fhe_rq_*, fhe_decompose, fhe_automorphism, fhe_monomial_mul,
@@ -350,6 +353,20 @@ enum {
  * the 30-bit CMUX whose digits are computed once and parked as bytes (form 30, base <= 2^7, 2d <= 8, lab switch NO_PACKED_DIGITS off: the
  * switch is read as the launch reads it), else 0.  A NULL key or a NULL output: FHE_ERR_INVALID.  Touches no device. */
 int fhe_tggsw_key_form(const fhe_tggsw_key *key, int *form, int *packs_digits);
+/* Workgroups per ciphertext (*g_out = 1, 2 or 6) that a blind rotation of `batch` ciphertexts under brk would use with the options as
+ * they are ("TFHE_SPLIT"): fhe_tfhe_blind_rotate, _tables and every entry that contains one (fhe_tfhe_bootstrap, _tables, _many, the
+ * circuits, the circuit bootstrap, fhe_tfhe_wop_pbs) ask the same rule.  Above 1 a cluster of workgroups owns each ciphertext: each
+ * member computes one output of every CMUX (2) or one key piece of one output (6) and the members add each other's shares inside the
+ * launch -- lower latency at batches that leave the chip idle, bit-identical results.  Eligible: a key in the x3 form at n = 1024 and
+ * batch x G <= compute units.  The waits are bounded: one that runs out writes no output and the call reports FHE_ERR_TIMEOUT --
+ * fhe_tfhe_blind_rotate, _tables, fhe_tfhe_bootstrap, _tables and _many on host memory in their return value (a word of the call's own),
+ * everything else through fhe_tggsw_key_status.  Touches no device beyond the context's compute-unit count.  A NULL argument, or a key
+ * of another context: FHE_ERR_INVALID. */
+int fhe_tfhe_blind_rotate_split(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, size_t batch, int *g_out);
+/* Waits for everything enqueued on `stream`, then FHE_ERR_TIMEOUT if a split blind rotation of a device-memory call on this key gave up
+ * a wait since the word was last cleared, else FHE_OK; clear != 0 resets the word (in stream order).  The word lives with the key;
+ * host-memory calls neither set nor clear it.  A key in a form that never splits is always FHE_OK. */
+int fhe_tggsw_key_status(const fhe_tggsw_key *key, void *stream, int clear);
 /* scheme/tfhe/src/tggsw.rs:100-112 `Tggsw::external_product(param, key[index], ct)`, in place on [batch][n] a / b. */
 int fhe_tggsw_external_product(const fhe_torus_ctx *t, const fhe_tggsw_key *key, size_t index, uint64_t *ct_a, uint64_t *ct_b,
                                size_t batch, fhe_mem mem, void *stream);

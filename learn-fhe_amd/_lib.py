@@ -157,6 +157,8 @@ def lib():
         L.fhe_tggsw_key_reserve.argtypes = [vp, ci, ci, sz, sz, ci, C.POINTER(vp)]
         L.fhe_tggsw_key_fill.argtypes = [vp, sz, vp, vp, sz, ci, vp]
         L.fhe_tggsw_key_form.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]
+        L.fhe_tggsw_key_status.argtypes = [vp, vp, ci]
+        L.fhe_tfhe_blind_rotate_split.argtypes = [vp, vp, sz, C.POINTER(ci)]
         L.fhe_torus_ctx_create.argtypes = [ci, C.POINTER(vp)]
         L.fhe_torus_ctx_destroy.argtypes = [vp]
         L.fhe_torus_ctx_destroy.restype = None

@@ -12,6 +12,7 @@
 
 #include "../../include/fhe_ring.h"
 #include "dev_arith.hpp"
+#include "tfhe_split.hpp"
 
 namespace fhe {
 inline thread_local int g_last_hip = 0;
@@ -111,13 +112,20 @@ namespace fhe {
 // PFKS_SPLIT: blocks that share the input rows of one output tile of fhe_tlwe_pfks (pfks_kernels.hpp): 0 the library's rule, 1 never split,
 // k >= 2: k blocks where the rows allow it.  PFKS_CHUNK: input coefficients whose digits a block keeps in LDS at a time: 0 the library's
 // rule, c >= 1: at most c.
+// TFHE_SPLIT: workgroups per ciphertext of the TFHE blind rotation (torus_split_kernels.hpp): -1 the library's rule, 0 never split, 2 / 6.
 // LUT_EXTRACT: who writes the extractions of fhe_tfhe_lut_eval: 0 the library's rule, 1 the rotation ladder from its registers, 2 a kernel
 // of its own that reads the stored accumulators (tfhe_lut_kernels.hpp).
 enum Opt { OPT_NO_EDGE = 0, OPT_NO_LIMB_MAJOR, OPT_NO_W12, OPT_NO_FUSED_MUL, OPT_SMALL_BATCH, OPT_NO_PACKED_DIGITS, OPT_NO_F64_EXACT, OPT_FHEW_COMPOSED,
-           OPT_BR_SPLIT, OPT_PFKS_SPLIT, OPT_PFKS_CHUNK, OPT_LUT_EXTRACT, OPT_COUNT };
+           OPT_BR_SPLIT, OPT_PFKS_SPLIT, OPT_PFKS_CHUNK, OPT_LUT_EXTRACT, OPT_TFHE_SPLIT, OPT_COUNT };
 inline const char *const OPT_NAMES[OPT_COUNT] = {"NO_EDGE", "NO_LIMB_MAJOR", "NO_W12", "NO_FUSED_MUL", "SMALL_BATCH", "NO_PACKED_DIGITS", "NO_F64_EXACT",
-                                                 "FHEW_COMPOSED", "BR_SPLIT", "PFKS_SPLIT", "PFKS_CHUNK", "LUT_EXTRACT"};
+                                                 "FHEW_COMPOSED", "BR_SPLIT", "PFKS_SPLIT", "PFKS_CHUNK", "LUT_EXTRACT", "TFHE_SPLIT"};
 inline bool br_split_value_ok(long v) { return v == -1 || v == 0 || v == 2 || v == 4 || v == 8; }
+// the values an option admits (tfhe_split.hpp states TFHE_SPLIT's); the others take any
+inline bool opt_value_ok(int i, long v) {
+    if (i == OPT_BR_SPLIT) return br_split_value_ok(v);
+    if (i == OPT_TFHE_SPLIT) return tfhe_split_value_ok(v);
+    return true;
+}
 struct Options {
     std::atomic<long> v[OPT_COUNT];
     Options() {
@@ -125,8 +133,8 @@ struct Options {
             char name[64] = "FHE_RING_";
             std::strncat(name, OPT_NAMES[i], sizeof(name) - 10);
             const char *e = std::getenv(name);
-            long val = e ? std::atol(e) : ((i == OPT_SMALL_BATCH || i == OPT_BR_SPLIT) ? -1L : 0L);
-            if (i == OPT_BR_SPLIT && !br_split_value_ok(val)) val = -1L;
+            long val = e ? std::atol(e) : ((i == OPT_SMALL_BATCH || i == OPT_BR_SPLIT || i == OPT_TFHE_SPLIT) ? -1L : 0L);
+            if (!opt_value_ok(i, val)) val = -1L;
             v[i].store(val, std::memory_order_relaxed);
         }
     }

@@ -267,7 +267,7 @@ int fhe_set_option(const char *name, long value) {
         const char *a = name, *b = fhe::OPT_NAMES[i];
         while (*a && *b && (*a == *b || *a - 32 == *b)) { ++a; ++b; }
         if (!*a && !*b) {
-            if (i == fhe::OPT_BR_SPLIT && !fhe::br_split_value_ok(value)) return FHE_ERR_INVALID;
+            if (!fhe::opt_value_ok(i, value)) return FHE_ERR_INVALID;
             fhe::options().v[i].store(value, std::memory_order_relaxed);
             return FHE_OK;
         }

@@ -11,6 +11,7 @@
 #include "torus_ctx.hpp"
 #include "dispatch.hpp"
 #include "torus_dispatch.hpp"
+#include "torus_split_kernels.hpp"
 #include "lwe_kernels.hpp"
 #include "keygen_kernels.hpp"
 #include "tfhe_circuit_kernels.hpp"
@@ -298,7 +299,8 @@ int fhe_tggsw_prepare(const fhe_torus_ctx *t, int log_b, int d, const uint64_t *
     if (e != hipSuccess) g_last_hip = (int)e;
     double2 *dstx3 = nullptr;
     if (rc == FHE_OK && usex3) {
-        if (hipMalloc((void **)&dstx3, 6 * rows * (n / 2) * sizeof(double2)) != hipSuccess) rc = FHE_ERR_HIP;
+        if (hipMalloc((void **)&dstx3, (6 * rows * (n / 2) + 1) * sizeof(double2)) != hipSuccess) rc = FHE_ERR_HIP;  // + the status word
+        if (rc == FHE_OK && hipMemsetAsync(dstx3 + 6 * rows * (n / 2), 0, sizeof(double2), st) != hipSuccess) rc = FHE_ERR_HIP;
         if (rc == FHE_OK) {
             rc = with_torus<TorusRingF>(log_n, [&](auto wr) {
                 using WR = typename decltype(wr)::type;
@@ -339,6 +341,7 @@ int fhe_tggsw_prepare(const fhe_torus_ctx *t, int log_b, int d, const uint64_t *
     if (!k) { if (dst) (void)hipFree(dst); if (dst30) (void)hipFree(dst30); if (dstx3) (void)hipFree(dstx3); return FHE_ERR_INVALID; }
     k->t = t; k->device = t->device; k->log_n = log_n; k->log_b = log_b; k->d = d; k->count = count; k->P = P;
     k->d_rows[0] = dst; k->d_rows[1] = dst ? dst + 2 * words : nullptr; k->d_rows30 = dst30; k->d_rowsx3 = dstx3;
+    if (dstx3) k->d_status = reinterpret_cast<int *>(dstx3 + 6 * rows * (n / 2));
     *out = k;
     return FHE_OK;
 }
@@ -401,13 +404,16 @@ int fhe_tggsw_key_reserve(const fhe_torus_ctx *t, int log_b, int d, size_t n, si
     k->t = t; k->device = t->device; k->log_n = log_n; k->log_b = log_b; k->d = d; k->count = count; k->P = P;
     hipError_t e;
     if (fft64) e = hipMalloc((void **)&k->d_rowsf, words * sizeof(double2));  // 2 rows (n / 2) complex values
-    else if (usex3) e = hipMalloc((void **)&k->d_rowsx3, 3 * words * sizeof(double2));
-    else if (use30) e = hipMalloc((void **)&k->d_rows30, 3 * 2 * words * sizeof(unsigned));
+    else if (usex3) {
+        e = hipMalloc((void **)&k->d_rowsx3, (3 * words + 1) * sizeof(double2));  // + the status word
+        if (e == hipSuccess) e = hipMemset(k->d_rowsx3 + 3 * words, 0, sizeof(double2));
+        if (e == hipSuccess) k->d_status = reinterpret_cast<int *>(k->d_rowsx3 + 3 * words);
+    } else if (use30) e = hipMalloc((void **)&k->d_rows30, 3 * 2 * words * sizeof(unsigned));
     else {
         e = hipMalloc((void **)&k->d_rows[0], 4 * words * sizeof(u64));  // both primes
         if (e == hipSuccess) k->d_rows[1] = k->d_rows[0] + 2 * words;
     }
-    if (e != hipSuccess) { g_last_hip = (int)e; delete k; return FHE_ERR_HIP; }
+    if (e != hipSuccess) { g_last_hip = (int)e; fhe_tggsw_key_destroy(k); return FHE_ERR_HIP; }
     *out = k;
     return FHE_OK;
 }
@@ -434,6 +440,24 @@ int fhe_tggsw_key_form(const fhe_tggsw_key *key, int *form, int *packs_digits) {
     *form = key_form(key);
     *packs_digits = key_packs_digits(key) ? 1 : 0;
     return FHE_OK;
+}
+
+// The sticky status of the split blind rotations of device-memory calls on this key: everything enqueued on `stream` so far is waited
+// for, then FHE_ERR_TIMEOUT if a cluster gave up a wait since the word was last cleared, else FHE_OK.  clear != 0 resets the word (in
+// stream order).  A key of a form that never splits has no word and is always FHE_OK.
+int fhe_tggsw_key_status(const fhe_tggsw_key *key, void *stream, int clear) {
+    if (!key) return FHE_ERR_INVALID;
+    if (key->device < 0) return FHE_ERR_NO_DEVICE;
+    hipStream_t st = (hipStream_t)stream;
+    DeviceGuard guard(key->device);
+    if (!guard.ok) return FHE_ERR_HIP;
+    int h = 0;
+    if (key->d_status) {
+        HIP_TRY(hipMemcpyAsync(&h, key->d_status, sizeof(int), hipMemcpyDeviceToHost, st));
+        if (clear) HIP_TRY(hipMemsetAsync(key->d_status, 0, sizeof(int), st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return h == fhe::BR_STATUS_TIMEOUT ? FHE_ERR_TIMEOUT : FHE_OK;
 }
 
 // scheme/tfhe/src/tggsw.rs:100-112 `Tggsw::external_product(param, key[index], ct)`, in place on [batch][n] a / b
@@ -516,10 +540,44 @@ namespace {
 // bootstrapping.rs:84-96 on device buffers: acc = (0, v).rotate(-b), then fold cmux(brk_i, acc, acc.rotate(a_i)) (91-95): one launch, the
 // accumulator never leaves the registers of the team that owns the ciphertext.  table_of null: v [n] serves the batch; else v is
 // [n_tables][n] and ciphertext i starts from row table_of[i] (device array, in range: the kernels do not clamp).
+//
+// Where split_g says so (tfhe_split.hpp has the rule) a cluster of G workgroups owns each ciphertext (torus_split_kernels.hpp): the same
+// bits at a fraction of the latency.  Its bounded waits report through `status`: null = the key's sticky word (device-memory callers,
+// fhe_tggsw_key_status), else a word of the caller's own, zeroed by the caller.
+int split_g(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, size_t batch) {
+    const long lab = fhe::opt(fhe::OPT_TFHE_SPLIT);
+    if (lab == 0 || !brk->d_status) return 1;  // (no device is asked for its compute units on behalf of a key that never splits)
+    return fhe::tfhe_split_g(key_form(brk), brk->log_n, batch, (size_t)fhe::cu_count(t->device), lab);
+}
+
+int blind_rotate_split_dev(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, int G, const u64 *at, const u64 *bt, const u64 *v, const unsigned *table_of,
+                           u64 *oa, u64 *ob, size_t batch, hipStream_t st, int *status) {
+    using W = TorusRingF<fhe::TFHE_SPLIT_LOG_N>;
+    using Form = fhe::FormF<W, true>;
+    const size_t n = size_t(1) << brk->log_n;
+    // polled words | slabs, in a stream-ordered workspace of this call; the polled words are zeroed in front of the launch
+    const size_t ctl_bytes = fhe::tfhe_split_ctl_bytes(batch);  // a multiple of 16 at the allocation's start
+    StreamWs sws(fhe::tfhe_split_ws_bytes(batch, G, n), st);
+    if (sws.rc != FHE_OK) return sws.rc;
+    fhe::TorusSplitWs S;
+    S.ctl = sws.as<unsigned>();
+    S.slabs = reinterpret_cast<u64 *>(sws.as<unsigned char>() + ctl_bytes);
+    S.status = status ? status : brk->d_status;
+    HIP_TRY(hipMemsetAsync(S.ctl, 0, ctl_bytes, st));
+    const typename Form::Key k{brk->d_rowsx3, brk->P, t->d_twf};
+    const size_t lds = Form::lds_bytes(brk->d);
+    return fhe::with_int<2, 6>(G, [&](auto g) {
+        return fhe::launch<fhe::torusx3_blind_rotate_split_kernel<W, decltype(g)::value>>((unsigned)(batch * G), W::THREADS, lds, st, v, table_of, at, bt,
+                                                                                          (unsigned)brk->count, (unsigned)batch, k, S, oa, ob);
+    });
+}
+
 int blind_rotate_dev(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, const u64 *at, const u64 *bt, const u64 *v, const unsigned *table_of, u64 *oa,
-                     u64 *ob, size_t batch, hipStream_t st) {
+                     u64 *ob, size_t batch, hipStream_t st, int *status = nullptr) {
     const size_t n_lwe = brk->count;
     if (batch > 0x7fffffffull || n_lwe > 0x7fffffffull) return FHE_ERR_UNSUPPORTED;
+    const int G = split_g(t, brk, batch);
+    if (G > 1) return blind_rotate_split_dev(t, brk, G, at, bt, v, table_of, oa, ob, batch, st, status);
     return with_key_form<true>(t, brk, 0, [&](auto form, auto k, size_t lds) {
         using Form = typename decltype(form)::type;
         return fhe::launch_teams<blind_rotate_kernel(decltype(form){}), typename Form::Ring>(batch, lds, st, v, table_of, at, bt, (unsigned)n_lwe,
@@ -547,6 +605,32 @@ struct TableOf {
 };
 constexpr size_t MAX_TABLES = 65536;
 
+// The status word of a HOST-memory call whose blind rotation splits: a word of the call's own, so that the call reports a timeout in its
+// return value and neither reads nor clears the key's sticky word, which belongs to the asynchronous device-memory calls of any stream.
+// d: null where the call does not split (blind_rotate_dev then never writes a status).  result(): after the stream has been waited for.
+struct CallStatus {
+    std::unique_ptr<StreamWs> ws;
+    int *d = nullptr;
+    int h = 0, rc = FHE_OK;
+    CallStatus(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, size_t batch, fhe_mem mem, hipStream_t st) {
+        if (mem == FHE_MEM_DEVICE || split_g(t, brk, batch) == 1) return;
+        ws.reset(new StreamWs(sizeof(int), st));
+        rc = ws->rc;
+        if (rc == FHE_OK && hipMemsetAsync(ws->p, 0, sizeof(int), st) != hipSuccess) rc = FHE_ERR_HIP;
+        if (rc == FHE_OK) d = ws->as<int>();
+    }
+    // enqueues the read; the caller's sync_out (or result) waits for it
+    int fetch(hipStream_t st) {
+        if (d && hipMemcpyAsync(&h, d, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) return FHE_ERR_HIP;
+        return FHE_OK;
+    }
+    int result(hipStream_t st) {
+        if (!d) return FHE_OK;
+        if (hipStreamSynchronize(st) != hipSuccess) return FHE_ERR_HIP;
+        return h == fhe::BR_STATUS_TIMEOUT ? FHE_ERR_TIMEOUT : FHE_OK;
+    }
+};
+
 // fhe_tfhe_blind_rotate (table_of null, n_tables = 1: v [n]) and fhe_tfhe_blind_rotate_tables
 int blind_rotate_any(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, const uint64_t *a_tilde, const uint64_t *b_tilde, const uint64_t *v,
                      size_t n_tables, const uint32_t *table_of, uint64_t *out_a, uint64_t *out_b, size_t batch, fhe_mem mem, void *stream) {
@@ -559,9 +643,13 @@ int blind_rotate_any(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, const uin
     Mirror ma(a_tilde, n_lwe * batch, mem, true, st), mb(b_tilde, batch, mem, true, st), mv(v, n_tables * n, mem, true, st);
     Mirror moa(out_a, n * batch, mem, false, st), mob(out_b, n * batch, mem, false, st);
     if (ma.rc | mb.rc | mv.rc | moa.rc | mob.rc) return FHE_ERR_HIP;
-    int rc = blind_rotate_dev(t, brk, ma.d, mb.d, mv.d, tof.d, moa.d, mob.d, batch, st);
+    CallStatus cs(t, brk, batch, mem, st);
+    if (cs.rc != FHE_OK) return cs.rc;
+    int rc = blind_rotate_dev(t, brk, ma.d, mb.d, mv.d, tof.d, moa.d, mob.d, batch, st, cs.d);
+    if (rc == FHE_OK) rc = cs.fetch(st);
     if (rc == FHE_OK) rc = moa.sync_out(st);
     if (rc == FHE_OK) rc = mob.sync_out(st);
+    if (rc == FHE_OK) rc = cs.result(st);  // a cluster gave up a wait: its output was not written
     return rc;
 }
 }  // namespace
@@ -588,6 +676,14 @@ int fhe_tfhe_blind_rotate_tables(const fhe_torus_ctx *t, const fhe_tggsw_key *br
     if ((!a_tilde || !b_tilde || !table_of || !out_a || !out_b) && batch) return FHE_ERR_INVALID;
     if (batch == 0) return FHE_OK;
     return blind_rotate_any(t, brk, a_tilde, b_tilde, tables, n_tables, table_of, out_a, out_b, batch, mem, stream);
+}
+
+// Workgroups per ciphertext (1, 2 or 6) that a blind rotation of `batch` ciphertexts under brk would run with the options as they are:
+// what blind_rotate_dev itself asks, so every entry point that reaches it (the bootstraps, the circuits, the look-ups) runs this.
+int fhe_tfhe_blind_rotate_split(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, size_t batch, int *g_out) {
+    if (!t || !brk || brk->t != t || !g_out) return FHE_ERR_INVALID;
+    *g_out = split_g(t, brk, batch);
+    return FHE_OK;
 }
 
 // scheme/tfhe/src/tglwe.rs:115-127 `sample_extract(ct, i)` (k = 1): ct_a, ct_b [batch][n] -> TLWE (out_a [batch][n], out_b [batch])
@@ -688,7 +784,10 @@ int bootstrap_any(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, int ks_log_b
     };
     int rc = mod_switch(ma.d, at, batch * n_lwe);
     if (rc == FHE_OK) rc = mod_switch(mb.d, bt, batch);
-    if (rc == FHE_OK) rc = blind_rotate_dev(t, brk, at, bt, mv.d, tof.d, ra, rb, batch, st);
+    CallStatus cs(t, brk, batch, mem, st);
+    if (rc == FHE_OK) rc = cs.rc;
+    if (rc == FHE_OK) rc = blind_rotate_dev(t, brk, at, bt, mv.d, tof.d, ra, rb, batch, st, cs.d);
+    if (rc == FHE_OK) rc = cs.fetch(st);
     if (rc == FHE_OK)
         rc = log_funcs ? sample_extract_dense_dev(ra, rb, n, funcs, ea, eb, batch, st)
                        : fhe_tglwe_sample_extract((const U *)ra, (const U *)rb, n, 0, (U *)ea, (U *)eb, batch, FHE_MEM_DEVICE, stream);
@@ -697,6 +796,7 @@ int bootstrap_any(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, int ks_log_b
                                  FHE_MEM_DEVICE, stream);
     if (rc == FHE_OK) rc = moa.sync_out(st);
     if (rc == FHE_OK) rc = mob.sync_out(st);
+    if (rc == FHE_OK) rc = cs.result(st);  // a cluster gave up a wait: the accumulator it left unwritten went into the outputs
     return rc;
 }
 }  // namespace

@@ -31,6 +31,9 @@ struct fhe_tggsw_key {
     double2 *d_rowsf = nullptr;           // fft64 mode: [count][2d][2][N / 2] complex evaluations (torusf_kernels.hpp)
     double2 *d_rowsx3 = nullptr;          // exact through f64 transforms: [count][2d][2][3 pieces][N / 2] complex evaluations (torusf_kernels.hpp)
     fhe::TDecomp P{};
+    // sticky device-side status word of the split blind rotation (torus_split_kernels.hpp), read by fhe_tggsw_key_status: the 16 bytes
+    // behind the x3 rows, inside their allocation; null in the other forms, which never split
+    int *d_status = nullptr;
 };
 
 namespace {

@@ -907,6 +907,20 @@ class TggswKey:
         lab switch NO_PACKED_DIGITS as the launch would), else 0"""
         return self._key_form()[1]
 
+    def split(self, batch: int) -> int:
+        """fhe_tfhe_blind_rotate_split: workgroups per ciphertext (1, 2 or 6) that a blind rotation of `batch` ciphertexts under this key
+        -- alone or inside a bootstrap, a circuit, a look-up -- would use under the current options (set_option("TFHE_SPLIT", v)); above 1
+        the low-latency cluster kernel runs."""
+        g = C.c_int(0)
+        L.check(L.lib().fhe_tfhe_blind_rotate_split(self.t.handle, self._h, int(batch), C.byref(g)), "fhe_tfhe_blind_rotate_split")
+        return int(g.value)
+
+    def check(self, like=None, clear=True):
+        """fhe_tggsw_key_status: device-memory calls are asynchronous; this waits for the stream `like` lives on (torch's current stream for
+        a CUDA tensor) and raises if a split blind rotation on this key gave up a wait (FHE_ERR_TIMEOUT)."""
+        st = _buf(like)[3] if like is not None else None
+        L.check(L.lib().fhe_tggsw_key_status(self._h, st, int(clear)), "fhe_tggsw_key_status")
+
     def external_product_(self, index, ct_a, ct_b):
         pa, cnt, mem, st = _buf(ct_a)
         pb, _, _, _ = _buf(ct_b)
