@@ -64,7 +64,8 @@ int fhe_trim(void);
  * extractions from its registers, 2 = a kernel of its own reads the stored accumulators), "TFHE_SPLIT" (TFHE blind rotation: workgroups per
  * ciphertext; -1 = the library's rule, 0 = never split, 2 / 6 = that many wherever the call is eligible -- a key in the x3 form at
  * n = 1024, batch x value <= compute units of the device -- and one workgroup per ciphertext elsewhere; any other value:
- * FHE_ERR_INVALID; fhe_tfhe_blind_rotate_split tells what a call will run).  Unknown name: FHE_ERR_INVALID. */
+ * FHE_ERR_INVALID; fhe_tfhe_blind_rotate_split tells what a call will run), "NO_RANKK_FUSED" (rank-k TGGSW keys prepared while it is
+ * set take the composed route where the fused kernels would serve them: fhe_tggswk_form_for).  Unknown name: FHE_ERR_INVALID. */
 int fhe_set_option(const char *name, long value);
 
 /* Entry points that take a modulus instead of a context (fhe_rq_*, fhe_decompose, fhe_automorphism, fhe_monomial_mul,
@@ -423,10 +424,24 @@ int fhe_tlwe_lincomb(int k, const int32_t *weight, const uint64_t *const *in_a, 
  * ciphertext is (k + 1) d of them in the order tggsw.rs:80-87 builds (message on a_0: d rows, .., on a_{k-1}, on b).  Products are
  * the exact ones of the k = 1 entries; k = 1 through these entries gives bit-identical results.  1 <= k <= 8, n = 2 .. 2^15. */
 typedef struct fhe_tggswk_key fhe_tggswk_key;
-/* rows [count][(k + 1) d][k + 1][n] -> prepared (evaluation-domain) key; FHE_ERR_UNSUPPORTED if (k + 1) d n 2^(62 + log_b) >= 2^118 */
+/* The form a prepared rank-k key is in.  Both are exact: every entry below gives the same bits on either.  X3: fused kernels, one launch
+ * per entry with the ciphertext in registers (three key pieces through f64 transforms, as FHE_TGGSW_FORM_X3 at k = 1); a key takes it
+ * exactly when k = 2 or 3, n = 256 .. 1024, log_b <= 7, log_b d <= 31, (k + 1) d <= 16, (k + 1) d n 2^log_b <= 2^21 and the lab switch
+ * "NO_RANKK_FUSED" is 0.  COMPOSED: streaming kernels around batched transforms, any admitted rank and ring. */
+enum {
+    FHE_TGGSWK_FORM_COMPOSED = 0,
+    FHE_TGGSWK_FORM_X3 = 1
+};
+/* rows [count][(k + 1) d][k + 1][n] -> prepared (evaluation-domain) key; FHE_ERR_INVALID: k < 1, n not a power of two, log_b outside
+ * 1 .. 63, d outside 1 .. 64; FHE_ERR_UNSUPPORTED: k > 8, n outside 2 .. 2^15, (k + 1) d n 2^(62 + log_b) >= 2^118 */
 int fhe_tggswk_prepare(const fhe_torus_ctx *t, int k, int log_b, int d, const uint64_t *rows, size_t n, size_t count, fhe_mem mem,
                        fhe_tggswk_key **out);
 void fhe_tggswk_key_destroy(fhe_tggswk_key *key);
+/* *form: FHE_TGGSWK_FORM_*, the form `key` was prepared in */
+int fhe_tggswk_key_form(const fhe_tggswk_key *key, int *form);
+/* *form: the form fhe_tggswk_prepare would give a key of this shape if it were called now (the lab switch is read at this call).  Host
+ * only: no device is needed.  FHE_ERR_INVALID / FHE_ERR_UNSUPPORTED on the arguments fhe_tggswk_prepare refuses with them. */
+int fhe_tggswk_form_for(int k, size_t n, int log_b, int d, int *form);
 /* tggsw.rs:100-112 `Tggsw::external_product(param, key[index], ct)`, in place on ct [batch][k + 1][n] */
 int fhe_tggswk_external_product(const fhe_torus_ctx *t, const fhe_tggswk_key *key, size_t index, uint64_t *ct, size_t batch, fhe_mem mem,
                                 void *stream);
@@ -446,6 +461,17 @@ int fhe_tfhek_blind_rotate(const fhe_torus_ctx *t, const fhe_tggswk_key *brk, co
 int fhe_tfhek_bootstrap(const fhe_torus_ctx *t, const fhe_tggswk_key *brk, int ks_log_b, int ks_d, const uint64_t *ksk_a, const uint64_t *ksk_b,
                         const uint64_t *v, const uint64_t *lwe_a, const uint64_t *lwe_b, uint64_t *out_a, uint64_t *out_b, size_t batch,
                         fhe_mem mem, void *stream);
+/* fhe_tfhek_blind_rotate with one test polynomial PER CIPHERTEXT: tables [n_tables][n] encoded, table_of [batch] (NULL: every ciphertext
+ * takes tables[0]); ciphertext i rotates tables[table_of[i]] and gets the bits of fhe_tfhek_blind_rotate with that table, in either key
+ * form.  n_tables <= 65536.  Host memory: an index >= n_tables is FHE_ERR_INVALID.  Device memory: the caller guarantees
+ * table_of[i] < n_tables; the kernels clamp nothing. */
+int fhe_tfhek_blind_rotate_tables(const fhe_torus_ctx *t, const fhe_tggswk_key *brk, const uint64_t *a_tilde, const uint64_t *b_tilde,
+                                  const uint64_t *tables, size_t n_tables, const uint32_t *table_of, uint64_t *out, size_t batch, fhe_mem mem,
+                                  void *stream);
+/* fhe_tfhek_bootstrap through tables[table_of[i]] for ciphertext i; tables and indices as above */
+int fhe_tfhek_bootstrap_tables(const fhe_torus_ctx *t, const fhe_tggswk_key *brk, int ks_log_b, int ks_d, const uint64_t *ksk_a,
+                               const uint64_t *ksk_b, const uint64_t *tables, size_t n_tables, const uint32_t *table_of, const uint64_t *lwe_a,
+                               const uint64_t *lwe_b, uint64_t *out_a, uint64_t *out_b, size_t batch, fhe_mem mem, void *stream);
 
 /* ---- key material on the device ------------------------------------------------- */
 /* Randomness.  Every producer below draws from an `fhe_rng`: a 256-bit ChaCha20 key.  Value i of a draw is a word of ChaCha20

@@ -24,5 +24,6 @@ from .ring import (BootstrapKey, CkksDiagMatrix, CkksEncoder, CkksKey, CkksLinea
                    sample_binary, sample_tdg, sample_zo, tggsw_encrypt, tglwe_sk_encrypt, tlwe_ksk_gen, tlwe_sk_encrypt,
                    rlwe_share_encrypt, rlwe_pk_encrypt, rlwe_decrypt, rgsw_pk_encrypt, lwe_share_encrypt, lwe_ksk_share_gen,
                    TggswKeyK, tglwek_rotate, tglwek_sample_extract, tglwek_sk_encrypt, tggswk_encrypt,
+                   TGGSWK_FORM_COMPOSED, TGGSWK_FORM_X3, tggswk_form_for,
                    rtk_gen,
                    Rng, STREAM_AUTO, chacha20_block)

@@ -283,6 +283,10 @@ def lib():
         L.fhe_tglwek_sample_extract.argtypes = [vp, ci, sz, sz, vp, vp, sz, ci, vp]
         L.fhe_tfhek_blind_rotate.argtypes = [vp, vp, vp, vp, vp, vp, sz, ci, vp]
         L.fhe_tfhek_bootstrap.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, sz, ci, vp]
+        L.fhe_tggswk_key_form.argtypes = [vp, C.POINTER(ci)]
+        L.fhe_tggswk_form_for.argtypes = [ci, sz, ci, ci, C.POINTER(ci)]
+        L.fhe_tfhek_blind_rotate_tables.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp, sz, ci, vp]
+        L.fhe_tfhek_bootstrap_tables.argtypes = [vp, vp, ci, ci, vp, vp, vp, sz, vp, vp, vp, vp, vp, sz, ci, vp]
         L.fhe_tglwek_sk_encrypt.argtypes = [vp, ci, vp, vp, sz, sz, dbl, vp, u64, vp, ci, vp]
         L.fhe_tggswk_encrypt.argtypes = [vp, ci, ci, ci, vp, vp, sz, sz, dbl, vp, u64, vp, ci, vp]
         _lib = L

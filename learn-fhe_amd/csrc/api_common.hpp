@@ -115,10 +115,12 @@ namespace fhe {
 // TFHE_SPLIT: workgroups per ciphertext of the TFHE blind rotation (torus_split_kernels.hpp): -1 the library's rule, 0 never split, 2 / 6.
 // LUT_EXTRACT: who writes the extractions of fhe_tfhe_lut_eval: 0 the library's rule, 1 the rotation ladder from its registers, 2 a kernel
 // of its own that reads the stored accumulators (tfhe_lut_kernels.hpp).
+// NO_RANKK_FUSED: rank-k TGGSW keys prepared while it is set take the composed route (torusk_kernels.hpp) where the fused three-piece
+// kernels (torusk_fused_kernels.hpp) would serve them.
 enum Opt { OPT_NO_EDGE = 0, OPT_NO_LIMB_MAJOR, OPT_NO_W12, OPT_NO_FUSED_MUL, OPT_SMALL_BATCH, OPT_NO_PACKED_DIGITS, OPT_NO_F64_EXACT, OPT_FHEW_COMPOSED,
-           OPT_BR_SPLIT, OPT_PFKS_SPLIT, OPT_PFKS_CHUNK, OPT_LUT_EXTRACT, OPT_TFHE_SPLIT, OPT_COUNT };
+           OPT_BR_SPLIT, OPT_PFKS_SPLIT, OPT_PFKS_CHUNK, OPT_LUT_EXTRACT, OPT_TFHE_SPLIT, OPT_NO_RANKK_FUSED, OPT_COUNT };
 inline const char *const OPT_NAMES[OPT_COUNT] = {"NO_EDGE", "NO_LIMB_MAJOR", "NO_W12", "NO_FUSED_MUL", "SMALL_BATCH", "NO_PACKED_DIGITS", "NO_F64_EXACT",
-                                                 "FHEW_COMPOSED", "BR_SPLIT", "PFKS_SPLIT", "PFKS_CHUNK", "LUT_EXTRACT", "TFHE_SPLIT"};
+                                                 "FHEW_COMPOSED", "BR_SPLIT", "PFKS_SPLIT", "PFKS_CHUNK", "LUT_EXTRACT", "TFHE_SPLIT", "NO_RANKK_FUSED"};
 inline bool br_split_value_ok(long v) { return v == -1 || v == 0 || v == 2 || v == 4 || v == 8; }
 // the values an option admits (tfhe_split.hpp states TFHE_SPLIT's); the others take any
 inline bool opt_value_ok(int i, long v) {

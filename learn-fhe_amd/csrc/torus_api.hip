@@ -585,26 +585,6 @@ int blind_rotate_dev(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, const u64
     });
 }
 
-// The table index of every ciphertext on the device.  Device memory: the caller's array as it is (its range is the caller's to guarantee).
-// Host memory: every index checked against n_tables, then mirrored (two indices to a word; the staging copy lives as long as this does).
-struct TableOf {
-    std::vector<u64> staged;
-    std::unique_ptr<Mirror> m;
-    const unsigned *d = nullptr;
-    int rc = FHE_OK;
-    TableOf(const uint32_t *table_of, size_t batch, size_t n_tables, fhe_mem mem, hipStream_t st) {
-        if (mem == FHE_MEM_DEVICE) { d = table_of; return; }
-        for (size_t i = 0; i < batch; ++i)
-            if (table_of[i] >= n_tables) { rc = FHE_ERR_INVALID; return; }
-        staged.assign((batch + 1) / 2, 0);
-        std::memcpy(staged.data(), table_of, batch * sizeof(uint32_t));
-        m.reset(new Mirror(staged.data(), staged.size(), mem, true, st));
-        rc = m->rc;
-        d = (const unsigned *)m->d;
-    }
-};
-constexpr size_t MAX_TABLES = 65536;
-
 // The status word of a HOST-memory call whose blind rotation splits: a word of the call's own, so that the call reports a timeout in its
 // return value and neither reads nor clears the key's sticky word, which belongs to the asynchronous device-memory calls of any stream.
 // d: null where the call does not split (blind_rotate_dev then never writes a status).  result(): after the stream has been waited for.

@@ -1,7 +1,11 @@
 // What the torus entry points share (torus_api.hip: k = 1, fused kernels; torusk_api.hip: any rank k, composed kernels): the
-// context and prepared-key structures and a small host helper.
+// context and prepared-key structures, a small host helper and the per-ciphertext table index of the blind rotations.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <memory>
+#include <vector>
 
 #include "api_common.hpp"
 #include "ctx.hpp"
@@ -51,4 +55,24 @@ inline int make_tdecomp(int log_b, int d, fhe::TDecomp *P) {
     P->rb = rb;
     return FHE_OK;
 }
+
+// The table index of every ciphertext on the device.  Device memory: the caller's array as it is (its range is the caller's to guarantee).
+// Host memory: every index checked against n_tables, then mirrored (two indices to a word; the staging copy lives as long as this does).
+struct TableOf {
+    std::vector<u64> staged;
+    std::unique_ptr<Mirror> m;
+    const unsigned *d = nullptr;
+    int rc = FHE_OK;
+    TableOf(const uint32_t *table_of, size_t batch, size_t n_tables, fhe_mem mem, hipStream_t st) {
+        if (mem == FHE_MEM_DEVICE) { d = table_of; return; }
+        for (size_t i = 0; i < batch; ++i)
+            if (table_of[i] >= n_tables) { rc = FHE_ERR_INVALID; return; }
+        staged.assign((batch + 1) / 2, 0);
+        std::memcpy(staged.data(), table_of, batch * sizeof(uint32_t));
+        m.reset(new Mirror(staged.data(), staged.size(), mem, true, st));
+        rc = m->rc;
+        d = (const unsigned *)m->d;
+    }
+};
+constexpr size_t MAX_TABLES = 65536;
 }  // namespace

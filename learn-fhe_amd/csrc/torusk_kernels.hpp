@@ -91,16 +91,17 @@ FHE_HEADER_KERNEL void torusk_crt_kernel(const u64 *__restrict__ r, u64 *out, un
     }
 }
 
-// bootstrapping.rs:90-92: acc = (0, .., 0, v).rotate(-b~) per ciphertext; acc [batch][k + 1][n]
-FHE_HEADER_KERNEL void torusk_init_acc_kernel(const u64 *__restrict__ v, const u64 *__restrict__ b_tilde, u64 *__restrict__ acc, unsigned n, unsigned k1,
-                                              size_t batch) {
+// bootstrapping.rs:90-92: acc = (0, .., 0, v).rotate(-b~) per ciphertext; acc [batch][k + 1][n].  table_of null: v [n] serves the batch; else
+// ciphertext c starts from v + table_of[c] * n (not range-checked here: torus_forms.hpp blind_rotate_body has the contract)
+FHE_HEADER_KERNEL void torusk_init_acc_kernel(const u64 *__restrict__ v, const unsigned *__restrict__ table_of, const u64 *__restrict__ b_tilde,
+                                              u64 *__restrict__ acc, unsigned n, unsigned k1, size_t batch) {
     const size_t total = size_t(n) * k1 * batch;
     for (size_t idx = blockIdx.x * size_t(blockDim.x) + threadIdx.x; idx < total; idx += size_t(gridDim.x) * blockDim.x) {
         const unsigned i = unsigned(idx % n);
         const size_t pc = idx / n, c = pc / k1;
         const unsigned pl = unsigned(pc - c * k1);
         const unsigned rneg = (0u - (unsigned)b_tilde[c]) & (2 * n - 1);
-        acc[idx] = pl + 1 == k1 ? torusk_rot_read(v, n, i, rneg) : 0;
+        acc[idx] = pl + 1 == k1 ? torusk_rot_read(table_of ? v + size_t(table_of[c]) * n : v, n, i, rneg) : 0;
     }
 }
 

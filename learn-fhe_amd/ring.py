@@ -1062,6 +1062,51 @@ class TggswKeyK:
                                             _buf(out_b)[0], batch, mem, st), "fhe_tfhek_bootstrap")
         return out_a, out_b
 
+    def form(self):
+        """fhe_tggswk_key_form: TGGSWK_FORM_COMPOSED (0) or TGGSWK_FORM_X3 (1, the fused kernels), fixed when the key was prepared"""
+        form = C.c_int()
+        L.check(L.lib().fhe_tggswk_key_form(self._h, C.byref(form)), "fhe_tggswk_key_form")
+        return form.value
+
+    def _table_of(self, table_of, batch, mem):
+        if table_of is None:
+            return None
+        pi, n_idx, mem_i = _buf32(table_of)
+        assert n_idx == batch and mem_i == mem
+        return pi
+
+    def blind_rotate_tables(self, a_tilde, b_tilde, tables, table_of):
+        """bootstrapping.rs:84-96 with one test polynomial per ciphertext: tables [n_tables][n] encoded, table_of [batch] (uint32 / torch
+        int32; None: tables[0] for all); ciphertext i rotates tables[table_of[i]] -> [batch][k + 1][n]."""
+        pa, _, mem, st = _buf(a_tilde)
+        pb, batch, _, _ = _buf(b_tilde)
+        pt, cnt, _, _ = _buf(tables)
+        out = _like(a_tilde, (batch, self.k + 1, self.n))
+        L.check(L.lib().fhe_tfhek_blind_rotate_tables(self.t.handle, self._h, pa, pb, pt, cnt // self.n, self._table_of(table_of, batch, mem), _buf(out)[0],
+                                                      batch, mem, st), "fhe_tfhek_blind_rotate_tables")
+        return out
+
+    def bootstrap_tables(self, ks_log_b, ks_d, ksk_a, ksk_b, tables, table_of, lwe_a, lwe_b):
+        """bootstrapping.rs:78-82 in one call, ciphertext i through tables[table_of[i]] -> (a [batch][n_lwe], b [batch])."""
+        pka, _, mem, st = _buf(ksk_a)
+        pt, cnt, _, _ = _buf(tables)
+        pb, batch, _, _ = _buf(lwe_b)
+        out_a, out_b = _like(lwe_a, (batch, self.count)), _like(lwe_a, (batch,))
+        L.check(L.lib().fhe_tfhek_bootstrap_tables(self.t.handle, self._h, ks_log_b, ks_d, pka, _buf(ksk_b)[0], pt, cnt // self.n,
+                                                   self._table_of(table_of, batch, mem), _buf(lwe_a)[0], pb, _buf(out_a)[0], _buf(out_b)[0], batch, mem, st),
+                "fhe_tfhek_bootstrap_tables")
+        return out_a, out_b
+
+
+TGGSWK_FORM_COMPOSED, TGGSWK_FORM_X3 = 0, 1  # FHE_TGGSWK_FORM_* (include/fhe_ring.h)
+
+
+def tggswk_form_for(k, n, log_b, d):
+    """fhe_tggswk_form_for: the form TggswKeyK(t, k, log_b, d, rows, n) would take now (host only; reads set_option("NO_RANKK_FUSED", v))"""
+    form = C.c_int()
+    L.check(L.lib().fhe_tggswk_form_for(k, n, log_b, d, C.byref(form)), "fhe_tggswk_form_for")
+    return form.value
+
 
 def tglwek_rotate(ct, k, n, i):
     """scheme/tfhe/src/tglwe.rs:61-66 for [batch][k + 1][n] ciphertexts."""
