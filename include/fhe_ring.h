@@ -65,7 +65,10 @@ int fhe_trim(void);
  * ciphertext; -1 = the library's rule, 0 = never split, 2 / 6 = that many wherever the call is eligible -- a key in the x3 form at
  * n = 1024, batch x value <= compute units of the device -- and one workgroup per ciphertext elsewhere; any other value:
  * FHE_ERR_INVALID; fhe_tfhe_blind_rotate_split tells what a call will run), "NO_RANKK_FUSED" (rank-k TGGSW keys prepared while it is
- * set take the composed route where the fused kernels would serve them: fhe_tggswk_form_for).  Unknown name: FHE_ERR_INVALID. */
+ * set take the composed route where the fused kernels would serve them: fhe_tggswk_form_for), "PACK_SPLIT" (fhe_tlwe_pack: 0 = the library's
+ * rule, k >= 1 = k chunks of key rows per pack, clamped to what exactness needs and to one row per chunk), "PACK_ROUTE" (fhe_tlwe_pack:
+ * 0 = the library's rule, 1 = the transforms, 2 = the scalar digits x key product and one rotate-and-add kernel), "PACK_SLAB"
+ * (fhe_tlwe_pack: packs per launch group; 0 = what 256 MiB of scratch hold, s >= 1 = at most s).  Unknown name: FHE_ERR_INVALID. */
 int fhe_set_option(const char *name, long value);
 
 /* Entry points that take a modulus instead of a context (fhe_rq_*, fhe_decompose, fhe_automorphism, fhe_monomial_mul,
@@ -1123,6 +1126,35 @@ int fhe_tfhe_wop_pbs(const fhe_torus_ctx *t, const fhe_tggsw_key *brk, int ks_lo
                      int cb_d, int pf_log_b, int pf_d, const uint64_t *pfksk, int m, const uint64_t *lwe_a, const uint64_t *lwe_b, fhe_tggsw_key *sel_key,
                      size_t first_index, const uint64_t *polys, size_t n_out, int out_ks_log_b, int out_ks_d, const uint64_t *out_ksk_a,
                      const uint64_t *out_ksk_b, size_t n_lwe_out, uint64_t *out_a, uint64_t *out_b, size_t batch, fhe_mem mem, void *stream);
+
+/* ---- packing key switch (k = 1): many TLWE ciphertexts into one TGLWE ciphertext ----
+ * The key is fhe_tlwe_pfksk_gen's with n_funcs = 1 and funcs = [1, 0, ..., 0] (the identity); gadget conventions as above.
+ *
+ * The prepared form: every row's a and b, once, in the evaluation domain of the context's two 60-bit primes -- an exact form for
+ * every admitted gadget (R rows are summed before an inverse transform, R n 2^(64 + log_b) < 2^118; fhe_tlwe_pack cuts the rows into
+ * such chunks itself), and keeps a device copy of the rows as they came: calls with count <= 16 run the scalar digits x key product of
+ * fhe_tlwe_pfks on it and one rotate-and-add kernel, which is faster there (the key takes 3 x the words of pfksk on the device).
+ * pfksk [d (n_in + 1)][1][2][n], read on `stream`; the entry returns when the prepared rows are complete, so
+ * the key then serves calls on any stream.  log_b d > 64, n_in = 0, n not one of the context's rings (256 .. 2048):
+ * FHE_ERR_INVALID; log_b > 31: FHE_ERR_UNSUPPORTED. */
+typedef struct fhe_tlwe_pack_key fhe_tlwe_pack_key;
+int  fhe_tlwe_pack_key_prepare(const fhe_torus_ctx *t, int log_b, int d, const uint64_t *pfksk, size_t n_in, size_t n, fhe_mem mem, void *stream,
+                               fhe_tlwe_pack_key **out);
+void fhe_tlwe_pack_key_destroy(fhe_tlwe_pack_key *key);
+/* The packing key switch (tlwe.rs:144-153's digit x key product against rows that are TGLWE ciphertexts, tglwe.rs:91-103, each result
+ * moved into place as tglwe.rs:61-66 rotates).  ct_a [packs][count][n_in], ct_b [packs][count]; out_a, out_b [packs][n].  With
+ * c_{g,r,i} = ct_a[g][r][i] for i < n_in and c_{g,r,n_in} = ct_b[g][r], the TGLWE ciphertext out[g] is
+ *   sum_{r < count} X^(r stride) * sum_j sum_{i <= n_in} digit_j(c_{g,r,i}) * pfksk[j (n_in + 1) + i]
+ * over Z/2^64 on both halves, digits those of fhe_torus_decompose: its phase at coefficient r stride is the phase of input (g, r) plus
+ * the rounding of the digits, elsewhere the phase is error only.  The same bits as fhe_tlwe_pfks (n_funcs = 1, group = 1) on the
+ * packs count inputs, fhe_tglwe_rotate by r stride and the sum mod 2^64, in every schedule and on either route (lab switches
+ * "PACK_SPLIT", "PACK_ROUTE", "PACK_SLAB").
+ * count < 1, stride < 1, (count - 1) stride >= n, a key of another context: FHE_ERR_INVALID.  The outputs must not overlap the inputs:
+ * FHE_MEM_DEVICE calls whose out_a or out_b equals ct_a or ct_b, and any call with out_a == out_b, return FHE_ERR_INVALID.  packs = 0:
+ * FHE_OK, nothing touched.  Device-memory calls are stream ordered: no hipMalloc, no host wait; the digit polynomials (or the scalar route's rows)
+ * are scratch from the library's stream-ordered pool. */
+int fhe_tlwe_pack(const fhe_torus_ctx *t, const fhe_tlwe_pack_key *key, const uint64_t *ct_a, const uint64_t *ct_b, size_t count, size_t stride,
+                  size_t packs, uint64_t *out_a, uint64_t *out_b, fhe_mem mem, void *stream);
 
 #ifdef __cplusplus
 }

@@ -154,6 +154,11 @@ def lib():
         L.fhe_tfhe_wop_front.argtypes = [vp, vp, vp, vp, sz, sz, sz, ci, ci, vp, vp, vp, vp, ci, vp]
         L.fhe_tfhe_wop_selectors.argtypes = [vp, vp, ci, ci, vp, vp, ci, ci, ci, ci, vp, ci, vp, vp, vp, vp, vp, vp, sz, ci, vp]
         L.fhe_tfhe_wop_pbs.argtypes = [vp, vp, ci, ci, vp, vp, ci, ci, ci, ci, vp, ci, vp, vp, vp, sz, vp, sz, ci, ci, vp, vp, sz, vp, vp, sz, ci, vp]
+        # packing key switch: many TLWE ciphertexts into one TGLWE (tfhe_pack_api.hip)
+        L.fhe_tlwe_pack_key_prepare.argtypes = [vp, ci, ci, vp, sz, sz, ci, vp, C.POINTER(vp)]
+        L.fhe_tlwe_pack_key_destroy.argtypes = [vp]
+        L.fhe_tlwe_pack_key_destroy.restype = None
+        L.fhe_tlwe_pack.argtypes = [vp, vp, vp, vp, sz, sz, sz, vp, vp, ci, vp]
         L.fhe_tggsw_key_reserve.argtypes = [vp, ci, ci, sz, sz, ci, C.POINTER(vp)]
         L.fhe_tggsw_key_fill.argtypes = [vp, sz, vp, vp, sz, ci, vp]
         L.fhe_tggsw_key_form.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]

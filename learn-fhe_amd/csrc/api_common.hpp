@@ -117,10 +117,16 @@ namespace fhe {
 // of its own that reads the stored accumulators (tfhe_lut_kernels.hpp).
 // NO_RANKK_FUSED: rank-k TGGSW keys prepared while it is set take the composed route (torusk_kernels.hpp) where the fused three-piece
 // kernels (torusk_fused_kernels.hpp) would serve them.
+// PACK_SPLIT: teams that share the key rows of one pack of fhe_tlwe_pack (tfhe_pack_kernels.hpp): 0 the library's rule, k >= 1: k chunks of
+// rows per pack, clamped to what the exactness bound needs and to one row per chunk (tfhe_pack.hpp: pack_plan).
+// PACK_ROUTE: which product fhe_tlwe_pack runs: 0 the library's rule (tfhe_pack.hpp: pack_scalar_route), 1 the transforms, 2 the scalar
+// digits x key product of fhe_tlwe_pfks followed by one rotate-and-add kernel.  PACK_SLAB: packs one launch group of fhe_tlwe_pack works on:
+// 0 the library's rule (what 256 MiB of scratch hold), s >= 1: at most s.
 enum Opt { OPT_NO_EDGE = 0, OPT_NO_LIMB_MAJOR, OPT_NO_W12, OPT_NO_FUSED_MUL, OPT_SMALL_BATCH, OPT_NO_PACKED_DIGITS, OPT_NO_F64_EXACT, OPT_FHEW_COMPOSED,
-           OPT_BR_SPLIT, OPT_PFKS_SPLIT, OPT_PFKS_CHUNK, OPT_LUT_EXTRACT, OPT_TFHE_SPLIT, OPT_NO_RANKK_FUSED, OPT_COUNT };
+           OPT_BR_SPLIT, OPT_PFKS_SPLIT, OPT_PFKS_CHUNK, OPT_LUT_EXTRACT, OPT_TFHE_SPLIT, OPT_NO_RANKK_FUSED, OPT_PACK_SPLIT, OPT_PACK_ROUTE, OPT_PACK_SLAB,
+           OPT_COUNT };
 inline const char *const OPT_NAMES[OPT_COUNT] = {"NO_EDGE", "NO_LIMB_MAJOR", "NO_W12", "NO_FUSED_MUL", "SMALL_BATCH", "NO_PACKED_DIGITS", "NO_F64_EXACT",
-                                                 "FHEW_COMPOSED", "BR_SPLIT", "PFKS_SPLIT", "PFKS_CHUNK", "LUT_EXTRACT", "TFHE_SPLIT", "NO_RANKK_FUSED"};
+                                                 "FHEW_COMPOSED", "BR_SPLIT", "PFKS_SPLIT", "PFKS_CHUNK", "LUT_EXTRACT", "TFHE_SPLIT", "NO_RANKK_FUSED", "PACK_SPLIT", "PACK_ROUTE", "PACK_SLAB"};
 inline bool br_split_value_ok(long v) { return v == -1 || v == 0 || v == 2 || v == 4 || v == 8; }
 // the values an option admits (tfhe_split.hpp states TFHE_SPLIT's); the others take any
 inline bool opt_value_ok(int i, long v) {
