@@ -1156,6 +1156,46 @@ void fhe_tlwe_pack_key_destroy(fhe_tlwe_pack_key *key);
 int fhe_tlwe_pack(const fhe_torus_ctx *t, const fhe_tlwe_pack_key *key, const uint64_t *ct_a, const uint64_t *ct_b, size_t count, size_t stride,
                   size_t packs, uint64_t *out_a, uint64_t *out_b, fhe_mem mem, void *stream);
 
+/* ---- TGLWE ciphertext product (k = 1): tensor, exact division by 2^p, relinearisation ----
+ * Ring Z[X]/(X^n + 1), n = 256 .. 2048.  s(w) is the word w read as a signed 64-bit integer (c64.rs:23-27, as fhe_torus_mul reads its
+ * operands); the phase of (a, b) is b - a S (tglwe.rs:101, 110); rnd_p(x) = floor((x + 2^(p - 1)) / 2^p) per coefficient, 1 <= p <= 63.
+ *   tensor : C2 = rnd_p(s(A1) s(A2)),  C1 = rnd_p(s(A1) s(B2) + s(B1) s(A2)),  C0 = rnd_p(s(B1) s(B2))   mod 2^64,
+ *            the products and the sum over the INTEGERS (|coefficient| up to n 2^127); phase C0 - C1 S + C2 S^2
+ *   key    : row j < d is a TGLWE encryption of h_j S^2, h_j = 2^(64 - log_b (d - j)) -- the weight of digit j of
+ *            fhe_torus_decompose, least significant first, as in the rows of fhe_tggsw_encrypt --, S^2 the integer square of the binary
+ *            key polynomial mod 2^64; rlk_a, rlk_b [d][n]
+ *   relin  : out_a = C1 + sum_j digit_j(C2) RLK_j.a,  out_b = C0 + sum_j digit_j(C2) RLK_j.b   mod 2^64, digits those of
+ *            fhe_torus_decompose(log_b, d); the same bits as fhe_tggsw_external_product of the pseudo-TGGSW [RLK rows; d zero rows]
+ *            on (C2, 0), plus (C1, C0)
+ *   mul    : relin(tensor(ct0, ct1, p)), those bits exactly
+ * What the caller owns: with phases 2^p m_i + e_i (as integers, |phase| < 2^63) the product's phase is 2^p m1 m2 + m1 e2 + m2 e1 +
+ * e1 e2 / 2^p, plus u e 2^(64 - p)-sized wrap terms whenever s(B) - s(A) S leaves [-2^63, 2^63) (|u| <= (n + 1) / 2), plus the
+ * rounding of C0, C1 (1/2, ||S||_1 / 2), of C2 against S^2 (||S^2||_1 / 2), of the digits (n ||S^2||_inf 2^(63 - log_b d)) and the
+ * key's noise times the digits; DESIGN.md 9.9 has the bound.  m1 m2 2^p must itself fit the torus.
+ * Gadgets: log_b >= 1, d >= 1, log_b d <= 64, d n 2^(64 + log_b) < 2^118, else FHE_ERR_UNSUPPORTED.  Another n, p outside 1 .. 63, a
+ * NULL pointer, a key of another context: FHE_ERR_INVALID.  Neither writes anything.  batch = 0: FHE_OK, nothing touched.
+ * Device-memory calls are stream ordered: no hipMalloc, no host wait. */
+typedef struct fhe_tglwe_relin_key fhe_tglwe_relin_key;
+/* S^2 and the d plaintext rows h_j S^2 on the device, encrypted as fhe_tglwe_sk_encrypt encrypts `d` rows under (rng, stream_id): bit for
+ * bit that entry's output on those plaintext rows.  sk [n] binary. */
+int fhe_tglwe_rlk_gen(const fhe_torus_ctx *t, int log_b, int d, const uint64_t *sk, size_t n, double std_dev, const fhe_rng *rng, uint64_t stream_id,
+                      uint64_t *rlk_a, uint64_t *rlk_b, fhe_mem mem, void *stream);
+/* The rows in the evaluation domain of the context's two 60-bit primes.  Read on `stream`; the entry returns when the prepared rows are
+ * complete, so the key then serves calls on any stream. */
+int  fhe_tglwe_rlk_prepare(const fhe_torus_ctx *t, int log_b, int d, const uint64_t *rlk_a, const uint64_t *rlk_b, size_t n, fhe_mem mem, void *stream,
+                           fhe_tglwe_relin_key **out);
+void fhe_tglwe_rlk_destroy(fhe_tglwe_relin_key *key);
+/* ct0, ct1 halves and c0, c1, c2: [batch][n].  Public so that several tensors can be added mod 2^64 and relinearised once.  The
+ * [batch][n] ranges of the outputs must not overlap the inputs or each other: FHE_ERR_INVALID. */
+int fhe_tglwe_tensor(const fhe_torus_ctx *t, const uint64_t *ct0_a, const uint64_t *ct0_b, const uint64_t *ct1_a, const uint64_t *ct1_b, size_t n,
+                     int log_delta, uint64_t *c0, uint64_t *c1, uint64_t *c2, size_t batch, fhe_mem mem, void *stream);
+/* (out_a, out_b) may be (c1, c0). */
+int fhe_tglwe_relin(const fhe_torus_ctx *t, const fhe_tglwe_relin_key *key, const uint64_t *c0, const uint64_t *c1, const uint64_t *c2, uint64_t *out_a,
+                    uint64_t *out_b, size_t batch, fhe_mem mem, void *stream);
+/* One launch.  ct0 may be ct1 (a square); out may be either input: a team reads all it needs before it stores. */
+int fhe_tglwe_mul(const fhe_torus_ctx *t, const fhe_tglwe_relin_key *key, const uint64_t *ct0_a, const uint64_t *ct0_b, const uint64_t *ct1_a,
+                  const uint64_t *ct1_b, int log_delta, uint64_t *out_a, uint64_t *out_b, size_t batch, fhe_mem mem, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

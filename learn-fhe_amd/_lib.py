@@ -159,6 +159,14 @@ def lib():
         L.fhe_tlwe_pack_key_destroy.argtypes = [vp]
         L.fhe_tlwe_pack_key_destroy.restype = None
         L.fhe_tlwe_pack.argtypes = [vp, vp, vp, vp, sz, sz, sz, vp, vp, ci, vp]
+        # TGLWE ciphertext product: tensor, relinearise, fused (tfhe_mul_api.hip)
+        L.fhe_tglwe_rlk_gen.argtypes = [vp, ci, ci, vp, sz, C.c_double, vp, C.c_uint64, vp, vp, ci, vp]
+        L.fhe_tglwe_rlk_prepare.argtypes = [vp, ci, ci, vp, vp, sz, ci, vp, C.POINTER(vp)]
+        L.fhe_tglwe_rlk_destroy.argtypes = [vp]
+        L.fhe_tglwe_rlk_destroy.restype = None
+        L.fhe_tglwe_tensor.argtypes = [vp, vp, vp, vp, vp, sz, ci, vp, vp, vp, sz, ci, vp]
+        L.fhe_tglwe_relin.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, ci, vp]
+        L.fhe_tglwe_mul.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp, vp, sz, ci, vp]
         L.fhe_tggsw_key_reserve.argtypes = [vp, ci, ci, sz, sz, ci, C.POINTER(vp)]
         L.fhe_tggsw_key_fill.argtypes = [vp, sz, vp, vp, sz, ci, vp]
         L.fhe_tggsw_key_form.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]

@@ -77,7 +77,9 @@ __device__ __forceinline__ u64 crt2_mod64(u64 r0, u64 r1, const TorusConsts &T) 
 
 // One gadget product pass for ONE prime over register-resident operands (coefficient layout): outputs the residues of
 // sum_l rows[l].a * limb_l and sum_l rows[l].b * limb_l (exact integers) mod that prime, coefficient layout.
-template <class W>
+// BOTH (the external product): limbs = decompose(da) ++ decompose(db) over 2d rows.  !BOTH (the relinearisation of tfhe_mul_kernels.hpp):
+// the limbs of da alone over d rows; db is not read.
+template <class W, bool BOTH = true>
 __device__ __forceinline__ void team_torus_gadget(const u64 (&da)[W::E], const u64 (&db)[W::E],
                                                   const u64 *__restrict__ rows, const TDecomp &P, u64 p, int lane, u64 *lds, const Barrett &B,
                                                   const typename ArithPM<60>::K &k, u64 (&sa)[W::E],
@@ -94,8 +96,8 @@ __device__ __forceinline__ void team_torus_gadget(const u64 (&da)[W::E], const u
     KeyRow<W> kr;  // one limb ahead (fhew_kernels.hpp)
     load_row<W>(kr, rows, lane);
 #pragma unroll 1
-    for (int j = 0; j < 2 * P.d; ++j) {
-        if (j == P.d) {
+    for (int j = 0; j < (BOTH ? 2 * P.d : P.d); ++j) {
+        if (BOTH && j == P.d) {
 #pragma unroll
             for (int e = 0; e < E; ++e) st[e] = tdecomp_init(db[e], P);
         }
@@ -107,7 +109,7 @@ __device__ __forceinline__ void team_torus_gadget(const u64 (&da)[W::E], const u
         }
         fwd_run<A, typename W::C, W::LOG_N, W::LOG_E, 0, true, W::WAVE>(x, lane, nullptr, lds, true, k);
         mac_row<A, W>(x, ma, mb, kr, j, K, k);
-        if (j + 1 < 2 * P.d) load_row<W>(kr, rows + size_t(j + 1) * 2 * W::N, lane);
+        if (j + 1 < (BOTH ? 2 * P.d : P.d)) load_row<W>(kr, rows + size_t(j + 1) * 2 * W::N, lane);
     }
 #pragma unroll
     for (int e = 0; e < E; ++e) { sa[e] = A::mac_finish(ma[e], k); sb[e] = A::mac_finish(mb[e], k); }
