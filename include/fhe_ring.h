@@ -1196,6 +1196,56 @@ int fhe_tglwe_relin(const fhe_torus_ctx *t, const fhe_tglwe_relin_key *key, cons
 int fhe_tglwe_mul(const fhe_torus_ctx *t, const fhe_tglwe_relin_key *key, const uint64_t *ct0_a, const uint64_t *ct0_b, const uint64_t *ct1_a,
                   const uint64_t *ct1_b, int log_delta, uint64_t *out_a, uint64_t *out_b, size_t batch, fhe_mem mem, void *stream);
 
+/* ---- TGLWE automorphism key switch, trace and ring packing (k = 1) ----
+ * Ring Z[X]/(X^n + 1), n = 256 .. 2048, words mod 2^64, phase of (a, b) = b - a S; digit_j and h_j = 2^(64 - log_b (d - j)) those of
+ * fhe_torus_decompose and of the relinearisation key above.
+ *   sigma_g   : coefficient i of p goes to i g mod 2n; a position >= n means position - n with the sign flipped.  g odd, 1 <= g < 2n
+ *   key       : AK_{g,j}, j < d: a TGLWE encryption of -h_j sigma_g(S) mod 2^64 under S; atk_a, atk_b [n_g][d][n] for the set gs [n_g]
+ *   autks_g   : out_a = sum_j digit_j(sigma_g(a)) AK_{g,j}.a,  out_b = sigma_g(b) + sum_j digit_j(sigma_g(a)) AK_{g,j}.b   mod 2^64;
+ *               phase = sigma_g(phase(a, b)) + the rounding of the digits + the key's noise times the digits
+ *   trace     : for u = hi, hi - 1, ..., lo + 1: ct <- ct + autks_{2^u + 1}(ct), 0 <= lo < hi <= log2 n.  With hi = log2 n the
+ *               coefficients at multiples of 2^(hi - lo) are kept, times 2^(hi - lo), and the others become zero; lo = 0 keeps
+ *               coefficient 0 alone, times n
+ *   embed     : the TLWE ciphertext (a'[n], b') under the coefficients of S -> the TGLWE ciphertext whose
+ *               fhe_tglwe_sample_extract(index 0) it is: a[0] = a'[0], a[i] = -a'[n - i], b = b' at coefficient 0 and zero elsewhere
+ *   merge_l   : (E, O) -> (E + X^(n/l) O) + autks_{l+1}(E - X^(n/l) O),  l = 2, 4, ..., count
+ *   ring_pack : count = 2^c inputs, c <= log2 n: P(x) = embed(x) for one input, P(x_0 .. x_{m-1}) = merge_m(P(even-indexed),
+ *               P(odd-indexed)); out = trace(P(all), lo = c, hi = log2 n) (count = n: P(all) itself).  n phase(x_r) sits at coefficient
+ *               r (n / count) for every count, error only elsewhere.  It needs the keys g = 2^u + 1 for u = 1 .. log2 n
+ * What the caller owns: every step doubles what it keeps, so phases leave multiplied by 2^(hi - lo), n for a pack: an input at scale
+ * Delta decodes at n Delta and the top log2 n bits of its message space must be empty.  Noise: err <- 2 err + ks per step,
+ * err_out <= n err_in + (n - 1) ks for a pack, ks = n 2^(63 - log_b d) (0 at log_b d = 64) + d n 2^(log_b - 1) |e_key|_inf; DESIGN.md
+ * 9.10.  The packing key of fhe_tlwe_pack has d (n_in + 1) rows, this one d log2 n: a factor (n + 1) / log2 n, about 100 at n = 1024.
+ * Gadgets: the rule of the relinearisation key (log_b >= 1, d >= 1, log_b d <= 64, d n 2^(64 + log_b) < 2^118), else
+ * FHE_ERR_UNSUPPORTED.  Another n, an even g or g >= 2n, a g twice in a set or with no key in it, count not a power of two or > n,
+ * lo >= hi or hi > log2 n, a NULL pointer, a key of another context: FHE_ERR_INVALID.  Rejected calls write nothing.  batch or
+ * packs = 0: FHE_OK, nothing touched.  Device-memory calls are stream ordered: no hipMalloc, no host wait. */
+typedef struct fhe_tglwe_auto_key fhe_tglwe_auto_key;
+/* The n_g d plaintext rows -h_j sigma_g(S) on the device, encrypted as fhe_tglwe_sk_encrypt encrypts `n_g d` rows under (rng, stream_id):
+ * bit for bit that entry's output on those plaintext rows.  sk [n] binary; gs [n_g] is a host array in both memory kinds, 1 <= n_g <= n. */
+int fhe_tglwe_atk_gen(const fhe_torus_ctx *t, int log_b, int d, const uint64_t *sk, size_t n, const uint32_t *gs, size_t n_g, double std_dev,
+                      const fhe_rng *rng, uint64_t stream_id, uint64_t *atk_a, uint64_t *atk_b, fhe_mem mem, void *stream);
+/* The whole set in the evaluation domain of the context's two 60-bit primes (the layout and the transform of fhe_tglwe_rlk_prepare).
+ * Read on `stream`; the entry returns when the prepared rows are complete, so the key then serves calls on any stream. */
+int  fhe_tglwe_atk_prepare(const fhe_torus_ctx *t, int log_b, int d, const uint64_t *atk_a, const uint64_t *atk_b, size_t n, const uint32_t *gs, size_t n_g,
+                           fhe_mem mem, void *stream, fhe_tglwe_auto_key **out);
+void fhe_tglwe_atk_destroy(fhe_tglwe_auto_key *key);
+/* autks_g on [batch][n] halves, one launch.  out may be the input (out_a == ct_a and out_b == ct_b: a team reads its ciphertext before
+ * it stores); any other overlap among the four [batch][n] ranges: FHE_ERR_INVALID. */
+int fhe_tglwe_automorphism(const fhe_torus_ctx *t, const fhe_tglwe_auto_key *key, uint32_t g, const uint64_t *ct_a, const uint64_t *ct_b, uint64_t *out_a,
+                           uint64_t *out_b, size_t batch, fhe_mem mem, void *stream);
+/* The hi - lo steps in ONE launch: the ciphertext stays in its team's registers, only the input and the result cross memory.  The same
+ * bits as fhe_tglwe_automorphism and an addition mod 2^64 per step.  Aliasing as fhe_tglwe_automorphism. */
+int fhe_tglwe_trace(const fhe_torus_ctx *t, const fhe_tglwe_auto_key *key, int lo, int hi, const uint64_t *ct_a, const uint64_t *ct_b, uint64_t *out_a,
+                    uint64_t *out_b, size_t batch, fhe_mem mem, void *stream);
+/* ct_a [packs][count][n], ct_b [packs][count] -> out_a, out_b [packs][n].  One launch per tree level over packs count / l teams (level
+ * l = 2 reads the TLWE inputs: the embedding and the rotation by n / l are index arithmetic in the load), then the trace launch; count = 1
+ * is embed + the full trace in one launch.  The inner levels are scratch from the library's stream-ordered pool; large `packs` run in
+ * slabs (lab switch "PACK_SLAB").  The same bits as embed, fhe_tglwe_rotate, fhe_tglwe_automorphism and additions mod 2^64 composed.
+ * The outputs must overlap neither the inputs nor each other: FHE_ERR_INVALID. */
+int fhe_tlwe_ring_pack(const fhe_torus_ctx *t, const fhe_tglwe_auto_key *key, const uint64_t *ct_a, const uint64_t *ct_b, size_t count, size_t packs,
+                       uint64_t *out_a, uint64_t *out_b, fhe_mem mem, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

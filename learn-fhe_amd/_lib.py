@@ -167,6 +167,15 @@ def lib():
         L.fhe_tglwe_tensor.argtypes = [vp, vp, vp, vp, vp, sz, ci, vp, vp, vp, sz, ci, vp]
         L.fhe_tglwe_relin.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, ci, vp]
         L.fhe_tglwe_mul.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp, vp, sz, ci, vp]
+        # TGLWE automorphism key switch, trace, ring packing (tfhe_trace_api.hip)
+        u32p = C.POINTER(C.c_uint32)
+        L.fhe_tglwe_atk_gen.argtypes = [vp, ci, ci, vp, sz, u32p, sz, C.c_double, vp, C.c_uint64, vp, vp, ci, vp]
+        L.fhe_tglwe_atk_prepare.argtypes = [vp, ci, ci, vp, vp, sz, u32p, sz, ci, vp, C.POINTER(vp)]
+        L.fhe_tglwe_atk_destroy.argtypes = [vp]
+        L.fhe_tglwe_atk_destroy.restype = None
+        L.fhe_tglwe_automorphism.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, vp, sz, ci, vp]
+        L.fhe_tglwe_trace.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp, sz, ci, vp]
+        L.fhe_tlwe_ring_pack.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, ci, vp]
         L.fhe_tggsw_key_reserve.argtypes = [vp, ci, ci, sz, sz, ci, C.POINTER(vp)]
         L.fhe_tggsw_key_fill.argtypes = [vp, sz, vp, vp, sz, ci, vp]
         L.fhe_tggsw_key_form.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]

@@ -9,6 +9,7 @@
 #include "torus_dispatch.hpp"
 #include "tfhe_mul.hpp"
 #include "tfhe_mul_kernels.hpp"
+#include "tglwe_key_rows.hpp"
 
 // The rows of a relinearisation key in the evaluation domain of the two 60-bit primes: per prime [d][2][n], key_perm layout.
 struct fhe_tglwe_relin_key {
@@ -120,20 +121,7 @@ int fhe_tglwe_rlk_prepare(const fhe_torus_ctx *t, int log_b, int d, const uint64
     k->d_rows[1] = k->d_rows[0] + words;
     {
         Mirror ma(rlk_a, half, mem, true, st), mb(rlk_b, half, mem, true, st);
-        StreamWs wsp(words * sizeof(u64), st);  // the residues of one prime, a then b, transformed in place
-        rc = (ma.rc | mb.rc) ? FHE_ERR_HIP : wsp.rc;
-        u64 *ta = wsp.as<u64>(), *tb = ta + half;
-        for (int pi = 0; pi < 2 && rc == FHE_OK; ++pi) {
-            const u64 p = pi ? t->T.p1 : t->T.p0;
-            rc = fhe::launch<fhe::torus_residue_kernel>(grid_for(half), 256, 0, st, (const u64 *)ma.d, ta, half, p);
-            if (rc == FHE_OK) rc = fhe::launch<fhe::torus_residue_kernel>(grid_for(half), 256, 0, st, (const u64 *)mb.d, tb, half, p);
-            if (rc == FHE_OK) rc = fhe::ntt_fwd_multi(t->d_descs + pi, 1, ta, log_n, 2 * size_t(d), st, 60);
-            if (rc == FHE_OK)
-                rc = with_torus<TorusRing>(log_n, [&](auto wr) {
-                    using W = typename decltype(wr)::type;
-                    return fhe::launch<fhe::key_permute_kernel<W>>(grid_for(half), 256, 0, st, (const u64 *)ta, (const u64 *)tb, k->d_rows[pi], (size_t)d, 60);
-                });
-        }
+        rc = (ma.rc | mb.rc) ? FHE_ERR_HIP : tglwe_rows_prepare(t, log_n, ma.d, mb.d, (size_t)d, k->d_rows, st);
         // the key may serve calls on any stream from here on: wait for its rows (and, with them, for the staging copies)
         if (hipStreamSynchronize(st) != hipSuccess && rc == FHE_OK) { (void)hipGetLastError(); rc = FHE_ERR_HIP; }
     }
