@@ -612,6 +612,63 @@ void fhe_ckks_diag_matrix_destroy(fhe_ckks_diag_matrix *m);
 int fhe_ckks_mul_mat(const fhe_ckks_diag_matrix *m, const uint64_t *ct_b, const uint64_t *ct_a, uint64_t *out_b, uint64_t *out_a, size_t batch,
                      fhe_mem mem, void *stream);
 
+/* ---- hoisted CKKS rotations and the double-hoisted diagonal-matrix product --------------------------------------
+ * Opt-in entries beside fhe_ckks_rotate and fhe_ckks_mul_mat, which keep the reference's bits.  The entries below are NOT the
+ * reference's `rotate` / `mul_mat`: they extend the ciphertext to qs || ps BEFORE the automorphism (the reference after it), so that
+ * one extension and one set of forward transforms serve every rotation of a ciphertext.
+ *
+ * Notation: n the ring degree, qs (L primes) and ps (K primes) the bases of the context, P = prod ps, sigma_t the automorphism
+ * X -> X^t, t_j = 5^j mod 2n, ext = fhe_rns_extend_bases (with its f64 correction), (*) the ring product limb by limb over qs || ps.
+ * For a ciphertext (b, a) over qs, coefficient domain:
+ *     a~ = (a || ext(a)),     b~ = P b  (limb q_l: (P mod q_l) b_l; the p-limbs are zero),
+ *     u_0 = (b~, P a),
+ *     u_j = ( sigma_{t_j}(b~) + k_j.b (*) sigma_{t_j}(a~),  k_j.a (*) sigma_{t_j}(a~) )     for j != 0 with the rotation key (k_j.b, k_j.a).
+ *
+ * fhe_rns_automorphism_eval: sigma_t on polynomials that already are in the evaluation domain (extended = 0: [batch][L][n] over qs,
+ * 1: [batch][L+K][n] over qs ++ ps), in != out.  A pure permutation of the n evaluation points of every limb, no signs: with psi the
+ * 2n-th root of the transform, index k of fhe_rns_ntt_fwd's output holds the value at psi^(2 brev(k) + 1) (fhe_ctx_twiddles documents
+ * the table that gives this order), and the output's value at psi^e is the input's value at psi^(e t).  For every x
+ *     automorphism_eval(ntt_fwd(x)) == ntt_fwd(fhe_rns_automorphism(x))     bit for bit.
+ * t is taken mod 2n; an even t returns FHE_ERR_UNSUPPORTED. */
+int fhe_rns_automorphism_eval(const fhe_rns_ctx *rns, int extended, int64_t t, const uint64_t *in, uint64_t *out, size_t n, size_t batch,
+                              fhe_mem mem, void *stream);
+/* Single hoisting: `count` rotations of ONE ciphertext batch.
+ *     out_r = ( rescale_k(u_r.b), rescale_k(u_r.a) ),     u_r of amount amounts[r] with keys[r],     rescale_k = fhe_rns_rescale_k.
+ * One ext, L + K forward transforms of a~ and L of b~ for the whole call; per rotation the permutation fused into the product with
+ * the key, 2 (L + K) inverse transforms and two rescale_k.  amounts[r] == 0 takes no key (keys[r] may be NULL) and copies the input
+ * (P b divided by P is b; u_0 has zero p-limbs, the one input that puts rescale_k's base conversion on a rounding tie, so it is not run).
+ *   ct_b, ct_a    [batch][L][n] over qs, coefficient domain; n up to the limit of fhe_ckks_key_switch;
+ *   keys          [count] rotation keys prepared on `rns` for this n (fhe_ckks_ksk_prepare); a missing key or one of another context
+ *                 or ring is FHE_ERR_INVALID and nothing is written;
+ *   out_b, out_a  [count] pointers to [batch][L][n], none overlapping the inputs or one another.
+ * NOT the bits of fhe_ckks_rotate, which extends sigma(a).  What holds instead: P b + x divided by P is b + rescale_k(x) exactly, so
+ * out_r == fhe_ckks_rotate(keys[r], t_r) wherever no coefficient of a lies within f64 error of a rounding tie of the base conversion
+ * (ext commutes with sigma but for the sign of that correction), and out_r decrypts to the same plaintext everywhere: the two differ
+ * by a multiple of Q in a~, which the key switch absorbs into its noise.  Stream-ordered workspace: 8 n batch (3 (L + K) + L) bytes. */
+int fhe_ckks_rotate_many(const fhe_rns_ctx *rns, size_t n, const uint32_t *amounts, const fhe_ckks_key *const *keys, int count,
+                         const uint64_t *ct_b, const uint64_t *ct_a, uint64_t *const *out_b, uint64_t *const *out_a, size_t batch, fhe_mem mem,
+                         void *stream);
+/* Double hoisting: the diagonal-matrix product with the baby-step sums kept in qs || ps.  The arguments are those of
+ * fhe_ckks_diag_matrix_prepare / fhe_ckks_mul_mat with ONE difference: `diags` is [terms][L+K][n] over qs ++ ps, the plaintexts lifted
+ * exactly to the extended base (the centred integer coefficients reduced modulo every prime of qs and ps), coefficient domain.  They
+ * are transformed once at prepare and kept on the device (8 terms (L + K) n bytes).  For giant step i, D_ij the diagonal of term (i, j):
+ *     w_i = sum_{j in js(i)} D_ij (*) u_j      on both halves, over qs || ps,
+ *     v_i = rescale( rescale_k(w_i) )          fhe_rns_rescale_k, then fhe_rns_rescale on rns_hi: L - 1 limbs,
+ *     out = sum_i rotate_i(v_i),               rotate_0 = identity; fhe_ckks_rotate on rns_lo with giant_keys, as fhe_ckks_mul_mat.
+ * Transforms per call, the giant steps' key switches apart: 2 L + K forward, 2 (L + K) n_giant inverse; no per-term product on the
+ * last limb.  The result is not the bits of fhe_ckks_mul_mat (fewer roundings, at other places); it decrypts to the same product.
+ * Stream-ordered workspace of fhe_ckks_mul_mat_hoisted, in bytes:
+ *     8 n batch ( (L + K) + L + 2 n_giant (L + K) + 2 n_giant L + 2 (L - 1) )
+ * (a~ | b~ | w, later the v_i | rescale_k(w) | one giant step's automorphism), + the giant steps' key switch's own. */
+typedef struct fhe_ckks_diag_matrix_hoisted fhe_ckks_diag_matrix_hoisted;
+int fhe_ckks_diag_matrix_prepare_hoisted(const fhe_rns_ctx *rns_hi, const fhe_rns_ctx *rns_lo, size_t n, const uint32_t *giant, int n_giant,
+                                         const uint32_t *baby, int n_baby, const uint8_t *present, const uint64_t *diags,
+                                         const fhe_ckks_key *const *baby_keys, const fhe_ckks_key *const *giant_keys, fhe_mem mem,
+                                         fhe_ckks_diag_matrix_hoisted **out);
+void fhe_ckks_diag_matrix_hoisted_destroy(fhe_ckks_diag_matrix_hoisted *m);
+int fhe_ckks_mul_mat_hoisted(const fhe_ckks_diag_matrix_hoisted *m, const uint64_t *ct_b, const uint64_t *ct_a, uint64_t *out_b, uint64_t *out_a,
+                             size_t batch, fhe_mem mem, void *stream);
+
 /* ---- CKKS encode / decode: scheme/ckks/src/ckks.rs:186-213 `Ckks::encode` / `Ckks::decode` over scheme/ckks/src/sfft.rs:7-72, in
  * double-double arithmetic (an unevaluated sum of two f64, about 106 bits) in place of the reference's 256-bit software floats
  * (util/src/complex/f256.rs).  Complex slots travel as two f64 arrays: `*_hi` [batch][l][2] (re, im: the memory of a complex128

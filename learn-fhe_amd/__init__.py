@@ -22,7 +22,9 @@ from . import tfhe_mul  # noqa: F401
 from .tfhe_mul import RelinKey, rlk_gen  # noqa: F401
 from . import tfhe_trace  # noqa: F401
 from .tfhe_trace import AutoKey, atk_gen, galois_set, ring_pack  # noqa: F401
-from .ring import (BootstrapKey, CkksDiagMatrix, CkksEncoder, CkksKey, CkksLinearPlan, CkksLinearTransform, CkksShard, Fhew, GadgetKey, NttContext, RnsContext, TggswKey, TorusContext,  # noqa: F401
+from . import ckks_hoist  # noqa: F401
+from .ckks_hoist import extend_plain, mul_mat_hoisted_composed, rotate_many_composed  # noqa: F401
+from .ring import (BootstrapKey, CkksDiagMatrix, CkksDiagMatrixHoisted, CkksEncoder, CkksKey, CkksLinearPlan, CkksLinearTransform, CkksShard, Fhew, GadgetKey, NttContext, RnsContext, TggswKey, TorusContext,  # noqa: F401
                    ak_t, automorphism, bsgs_split, decompose, lwe_key_switch, lwe_lincomb, lwe_mod_switch, monomial_mul, rlwe_sample_extract, rq_add, rq_from_i64, rq_neg, rq_scalar_mul, rq_sub,
                    tglwe_sample_extract, tglwe_sample_extract_many, tlwe_key_switch, tlwe_lincomb, torus_decompose, tglwe_rotate,
                    power_up, rgsw_encrypt, rlwe_ksk_gen, rlwe_sk_encrypt, sample_dg, sample_torus, sample_uniform,

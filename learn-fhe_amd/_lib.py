@@ -245,6 +245,13 @@ def lib():
         L.fhe_ckks_diag_matrix_destroy.argtypes = [vp]
         L.fhe_ckks_diag_matrix_destroy.restype = None
         L.fhe_ckks_mul_mat.argtypes = [vp, vp, vp, vp, vp, sz, ci, vp]
+        # hoisted rotations and the double-hoisted diagonal-matrix product (ckks_hoist_api.hip)
+        L.fhe_rns_automorphism_eval.argtypes = [vp, ci, C.c_int64, vp, vp, sz, sz, ci, vp]
+        L.fhe_ckks_rotate_many.argtypes = [vp, sz, u32p, C.POINTER(vp), ci, vp, vp, C.POINTER(vp), C.POINTER(vp), sz, ci, vp]
+        L.fhe_ckks_diag_matrix_prepare_hoisted.argtypes = [vp, vp, sz, u32p, ci, u32p, ci, C.c_char_p, vp, C.POINTER(vp), C.POINTER(vp), ci, C.POINTER(vp)]
+        L.fhe_ckks_diag_matrix_hoisted_destroy.argtypes = [vp]
+        L.fhe_ckks_diag_matrix_hoisted_destroy.restype = None
+        L.fhe_ckks_mul_mat_hoisted.argtypes = [vp, vp, vp, vp, vp, sz, ci, vp]
         # CKKS encode / decode (ckks_encode_api.hip)
         dblp = C.POINTER(C.c_double)
         L.fhe_ckks_encoder_create.argtypes = [sz, ci, C.POINTER(vp)]

@@ -1177,4 +1177,14 @@ int ckks_rescale_last_dev(const fhe_rns_ctx *r, const u64 *in, u64 *out, size_t 
     const size_t L = r->L;
     return launch_rescale(r, true, rescale_in_block(in, L * n, r->L - 1, 1, n), out, (L - 1) * n, nullptr, 0, n, batch, st);
 }
+// what csrc/ckks_hoist_api.hip lifts and lowers with: the key switch's own extension (ext [batch][L+K][n] = in || extend_bases(in),
+// the launch of key_switch_dev's plain route) and fhe_rns_rescale_k on device pointers
+int ckks_extend_dev(const fhe_rns_ctx *r, const u64 *in, u64 *ext, size_t n, size_t batch, hipStream_t st) {
+    const size_t L = r->L, lk = size_t(r->L + r->K);
+    return launch_extend(r, in, L * n, ext + L * n, lk * n, n, batch, st, ext, lk * n);
+}
+int ckks_rescale_k_dev(const fhe_rns_ctx *r, const u64 *in, u64 *out, size_t n, size_t batch, hipStream_t st) {
+    const size_t lk = size_t(r->L + r->K);
+    return launch_rescale(r, false, rescale_in_block(in, lk * n, r->L, r->K, n), out, size_t(r->L) * n, nullptr, 0, n, batch, st);
+}
 }  // namespace fhe

@@ -40,6 +40,10 @@ int ckks_key_switch_dev(const fhe_rns_ctx *r, const fhe_ckks_key *key, const u64
 int ckks_ring_status(const fhe_rns_ctx *r, size_t n);
 // rns.rs:99-101 `rescale()` on device pointers (rns_api.hip, what fhe_rns_rescale launches): in [batch][L][n] -> out [batch][L-1][n]
 int ckks_rescale_last_dev(const fhe_rns_ctx *r, const u64 *in, u64 *out, size_t n, size_t batch, hipStream_t st);
+// ext [batch][L+K][n] = in || extend_bases(in) (in [batch][L][n]; rns_api.hip launch_extend as the key switch calls it) and
+// fhe_rns_rescale_k on device pointers (in [batch][L+K][n] -> out [batch][L][n]): what ckks_hoist_api.hip lifts and lowers with
+int ckks_extend_dev(const fhe_rns_ctx *r, const u64 *in, u64 *ext, size_t n, size_t batch, hipStream_t st);
+int ckks_rescale_k_dev(const fhe_rns_ctx *r, const u64 *in, u64 *out, size_t n, size_t batch, hipStream_t st);
 // the borrowed level chain of a prepared linear transform (ckks_linear_api.hip) or polynomial evaluator (ckks_poly_api.hip), depth + 1
 // contexts with levels[0] the input's, and its ring degree: what fhe_ckks_bootstrap_prepare checks its stages against
 const std::vector<const fhe_rns_ctx *> &ckks_linear_transform_levels(const fhe_ckks_linear_transform *t, size_t *n);

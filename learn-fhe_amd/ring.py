@@ -505,6 +505,15 @@ class RnsContext:
         L.check(L.lib().fhe_rns_automorphism(self._h, t, p, po, n, batch, mem, st), "fhe_rns_automorphism")
         return out
 
+    def automorphism_eval(self, limbs, t, n, extended=False):
+        """sigma_t on evaluation-domain polynomials [batch][L (+K)][n] (include/fhe_ring.h fhe_rns_automorphism_eval): a permutation."""
+        p, cnt, mem, st = _buf(limbs)
+        k = self.L + self.K if extended else self.L
+        batch = cnt // (k * n)
+        out = _like(limbs, (batch, k, n))
+        L.check(L.lib().fhe_rns_automorphism_eval(self._h, int(extended), t, p, _buf(out)[0], n, batch, mem, st), "fhe_rns_automorphism_eval")
+        return out
+
 
 class CkksKey:
     """A CKKS key-switching key (scheme/ckks/src/ckks.rs:86-88) prepared in the evaluation domain."""
@@ -548,6 +557,24 @@ class CkksKey:
         ob, oa = _like(ct0_b, (batch, self.rns.L - 1, self.n)), _like(ct0_b, (batch, self.rns.L - 1, self.n))
         L.check(L.lib().fhe_ckks_mul(self.rns.handle, self._h, p0b, p0a, p1b, p1a, _buf(ob)[0], _buf(oa)[0], batch, mem, st), "fhe_ckks_mul")
         return ob, oa
+
+    @staticmethod
+    def rotate_many(rns, n, amounts, keys, ct_b, ct_a, outs=None):
+        """Single hoisting (include/fhe_ring.h fhe_ckks_rotate_many): the rotations of (ct_b, ct_a) [batch][L][n] by every j of
+        `amounts` with keys[r] the CkksKey of amounts[r] (None where the amount is 0) -> [(b, a), ...]; the input is left as it was.
+        `outs`: the output pairs to write instead of new ones."""
+        pb, cnt, mem, st = _buf(ct_b)
+        batch = cnt // (rns.L * n)
+        amounts, keys = list(amounts), list(keys)
+        assert len(amounts) == len(keys)
+        if outs is None:
+            outs = [(_like(ct_b, (batch, rns.L, n)), _like(ct_b, (batch, rns.L, n))) for _ in amounts]
+        cnt_r = len(amounts)
+        ptrs = lambda xs: (C.c_void_p * max(cnt_r, 1))(*[_buf(x)[0] for x in xs])  # noqa: E731
+        kh = (C.c_void_p * max(cnt_r, 1))(*[k.handle if k is not None else None for k in keys])
+        L.check(L.lib().fhe_ckks_rotate_many(rns.handle, n, (C.c_uint32 * max(cnt_r, 1))(*amounts), kh, cnt_r, pb, _buf(ct_a)[0],
+                                             ptrs([o[0] for o in outs]), ptrs([o[1] for o in outs]), batch, mem, st), "fhe_ckks_rotate_many")
+        return outs
 
 
 def bsgs_split(diag_indices):
@@ -604,6 +631,44 @@ class CkksDiagMatrix:
         batch = cnt // (self.rns_hi.L * self.n)
         ob, oa = _like(ct_b, (batch, self.rns_hi.L - 1, self.n)), _like(ct_b, (batch, self.rns_hi.L - 1, self.n))
         L.check(L.lib().fhe_ckks_mul_mat(self._h, pb, _buf(ct_a)[0], _buf(ob)[0], _buf(oa)[0], batch, mem, st), "fhe_ckks_mul_mat")
+        return ob, oa
+
+
+class CkksDiagMatrixHoisted:
+    """The double-hoisted diagonal-matrix product (include/fhe_ring.h fhe_ckks_diag_matrix_prepare_hoisted): the arguments of
+    CkksDiagMatrix, except that diags is [terms][L+K][n] over rns_hi.qs + rns_hi.ps (ckks_hoist.extend_plain lifts encoded plaintexts).
+    Not the bits of CkksDiagMatrix.apply: the same plaintext product with fewer roundings.  Keeps the contexts and the keys alive."""
+
+    def __init__(self, rns_hi: RnsContext, rns_lo: RnsContext, n, split, diags, baby_keys, giant_keys):
+        self.rns_hi, self.rns_lo, self.n = rns_hi, rns_lo, n
+        self.giant = sorted(split)
+        self.baby = sorted({j for js in split.values() for j in js})
+        self.terms = sum(len(set(js)) for js in split.values())
+        self._keys = (dict(baby_keys), dict(giant_keys))  # borrowed by the library
+        present = bytes(1 if j in split[i] else 0 for i in self.giant for j in self.baby)
+        handle = lambda keys, idx: keys[idx].handle if idx and keys.get(idx) is not None else None  # noqa: E731
+        bk = (C.c_void_p * len(self.baby))(*[handle(self._keys[0], j) for j in self.baby])
+        gk = (C.c_void_p * len(self.giant))(*[handle(self._keys[1], i) for i in self.giant])
+        pd, cnt, mem, _ = _buf(diags)
+        if cnt != self.terms * (rns_hi.L + rns_hi.K) * n:  # the C entry takes a pointer: the limb count is checked here
+            raise L.FheError(1, "CkksDiagMatrixHoisted: diags must be [terms][L+K][n]")
+        self._h = C.c_void_p()
+        L.check(L.lib().fhe_ckks_diag_matrix_prepare_hoisted(rns_hi.handle, rns_lo.handle, n, (C.c_uint32 * len(self.giant))(*self.giant),
+                                                              len(self.giant), (C.c_uint32 * len(self.baby))(*self.baby), len(self.baby), present, pd,
+                                                              bk, gk, mem, C.byref(self._h)), "fhe_ckks_diag_matrix_prepare_hoisted")
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and L is not None and getattr(L, "lib", None):  # (module globals are gone at interpreter shutdown)
+            L.lib().fhe_ckks_diag_matrix_hoisted_destroy(h)
+
+    def apply(self, ct_b, ct_a, out=None):
+        """[batch][L][n] over rns_hi -> (b, a) [batch][L-1][n] over rns_lo."""
+        pb, cnt, mem, st = _buf(ct_b)
+        batch = cnt // (self.rns_hi.L * self.n)
+        shape = (batch, self.rns_hi.L - 1, self.n)
+        ob, oa = out if out is not None else (_like(ct_b, shape), _like(ct_b, shape))
+        L.check(L.lib().fhe_ckks_mul_mat_hoisted(self._h, pb, _buf(ct_a)[0], _buf(ob)[0], _buf(oa)[0], batch, mem, st), "fhe_ckks_mul_mat_hoisted")
         return ob, oa
 
 
